@@ -21,10 +21,21 @@ one batch overlap those of the next (e.g. the latency-bound final kernel of step
 k beside the cost kernel of step k+1) -- the serving shape of the batch mode;
 every step still computes its whole batch.  value = frames of all K steps / wall
 time.  --inflight 1 runs the steps strictly one after the other
-(single_batch_ms reports that latency in every run).  The roofline's stage
-times come from a separate one-in-flight pass (overlapped launches have no
-kernel duration); profile rocprofv3 runs with --inflight 1 so its kernel
+(single_batch_ms reports that latency in every --full run).  The roofline's
+stage times come from a separate one-in-flight pass (overlapped launches have
+no kernel duration); profile rocprofv3 runs with --inflight 1 so its kernel
 averages agree.
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, ms_per_step = wall time of the K steps / K, the workload).
+--full adds everything that takes runs of its own after the timed steps: the
+one-in-flight stage pass with single_batch_ms, stages_ms_per_step and the
+roofline, the CPU baseline and the parity samples against the oracle, the
+per-config table (--profile-steps, --no-cpu-baseline, --cpu-threads and
+--no-configs select among these).  --dump-outputs DIR writes the maps of the
+last timed step (on rank 0 the gathered global batch when there is a gather) to
+DIR/disparity.npy as float32; the inputs are seeded, so two builds run with the
+same arguments can be compared map for map.
 
 Run: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no
 WORLD_SIZE in the environment, bench.py starts the N ranks itself (a child
@@ -91,7 +102,16 @@ def parse(argv=None):
                     help="skip the per-config table (BASELINE configs 1, 2, 3, 5; single GPU only)")
     ap.add_argument("--dry", action="store_true",
                     help="CPU rehearsal of launcher + gather (gloo, trivial compute)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the "
+                         "one-in-flight stage pass and roofline, the CPU baseline and parity samples "
+                         "against the oracle, the per-config table")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -370,6 +390,25 @@ def config_table(mvsv, _lib, dev, steps=10, warmup=3):
     return recs
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # of all --dump-outputs files together
+
+
+def dump_outputs(dirname, arrays):
+    """Write each named array as dirname/<name>.npy in float32.  An array over its
+    share of DUMP_LIMIT_BYTES is cut to a fixed sample of its flattened elements
+    (indices drawn once from a generator seeded with SEED0, ascending), the same
+    in every run of the same shape."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    budget = (DUMP_LIMIT_BYTES - 1024 * len(arrays)) // (4 * len(arrays))  # elements per array
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size > budget:
+            idx = np.sort(np.random.default_rng(SEED0).integers(0, a.size, size=budget))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def cpu_info():
     model = ""
     try:
@@ -558,72 +597,49 @@ def main(argv=None):
     check_contexts()  # no map of the timed steps came from a given-up hand-off
     elapsed = t1 - t0
     step_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(K)] if n_in == 1 else None
-    # stage times for the roofline: a separate pass, one step after the other
-    # on the default context (with batches in flight the launches overlap, so
-    # their spans are not kernel durations)
-    ctx = _lib.context(local)
-    pout = torch.empty((F, H, W), dtype=torch.int16, device=dev)
-    compute(Lt, Rt, pout)
-    barrier()
-    _lib.profile_reset(ctx)
-    _lib.profile_enable(ctx, True)
-    P = max(1, args.profile_steps)
-    p0, p1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    p0.record()
-    for _ in range(P):
+    prof, P, single_ms = {}, 0, None
+    if args.full:
+        # stage times for the roofline: a separate pass, one step after the other
+        # on the default context (with batches in flight the launches overlap, so
+        # their spans are not kernel durations)
+        ctx = _lib.context(local)
+        pout = torch.empty((F, H, W), dtype=torch.int16, device=dev)
         compute(Lt, Rt, pout)
-    p1.record()
-    barrier()
-    _lib.profile_enable(ctx, False)
-    prof = _lib.profile_read(ctx)
-    _lib.synchronize(local)
-    single_ms = p0.elapsed_time(p1) / P
+        barrier()
+        _lib.profile_reset(ctx)
+        _lib.profile_enable(ctx, True)
+        P = max(1, args.profile_steps)
+        p0, p1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        p0.record()
+        for _ in range(P):
+            compute(Lt, Rt, pout)
+        p1.record()
+        barrier()
+        _lib.profile_enable(ctx, False)
+        prof = _lib.profile_read(ctx)
+        _lib.synchronize(local)
+        single_ms = p0.elapsed_time(p1) / P
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # the gathered global batch of the last timed step, on rank 0 (host copy,
-    # outside the timed region) for the parity sample below
+    # what a caller of the timed path holds after the last timed step: this
+    # rank's maps, or on rank 0 the gathered global batch (host copy, outside the
+    # timed region) for the parity sample and --dump-outputs below
     gathered = None
-    if gather and rank == 0 and batch.gathered is not None:
+    if gather and rank == 0 and batch.gathered is not None and (args.full or args.dump_outputs):
         gathered = [g.cpu().numpy() for g in batch.gathered]
 
     if rank == 0:
         ms_per_step = elapsed / K * 1e3
         mpix = world * F * W * H * K / elapsed / 1e6
-        stages = {k: {"ms_per_step": v[0] / P, "launches_per_step": v[1] / P}
-                  for k, v in prof.items() if v[1]}
-        strips = D in (32, 64, 128, 256)
-        # dominant KERNEL: path_aggregation is the span of the strip and line
-        # kernels (which run concurrently) when both are timed separately
-        kernels = [k for k in stages if not (k == "path_aggregation" and "path_strips" in stages)]
-        dom = max(kernels, key=lambda k: stages[k]["ms_per_step"])
-        launches = stages[dom]["launches_per_step"]
-        avg_launch_s = stages[dom]["ms_per_step"] / launches / 1e3
         # SURVEY.md §8(d) compulsory bytes per frame (8 paths): u8 L+R in, int16
         # map out, one int16 write + read of the cross-sweep aggregate per (px, d)
         comp = 4 * W * H * (1 + D)
-        alg_bytes_per_launch = comp * F / launches
-        achieved = alg_bytes_per_launch / avg_launch_s / 1e9
-        impl_bytes_per_launch = stage_bytes(dom, F, W, H, W1, D, ndir, acc, strips, residual, bitslice,
-                                            side) / launches
-        workload = f"sgbm_{W}x{H}_d{D}_{ndir}path_batch{F}"
-        sha = kernel_source_sha()
-        pmc, traffic_note = _summary(PMC_FILE, workload, sha, "PMC")
-        traffic = pmc.get("stages", {}).get(dom, {}).get("hbm_bytes_per_launch") if pmc else None
-        if pmc:
-            traffic_note += " (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE in separate passes)"
-        sq, sq_note = _summary(SQ_FILE, workload, sha, "SQ")
-        valu_frac = sq.get("stages", {}).get(dom, {}).get("valu_util") if sq else None
-        if sq:
-            sq_note += " (rocprofv3 SQ_ACTIVE_INST_VALU x4 / (1024 SIMDs x GRBM_GUI_ACTIVE/8))"
-        # measured HBM utilisation of the dominant kernel: counter bytes over its
-        # live launch time, against the same peak
-        hbm_util = traffic / avg_launch_s / 1e9 / HBM_PEAK_GBPS if traffic else None
-        if valu_frac is not None and hbm_util is not None:
-            bound = "valu" if valu_frac > hbm_util else "hbm"
-        else:
-            bound = "unmeasured"
+        if args.dump_outputs:
+            last = batch.last_out if n_in > 1 else out
+            dump_outputs(args.dump_outputs, {
+                "disparity": np.concatenate(gathered) if gathered is not None else last.cpu().numpy()})
         res = {
             "metric": "Mpix disparities/sec (SGBM 128-disp, 8-path) at 1/2/4/8 GPUs; % HBM roofline",
             "value": round(mpix, 2),
@@ -634,8 +650,6 @@ def main(argv=None):
             "ms_per_step": round(ms_per_step, 4),
             "median_ms_per_step": round(statistics.median(step_ms), 4) if step_ms else None,
             "inflight": n_in,
-            "single_batch_ms": round(single_ms, 4),
-            "single_batch_mpix_s": round(F * W * H / single_ms / 1e3, 2),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -649,29 +663,63 @@ def main(argv=None):
                        "launch": "torch.distributed.run" if distributed else "single process",
                        "batches_in_flight": n_in,
                        "parallelism": f"frame-parallel x{world}"},
-            "roofline": {"kernel": dom, "bound": bound,
-                         "bound_rule": "larger of the measured utilisations hbm_util (PMC traffic) and "
-                                       "valu_frac (SQ counters) of the dominant kernel",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                         "traffic_source": traffic_note,
-                         "hbm_util": round(hbm_util, 4) if hbm_util is not None else None,
-                         "valu_frac": valu_frac,
-                         "valu_source": sq_note,
-                         "pipeline_frac": round(comp * F * K / elapsed / 1e9 / HBM_PEAK_GBPS, 5),
-                         "pipeline_frac_rule": "SURVEY.md §8(d) bytes of the whole step over its wall time / peak",
-                         "algorithmic_bytes_per_launch": int(alg_bytes_per_launch),
-                         "algorithmic_bytes": "SURVEY.md §8(d): 4*W*H*(1+D) per frame x frames per launch",
-                         "avg_launch_ms": round(avg_launch_s * 1e3, 4),
-                         "impl_bytes_per_launch": int(impl_bytes_per_launch),
-                         "impl_frac": round(impl_bytes_per_launch / avg_launch_s / 1e9 / HBM_PEAK_GBPS, 4)},
             "pipeline_compulsory": {"bytes_per_frame": comp,
                                     "achieved_GBps_per_gpu": round(comp * F * K / elapsed / 1e9, 1),
                                     "frac_of_peak": round(comp * F * K / elapsed / 1e9 / HBM_PEAK_GBPS, 5)},
-            "stages_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in stages.items()},
-            "stages_source": f"HIP events around each stage, {P} steps one after the other (no overlap)",
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            stages = {k: {"ms_per_step": v[0] / P, "launches_per_step": v[1] / P}
+                      for k, v in prof.items() if v[1]}
+            strips = D in (32, 64, 128, 256)
+            # dominant KERNEL: path_aggregation is the span of the strip and line
+            # kernels (which run concurrently) when both are timed separately
+            kernels = [k for k in stages if not (k == "path_aggregation" and "path_strips" in stages)]
+            dom = max(kernels, key=lambda k: stages[k]["ms_per_step"])
+            launches = stages[dom]["launches_per_step"]
+            avg_launch_s = stages[dom]["ms_per_step"] / launches / 1e3
+            alg_bytes_per_launch = comp * F / launches
+            achieved = alg_bytes_per_launch / avg_launch_s / 1e9
+            impl_bytes_per_launch = stage_bytes(dom, F, W, H, W1, D, ndir, acc, strips, residual, bitslice,
+                                                side) / launches
+            workload = f"sgbm_{W}x{H}_d{D}_{ndir}path_batch{F}"
+            sha = kernel_source_sha()
+            pmc, traffic_note = _summary(PMC_FILE, workload, sha, "PMC")
+            traffic = pmc.get("stages", {}).get(dom, {}).get("hbm_bytes_per_launch") if pmc else None
+            if pmc:
+                traffic_note += " (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE in separate passes)"
+            sq, sq_note = _summary(SQ_FILE, workload, sha, "SQ")
+            valu_frac = sq.get("stages", {}).get(dom, {}).get("valu_util") if sq else None
+            if sq:
+                sq_note += " (rocprofv3 SQ_ACTIVE_INST_VALU x4 / (1024 SIMDs x GRBM_GUI_ACTIVE/8))"
+            # measured HBM utilisation of the dominant kernel: counter bytes over its
+            # live launch time, against the same peak
+            hbm_util = traffic / avg_launch_s / 1e9 / HBM_PEAK_GBPS if traffic else None
+            if valu_frac is not None and hbm_util is not None:
+                bound = "valu" if valu_frac > hbm_util else "hbm"
+            else:
+                bound = "unmeasured"
+            res["single_batch_ms"] = round(single_ms, 4)
+            res["single_batch_mpix_s"] = round(F * W * H / single_ms / 1e3, 2)
+            res["roofline"] = {
+                "kernel": dom, "bound": bound,
+                "bound_rule": "larger of the measured utilisations hbm_util (PMC traffic) and "
+                              "valu_frac (SQ counters) of the dominant kernel",
+                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                "traffic_source": traffic_note,
+                "hbm_util": round(hbm_util, 4) if hbm_util is not None else None,
+                "valu_frac": valu_frac,
+                "valu_source": sq_note,
+                "pipeline_frac": round(comp * F * K / elapsed / 1e9 / HBM_PEAK_GBPS, 5),
+                "pipeline_frac_rule": "SURVEY.md §8(d) bytes of the whole step over its wall time / peak",
+                "algorithmic_bytes_per_launch": int(alg_bytes_per_launch),
+                "algorithmic_bytes": "SURVEY.md §8(d): 4*W*H*(1+D) per frame x frames per launch",
+                "avg_launch_ms": round(avg_launch_s * 1e3, 4),
+                "impl_bytes_per_launch": int(impl_bytes_per_launch),
+                "impl_frac": round(impl_bytes_per_launch / avg_launch_s / 1e9 / HBM_PEAK_GBPS, 4)}
+            res["stages_ms_per_step"] = {k: round(v["ms_per_step"], 4) for k, v in stages.items()}
+            res["stages_source"] = f"HIP events around each stage, {P} steps one after the other (no overlap)"
+        if args.full and world == 1 and not args.no_cpu_baseline:
             info = cpu_info()
             thr = args.cpu_threads or max(1, min(CPU_SHARE, info["affinity"]))
             # one frame per thread: the first F are the GPU's frames (parity sample)
@@ -692,13 +740,13 @@ def main(argv=None):
                                    "latency_1core_s": round(lat, 3),
                                    "host": info}
             res["parity_sample"] = f"{same}/{nchk} frames bit-exact vs oracle"
-        if world == 1 and not args.no_configs and not distributed:
+        if args.full and world == 1 and not args.no_configs and not distributed:
             tc0 = time.perf_counter()
             res["configs"] = config_table(mvsv, _lib, dev)
             res["configs_note"] = (f"BASELINE configs 1, 2, 3, 5 on this GPU, device-resident (median of 10 "
                                    f"HIP-event steps after 3 warm-up), roof per SURVEY.md §8(d), parity_frame0 = "
                                    f"frame 0 vs the oracle; {time.perf_counter() - tc0:.1f} s incl. oracles")
-        if gathered is not None:
+        if args.full and gathered is not None:
             # the gathered global batch: frame 0 of every rank, as it arrived on
             # rank 0, against the oracle (outside the timed region)
             sample = [(r, mvsv.synth_pair(frame_seeds(r, world, F, SEED0)[0], W, H, minD, D))

@@ -32,6 +32,24 @@ def test_bench_spawns_ranks_and_gathers(n):
     assert res["gathered_frames_ok"] == f"{2 * n}/{2 * n}"
 
 
+def test_dump_outputs_float32_and_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files, whole while they fit the limit, else
+    the same sample of the flattened elements in every run."""
+    import numpy as np
+    import bench
+    a = (np.arange(7 * 33 * 65) % 2048 - 16).astype(np.int16).reshape(7, 33, 65)
+    bench.dump_outputs(str(tmp_path / "whole"), {"disparity": a})
+    got = np.load(tmp_path / "whole" / "disparity.npy")
+    assert got.dtype == np.float32 and got.shape == a.shape and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * 1024)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"disparity": a})
+    s1, s2 = (np.load(tmp_path / d / "disparity.npy") for d in ("s1", "s2"))
+    assert s1.dtype == np.float32 and s1.ndim == 1 and 0 < s1.size < a.size
+    assert os.path.getsize(tmp_path / "s1" / "disparity.npy") <= 16 * 1024
+    assert np.array_equal(s1, s2) and np.isin(s1, a).all()
+
+
 def test_bench_rejects_world_size_mismatch():
     r = _run(["--dry", "--gpus", "4"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0

@@ -69,7 +69,7 @@ def test_bench_force_gather_one_rank(gpu, tmp_path):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-gather",
            "--steps", "3", "--warmup", "1", "--frames", "2", "--width", "640", "--height", "480",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")][-1]

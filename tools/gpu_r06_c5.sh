@@ -5,7 +5,7 @@ set -o pipefail
 TAG=${1:?TAG}; cd $GRAFT_REPO_ROOT; O=gpurun_out/$TAG; mkdir -p $O
 for f in 1 2 3 8; do timeout -k 10 60 python tools/stage_times.py --frames $f >> $O/c5_stages.jsonl || exit 1; done
 cat $O/c5_stages.jsonl
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python - <<PY
 import json
 d=json.load(open("$O/bench.json"))

@@ -6,7 +6,7 @@ TAG=${1:?TAG}; SQ=${2:-}
 cd $GRAFT_REPO_ROOT; O=gpurun_out/$TAG; mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1 || { echo "tests failed"; tail -40 $O/gpu_tests.log; exit 1; }
 tail -1 $O/gpu_tests.log
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python -c "
 import json; d=json.load(open('$O/bench.json'))
 print(d['value'], d['ms_per_step'], d.get('single_batch_ms'), json.dumps(d.get('roofline'))[:300])"
