@@ -28,6 +28,10 @@
  *                                     trgt/mean_test.cpp:61-70,258-318 (condvar
  *                                     hand-off, Disparity::sgbm, build(MEAN_VALUE))
  *                                     as a double-buffered device pipeline
+ *   mvsv_stream_create_raw /          the same loop from the raw camera pair
+ *   _push_raw / _pop_pair             (trgt/liveDisparity.cpp:82-101): rectification,
+ *                                     crop and resize on the device, ahead of SGBM
+ *   mvsv_convert_maps                 cv::convertMaps(CV_16SC2, CV_16UC1)
  *   mvsv_remap_device / mvsv_rectify  cv::remap(INTER_LINEAR) + ROI crop of
  *                                     Stereosystem::getRectifiedImagepair
  *                                     src/Stereosystem.cpp:243-262
@@ -294,6 +298,48 @@ MVSV_API int mvsv_stream_pop_view(mvsv_stream* s, const int16_t** map, float* me
 MVSV_API int mvsv_stream_pending(const mvsv_stream* s);
 MVSV_API void mvsv_stream_destroy(mvsv_stream* s);
 
+/* ---- raw frame stream: camera pairs in, rectified on the device ------------------
+ * The loop of trgt/liveDisparity.cpp:82-101 / trgt/mean_test.cpp:258-318:
+ * Stereosystem::getRectifiedImagepair (two cv::remap + the mDisplayROI crop,
+ * src/Stereosystem.cpp:244-315), optionally cv::resize by a factor, then
+ * Disparity::sgbm and the detection grid.  A raw stream owns the rectification:
+ * the four float maps are converted once, at creation, to cv::convertMaps'
+ * fixed-point form (cropped to roi, device resident); a pushed raw pair is
+ * uploaded once and rectified (and resized) by kernels ahead of its SGBM launch,
+ * so the rectified pair never visits the host unless keep_rectified asks for it.
+ * The maps are only read during mvsv_stream_create_raw.  Map values follow
+ * mvsv_convert_maps' contract. */
+typedef struct {
+    int raw_width, raw_height; /* the camera frame, each 1..32767 */
+    const float* maps[4];      /* left x, left y, right x, right y: host, raw size */
+    size_t map_stride;         /* floats per row, >= raw_width */
+    mvsv_rect roi;             /* mDisplayROI: non-empty, inside the raw frame */
+    double factor;             /* 0 or 1: none; else cv::resize(.., factor, factor) of the crop */
+    int keep_rectified;        /* mvsv_stream_pop_pair can also return the rectified pair */
+} mvsv_rectification;
+/* The stream's frames (what SGBM sees and pop returns) have the roi's size, or
+ * mvsv_resize_size(roi width, roi height, factor, factor) with a factor; p and
+ * grid_roi are validated against that size (mvsv_stream_size reports it).
+ * set_params / set_batch / set_inflight / pop / pop_view / pending / destroy work
+ * as on a stream of rectified pairs. */
+MVSV_API int mvsv_stream_create_raw(mvsv_ctx* ctx, const mvsv_rectification* rect,
+                                    const mvsv_sgbm_params* p, int depth, const mvsv_rect* grid_roi,
+                                    mvsv_stream** out);
+/* size of the maps a stream returns (either kind of stream) */
+MVSV_API int mvsv_stream_size(const mvsv_stream* s, int* width, int* height);
+/* a raw_width x raw_height pair; MVSV_E_INVALID_ARG on a stream of rectified pairs
+ * (as mvsv_stream_push is on a raw stream) and when depth frames are pending */
+MVSV_API int mvsv_stream_push_raw(mvsv_stream* s, const uint8_t* left, size_t left_stride,
+                                  const uint8_t* right, size_t right_stride);
+/* mvsv_stream_pop that can also hand out the frame's rectified (cropped, resized)
+ * pair -- what the reference's loops display or save
+ * (trgt/captureDisparity.cpp:270-271).  Every output may be NULL; non-NULL
+ * rect_left / rect_right on a stream without keep_rectified is
+ * MVSV_E_INVALID_ARG (the frame stays pending). */
+MVSV_API int mvsv_stream_pop_pair(mvsv_stream* s, int16_t* out, size_t out_stride, float* means,
+                                  uint8_t* rect_left, size_t rect_left_stride, uint8_t* rect_right,
+                                  size_t rect_right_stride);
+
 /* ---- before the path: rectification ---------------------------
  * cv::remap(src, dst, map_x, map_y, INTER_LINEAR) with BORDER_CONSTANT 0 for CV_8UC1
  * images and CV_32FC1 maps, in OpenCV 3.4's fixed-point arithmetic (INTER_BITS 5,
@@ -304,6 +350,18 @@ MVSV_API int mvsv_remap_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t 
                                const float* map_x, const float* map_y, size_t map_stride,
                                uint8_t* dst, size_t dst_stride, size_t dst_frame_stride,
                                int dst_width, int dst_height);
+
+/* cv::convertMaps(map_x, map_y, xy, frac, CV_16SC2, false): the fixed-point form
+ * in which cv::remap consumes CV_32FC1 maps (host only, no device needed).  Per
+ * pixel X = cvRound(map_x * 32), Y = cvRound(map_y * 32) (float product, round
+ * half to even); xy = (saturate_cast<short>(X >> 5), saturate_cast<short>(Y >> 5));
+ * frac = (Y & 31) * 32 + (X & 31).  Strides per row: map_stride in floats,
+ * xy_stride in int16 pairs, frac_stride in elements.  The same arithmetic as
+ * the first lines of the remap kernel; as for mvsv_remap_device, the result is
+ * undefined for map values that are not finite or have |value * 32| >= 2^31. */
+MVSV_API int mvsv_convert_maps(const float* map_x, const float* map_y, size_t map_stride, int width,
+                               int height, int16_t* xy, size_t xy_stride, uint16_t* frac,
+                               size_t frac_stride);
 
 /* Stereosystem::getRectifiedImagepair on host buffers: remap both images of a
  * W x H pair with their map pairs (maps: left x, left y, right x, right y, host,

@@ -11,6 +11,8 @@
 //   resetRectification                               src/Stereosystem.cpp:317-320
 //   loadExtrinisic / loadIntrinsic / saveExtrinsic / saveIntrinsic
 //                                                    src/Stereosystem.cpp:326-446
+// New: RawDisparityStream, the loop of trgt/liveDisparity.cpp:82-101 from the raw
+// pair to the disparity map as a device pipeline (mvsv_stream_create_raw).
 // What the reference gets from its two mvIMPACT cameras (image size, binning
 // mode, the raw pair of getImagepair) is given here at construction / passed
 // in: getRectifiedImagepair rectifies the raw pair the Stereopair holds, in
@@ -237,6 +239,9 @@ public:
     }
 
     // the state the reference keeps private, readable for tests / tools
+    int width() const { return mWidth; }
+    int height() const { return mHeight; }
+    bool isInit() const { return mIsInit; }
     const mvsv_rect& displayROI() const { return mDisplayROI; }
     const std::vector<float>& map1(int c) const { return mMap1[c]; }
     const std::vector<float>& map2(int c) const { return mMap2[c]; }
@@ -288,6 +293,83 @@ private:
     mvsv_rect mDisplayROI = {};
     Matd mIntrinsicLeft, mIntrinsicRight, mDistCoeffsLeft, mDistCoeffsRight;
     std::string mTag;
+};
+
+// The camera loop of trgt/liveDisparity.cpp:82-101 (getImagepair,
+// getRectifiedImagepair[, factor], Disparity::sgbm) as a pipelined stream on the
+// device (mvsv_stream_create_raw): push_raw(raw pair) / pop(disparity).  Opened
+// from a Stereosystem that has run initRectification(); its maps are converted
+// and uploaded once, here.  Every frame is resized when a factor is given (the
+// reference's unresized initialising call has no counterpart).  Uses the calling
+// thread's context: create, use and destroy it on one thread.
+class RawDisparityStream {
+public:
+    RawDisparityStream(const Stereosystem& s, const StereoSGBM& matcher, float factor = 0.f, int depth = 3,
+                       const mvsv_rect* grid_roi = nullptr, bool keep_rectified = false, int batch = 1,
+                       int inflight = 1)
+        : mRawW(s.width()), mRawH(s.height()), mKeep(keep_rectified)
+    {
+        if (!s.isInit()) throw Error(MVSV_E_INVALID_ARG, "RawDisparityStream: initRectification() has not run");
+        mCtx = thread_context();
+        mvsv_rectification r{};
+        r.raw_width = mRawW;
+        r.raw_height = mRawH;
+        r.maps[0] = s.map1(0).data();
+        r.maps[1] = s.map2(0).data();
+        r.maps[2] = s.map1(1).data();
+        r.maps[3] = s.map2(1).data();
+        r.map_stride = (size_t)mRawW;
+        r.roi = s.displayROI();
+        r.factor = factor;
+        r.keep_rectified = keep_rectified ? 1 : 0;
+        check(mvsv_stream_create_raw(mCtx, &r, &matcher.params(), depth, grid_roi, &mStream), mCtx);
+        int rc = mvsv_stream_size(mStream, &mW, &mH);
+        if (rc == MVSV_OK && batch != 1) rc = mvsv_stream_set_batch(mStream, batch);
+        if (rc == MVSV_OK && inflight != 1) rc = mvsv_stream_set_inflight(mStream, inflight);
+        if (rc != MVSV_OK) {
+            mvsv_stream_destroy(mStream);
+            check(rc, mCtx);
+        }
+    }
+    ~RawDisparityStream() { mvsv_stream_destroy(mStream); }
+    RawDisparityStream(const RawDisparityStream&) = delete;
+    RawDisparityStream& operator=(const RawDisparityStream&) = delete;
+
+    int width() const { return mW; }
+    int height() const { return mH; }
+    int pending() const { return mvsv_stream_pending(mStream); }
+    void set_params(const StereoSGBM& matcher) { check(mvsv_stream_set_params(mStream, &matcher.params()), mCtx); }
+
+    void push_raw(const Mat& left, const Mat& right)
+    {
+        check_pair(left, right);
+        if (left.cols != mRawW || left.rows != mRawH)
+            throw Error(MVSV_E_INVALID_ARG, "RawDisparityStream: pair of the raw frame's size expected");
+        check(mvsv_stream_push_raw(mStream, left.data, left.step, right.data, right.step), mCtx);
+    }
+    // the oldest frame's map (CV_16S, disparity * 16); means: 81 floats of the
+    // grid_roi's 9x9 grid, or nullptr; rectified: the frame's rectified pair
+    // (needs keep_rectified), or nullptr
+    void pop(Mat& disparity, float* means = nullptr, Stereopair* rectified = nullptr)
+    {
+        if (rectified && !mKeep) throw Error(MVSV_E_INVALID_ARG, "RawDisparityStream: opened without keep_rectified");
+        disparity.create(mH, mW, MAT_16SC1);
+        if (rectified) {
+            rectified->mLeft.create(mH, mW, MAT_8UC1);
+            rectified->mRight.create(mH, mW, MAT_8UC1);
+        }
+        check(mvsv_stream_pop_pair(mStream, reinterpret_cast<int16_t*>(disparity.data), disparity.step / 2, means,
+                                   rectified ? rectified->mLeft.data : nullptr, rectified ? rectified->mLeft.step : 0,
+                                   rectified ? rectified->mRight.data : nullptr,
+                                   rectified ? rectified->mRight.step : 0),
+              mCtx);
+    }
+
+private:
+    mvsv_ctx* mCtx = nullptr;
+    mvsv_stream* mStream = nullptr;
+    int mRawW, mRawH, mW = 0, mH = 0;
+    bool mKeep;
 };
 
 }  // namespace mvsv

@@ -14,7 +14,7 @@ from .disparity import (Disparity, StereoBM, StereoSGBM, Stereopair, mean_dispar
                         sgbmParameters, synth_pair)
 from .detection import DisparityStream, MeanDisparityDetection, Subimage, create_dmap_rois
 from .calibration import Stereosystem, read_matrix, stereo_rectify, write_matrices
-from .rectify import init_undistort_rectify_map, rectify_pair, remap
+from .rectify import convert_maps, init_undistort_rectify_map, rectify_pair, remap
 from .utility import Utility, dMapValues, ply, reproject
 
 __all__ = [
@@ -24,7 +24,7 @@ __all__ = [
     "DisparityStream", "MeanDisparityDetection", "Subimage", "create_dmap_rois", "Utility",
     "dMapValues", "ply", "reproject", "init_undistort_rectify_map", "rectify_pair", "remap",
     "synchronize", "set_option", "Stereosystem", "read_matrix", "write_matrices",
-    "stereo_rectify", "MVSV_E_TIMEOUT", "OPT_STRIP_SPIN_LIMIT", "OPT_STRIP_WAVES", "OPT_BM_TILE_ROWS",
+    "stereo_rectify", "convert_maps", "MVSV_E_TIMEOUT", "OPT_STRIP_SPIN_LIMIT", "OPT_STRIP_WAVES", "OPT_BM_TILE_ROWS",
     "OPT_PATH_SCHEDULE", "OPT_BITSLICE",
 ]
 __version__ = "1.0.0"

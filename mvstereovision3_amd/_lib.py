@@ -91,6 +91,13 @@ class Rect(ctypes.Structure):
                 ("y1", ctypes.c_int)]
 
 
+class Rectification(ctypes.Structure):
+    """mvsv_rectification: what mvsv_stream_create_raw takes over from Stereosystem."""
+    _fields_ = [("raw_width", ctypes.c_int), ("raw_height", ctypes.c_int),
+                ("maps", ctypes.c_void_p * 4), ("map_stride", ctypes.c_size_t), ("roi", Rect),
+                ("factor", ctypes.c_double), ("keep_rectified", ctypes.c_int)]
+
+
 class SgbmYamlValues(ctypes.Structure):
     _fields_ = [(f, ctypes.c_int) for f in YAML_FIELDS]
 
@@ -143,6 +150,11 @@ def _declare(lib, strict=True):
         "mvsv_stream_pop_view": ([P, P, P], I),
         "mvsv_stream_pending": ([P], I),
         "mvsv_stream_destroy": ([P], None),
+        "mvsv_stream_create_raw": ([P, P, P, I, P, ctypes.POINTER(P)], I),
+        "mvsv_stream_size": ([P, ctypes.POINTER(I), ctypes.POINTER(I)], I),
+        "mvsv_stream_push_raw": ([P, P, Z, P, Z], I),
+        "mvsv_stream_pop_pair": ([P, P, Z, P, P, Z, P, Z], I),
+        "mvsv_convert_maps": ([P, P, Z, I, I, P, Z, P, Z], I),
         "mvsv_remap_device": ([P, I, P, Z, Z, I, I, P, P, Z, P, Z, Z, I, I], I),
         "mvsv_rectify_pair": ([P, P, Z, P, Z, I, I, P, P, P, Z, P, Z], I),
         "mvsv_init_undistort_rectify_map": ([P, P, I, P, P, I, I, P, P, Z], I),

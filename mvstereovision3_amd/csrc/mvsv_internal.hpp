@@ -252,6 +252,12 @@ int speckle_device(mvsv_ctx* ctx, int n, int16_t* img, size_t st, size_t fs, int
 int remap_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh,
                  const float* mx, const float* my, size_t ms, uint8_t* dst, size_t ds, size_t dfs,
                  int dw, int dh);
+// The raw frame stream's rectification (mvsv_post.hip): raw = [n][2][sh][sw], maps
+// in mvsv_convert_maps' form as [2][dh][ms] entries (ms a multiple of 4, >= dw,
+// padding entries zero); frame f goes to dL / dR + f * dfs, rows ds bytes apart.
+int rectify_pair_device(mvsv_ctx* ctx, int n, const uint8_t* raw, int sw, int sh, const int16_t* xy,
+                        const uint16_t* frac, size_t ms, int dw, int dh, uint8_t* dL, uint8_t* dR, size_t ds,
+                        size_t dfs);
 // cv::resize INTER_LINEAR (CV_8UC1) output size / launch (mvsv_post.hip)
 int resize_size(int sw, int sh, double fx, double fy, int* dw, int* dh);
 int resize_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh, double fx,

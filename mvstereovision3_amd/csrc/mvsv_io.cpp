@@ -323,6 +323,29 @@ int mvsv_write_ply(const char* path, const char* author, const char* object_name
     return out ? MVSV_OK : MVSV_E_IO;
 }
 
+// [cv::convertMaps CV_32FC1 x 2 -> CV_16SC2 + CV_16UC1] the arithmetic of the
+// first lines of the remap kernel (mvsv_post.hip): nearbyintf under the default
+// rounding mode is __float2int_rn for |v| < 2^31
+int mvsv_convert_maps(const float* mx, const float* my, size_t ms, int W, int H, int16_t* xy, size_t xs,
+                      uint16_t* frac, size_t fs)
+{
+    if (!mx || !my || !xy || !frac || W <= 0 || H <= 0 || ms < (size_t)W || xs < (size_t)W || fs < (size_t)W)
+        return MVSV_E_INVALID_ARG;
+    for (int y = 0; y < H; y++) {
+        const float* px = mx + (size_t)y * ms;
+        const float* py = my + (size_t)y * ms;
+        int16_t* o = xy + (size_t)y * xs * 2;
+        uint16_t* a = frac + (size_t)y * fs;
+        for (int x = 0; x < W; x++) {
+            const float fx = px[x] * 32.0f, fy = py[x] * 32.0f;
+            const int X = (int)std::nearbyintf(fx), Y = (int)std::nearbyintf(fy);
+            o[2 * x] = (int16_t)std::min(std::max(X >> 5, -32768), 32767);
+            o[2 * x + 1] = (int16_t)std::min(std::max(Y >> 5, -32768), 32767);
+            a[x] = (uint16_t)((Y & 31) * 32 + (X & 31));
+        }
+    }
+    return MVSV_OK;
+}
 
 // [cv::initUndistortRectifyMap] (OpenCV 3.4 undistort.cpp), CV_32FC1 output
 int mvsv_init_undistort_rectify_map(const double* K, const double* dist, int ndist,

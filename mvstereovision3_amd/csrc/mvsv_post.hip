@@ -521,6 +521,56 @@ __global__ __launch_bounds__(256) void remap_linear_kernel(
     dst[f * dfs + (size_t)y * ds + x] = (uint8_t)v;
 }
 
+// ---- the raw frame stream's rectification: both sides of n frames, ROI only -----
+// cv::remap as above on maps already in cv::convertMaps' form (mvsv_convert_maps:
+// (sx, sy) as a short pair and ay * 32 + ax as a u16 per pixel, cropped to the
+// display ROI, rows padded with zero entries to a multiple of 4 pixels, left
+// side then right side).  raw is [n][2][sh][sw]; blockIdx.z = 2 * frame + side.
+// A thread computes 4 adjacent pixels of a row: one 16-byte and one 8-byte map
+// load, the 2x2 taps as bounds-checked gathers, one dword store where the
+// destination is 4-byte aligned (the row stride may be odd) and byte stores
+// otherwise and in the row's tail.
+__device__ __forceinline__ int rectify_px(const uint8_t* s, int sw, int sh, int sxy, int fr)
+{
+    const int sx = (int)(short)(sxy & 0xffff), sy = sxy >> 16;
+    const int ax = fr & 31, ay = fr >> 5;
+    if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) return 0;
+    const int w00 = (32 - ay) * (32 - ax) * 32, w01 = (32 - ay) * ax * 32;
+    const int w10 = ay * (32 - ax) * 32, w11 = ay * ax * 32;
+    const int acc = remap_tap(s, sw, sw, sh, sx, sy) * w00 + remap_tap(s, sw, sw, sh, sx + 1, sy) * w01 +
+                    remap_tap(s, sw, sw, sh, sx, sy + 1) * w10 + remap_tap(s, sw, sw, sh, sx + 1, sy + 1) * w11;
+    return clampi((acc + (1 << 14)) >> 15, 0, 255);
+}
+
+__global__ __launch_bounds__(256) void rectify_pair_kernel(
+    const uint8_t* __restrict__ raw, int sw, int sh, const int16_t* __restrict__ xy,
+    const uint16_t* __restrict__ frac, size_t ms, uint8_t* __restrict__ dL, uint8_t* __restrict__ dR,
+    size_t ds, size_t dfs, int dw, int dh)
+{
+    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int side = blockIdx.z & 1, f = blockIdx.z >> 1;
+    if (x >= dw || y >= dh) return;
+    const uint8_t* s = raw + (size_t)blockIdx.z * sw * sh;
+    // ms and x are multiples of 4: 16- / 8-byte aligned, and inside the padded row
+    const size_t m = ((size_t)side * dh + y) * ms + x;
+    const int4 q = *reinterpret_cast<const int4*>(xy + 2 * m);
+    const uint2 a = *reinterpret_cast<const uint2*>(frac + m);
+    const int v0 = rectify_px(s, sw, sh, q.x, (int)(a.x & 0xffffu));
+    const int v1 = rectify_px(s, sw, sh, q.y, (int)(a.x >> 16));
+    const int v2 = rectify_px(s, sw, sh, q.z, (int)(a.y & 0xffffu));
+    const int v3 = rectify_px(s, sw, sh, q.w, (int)(a.y >> 16));
+    uint8_t* d = (side ? dR : dL) + f * dfs + (size_t)y * ds + x;
+    if (x + 3 < dw && ((uintptr_t)d & 3) == 0) {
+        *reinterpret_cast<uint32_t*>(d) = (uint32_t)v0 | (uint32_t)v1 << 8 | (uint32_t)v2 << 16 | (uint32_t)v3 << 24;
+    } else {
+        d[0] = (uint8_t)v0;
+        if (x + 1 < dw) d[1] = (uint8_t)v1;
+        if (x + 2 < dw) d[2] = (uint8_t)v2;
+        if (x + 3 < dw) d[3] = (uint8_t)v3;
+    }
+}
+
 // ---- cv::resize(src, dst, Size(0, 0), fx, fy, INTER_LINEAR), CV_8UC1 ----------
 // The resize of Stereosystem::getRectifiedImagepair(Stereopair&, float)
 // (src/Stereosystem.cpp:279-315).  [OpenCV 3.4 resize.cpp, x86 build] (oracle:
@@ -722,6 +772,16 @@ int remap_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs
     hipLaunchKernelGGL(remap_linear_kernel, grid, dim3(256), 0, ctx->stream, src, ss, sfs, sw, sh,
                        mx, my, ms, dst, ds, dfs, dw, dh);
     return check_hip(ctx, hipGetLastError(), "remap");
+}
+
+int rectify_pair_device(mvsv_ctx* ctx, int n, const uint8_t* raw, int sw, int sh, const int16_t* xy,
+                        const uint16_t* frac, size_t ms, int dw, int dh, uint8_t* dL, uint8_t* dR, size_t ds,
+                        size_t dfs)
+{
+    dim3 grid((dw + 255) / 256, (dh + 3) / 4, 2 * n);
+    hipLaunchKernelGGL(rectify_pair_kernel, grid, dim3(256), 0, ctx->stream, raw, sw, sh, xy, frac, ms, dL, dR, ds,
+                       dfs, dw, dh);
+    return check_hip(ctx, hipGetLastError(), "rectify pair");
 }
 
 int resize_size(int sw, int sh, double fx, double fy, int* dw, int* dh)

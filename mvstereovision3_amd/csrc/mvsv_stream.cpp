@@ -140,6 +140,8 @@ struct mvsv_stream {
     hipStream_t up = nullptr, down = nullptr;
     struct Slot {
         uint8_t *hL = nullptr, *hR = nullptr;  // pinned
+        uint8_t *hRectL = nullptr, *hRectR = nullptr;  // pinned, keep_rectified streams
+        uint8_t* dRaw = nullptr;                       // [2][rawH][rawW], raw streams
         int16_t* hOut = nullptr;
         float* hMeans = nullptr;
         uint8_t *dL = nullptr, *dR = nullptr;
@@ -162,6 +164,25 @@ struct mvsv_stream {
     long launched = 0;            // frames whose compute is enqueued
     int batch = 1;
     CopyPool* pool = nullptr;     // host copies of push / pop (nullptr: caller's thread only)
+    // raw stream (mvsv_stream_create_raw): pushed frames are raw camera pairs,
+    // rectified (cropped, resized) into the slots' dL / dR ahead of their SGBM
+    bool raw = false;
+    int rawW = 0, rawH = 0;       // the camera frame; a slot's hL / hR hold one each
+    int cropW = 0, cropH = 0;     // the display ROI's size
+    double factor = 0;            // 0: the crop is the frame; else cv::resize of the crop
+    bool keep = false;            // the rectified pair comes back to the host too
+    uint8_t* dRaw_all = nullptr;  // [depth][2][rawH][rawW]
+    int16_t* dMapXY = nullptr;    // [2][cropH][mapStride] (sx, sy), ROI only
+    uint16_t* dMapFrac = nullptr; // [2][cropH][mapStride] ay * 32 + ax
+    size_t mapStride = 0;         // entries per map row: cropW rounded up to 4, padding zero
+    uint8_t *dCropL = nullptr, *dCropR = nullptr;  // [depth][cropH][cropW] each, with a factor
+};
+
+// what mvsv_stream_create_raw adds to a stream's creation
+struct RawSetup {
+    const mvsv_rectification* rect;
+    int cropW, cropH;
+    bool resized;
 };
 
 static void stream_free(mvsv_stream* st)
@@ -172,6 +193,8 @@ static void stream_free(mvsv_stream* st)
         if (s.hR) (void)hipHostFree(s.hR);
         if (s.hOut) (void)hipHostFree(s.hOut);
         if (s.hMeans) (void)hipHostFree(s.hMeans);
+        if (s.hRectL) (void)hipHostFree(s.hRectL);
+        if (s.hRectR) (void)hipHostFree(s.hRectR);
         for (hipEvent_t e : {s.uploaded, s.computed, s.done})
             if (e) (void)hipEventDestroy(e);
     }
@@ -179,6 +202,11 @@ static void stream_free(mvsv_stream* st)
     if (st->dR_all) (void)hipFree(st->dR_all);
     if (st->dOut_all) (void)hipFree(st->dOut_all);
     if (st->dMeans_all) (void)hipFree(st->dMeans_all);
+    if (st->dRaw_all) (void)hipFree(st->dRaw_all);
+    if (st->dMapXY) (void)hipFree(st->dMapXY);
+    if (st->dMapFrac) (void)hipFree(st->dMapFrac);
+    if (st->dCropL) (void)hipFree(st->dCropL);
+    if (st->dCropR) (void)hipFree(st->dCropR);
     if (st->rep) (void)hipHostFree(st->rep);
     if (st->up) (void)hipStreamDestroy(st->up);
     if (st->down) (void)hipStreamDestroy(st->down);
@@ -186,11 +214,36 @@ static void stream_free(mvsv_stream* st)
     delete st;
 }
 
-int mvsv_stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, int depth,
-                       const mvsv_rect* grid_roi, mvsv_stream** out)
+// The display ROI of both map pairs in cv::convertMaps' form, on the device.
+static bool upload_maps(mvsv_stream* st, const mvsv_rectification* r)
 {
-    if (!ctx || !out) return MVSV_E_INVALID_ARG;
-    *out = nullptr;
+    const int cw = st->cropW, ch = st->cropH;
+    const size_t ms = ((size_t)cw + 3) & ~(size_t)3, side = ms * ch;
+    st->mapStride = ms;
+    std::vector<int16_t> xy;
+    std::vector<uint16_t> frac;
+    try {
+        xy.assign(side * 4, 0);
+        frac.assign(side * 2, 0);
+    } catch (...) {
+        return false;
+    }
+    for (int k = 0; k < 2; k++) {
+        const size_t o = (size_t)r->roi.y0 * r->map_stride + r->roi.x0;
+        if (mvsv_convert_maps(r->maps[2 * k] + o, r->maps[2 * k + 1] + o, r->map_stride, cw, ch,
+                              xy.data() + k * side * 2, ms, frac.data() + k * side, ms) != MVSV_OK)
+            return false;
+    }
+    return hipMalloc((void**)&st->dMapXY, xy.size() * sizeof(int16_t)) == hipSuccess &&
+           hipMalloc((void**)&st->dMapFrac, frac.size() * sizeof(uint16_t)) == hipSuccess &&
+           hipMemcpy(st->dMapXY, xy.data(), xy.size() * sizeof(int16_t), hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(st->dMapFrac, frac.data(), frac.size() * sizeof(uint16_t), hipMemcpyHostToDevice) ==
+               hipSuccess;
+}
+
+static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, int depth,
+                         const mvsv_rect* grid_roi, const RawSetup* raw, mvsv_stream** out)
+{
     if (depth < 1 || depth > 64) return set_error(ctx, MVSV_E_INVALID_ARG, "stream depth must be 1..64");
     SgbmEff e;
     std::string why;
@@ -211,9 +264,27 @@ int mvsv_stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, i
     st->grid = grid_roi != nullptr;
     if (grid_roi) st->roi = *grid_roi;
     const size_t px = (size_t)W * H;
+    size_t in_px = px;  // a slot's pinned input images
+    if (raw) {
+        st->raw = true;
+        st->rawW = raw->rect->raw_width;
+        st->rawH = raw->rect->raw_height;
+        st->cropW = raw->cropW;
+        st->cropH = raw->cropH;
+        st->factor = raw->resized ? raw->rect->factor : 0;
+        st->keep = raw->rect->keep_rectified != 0;
+        in_px = (size_t)st->rawW * st->rawH;
+    }
+    const size_t crop_px = (size_t)st->cropW * st->cropH;
     bool ok = hipStreamCreateWithFlags(&st->up, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&st->down, hipStreamNonBlocking) == hipSuccess;
     st->slots.resize(depth);
+    if (raw) {
+        ok = ok && hipMalloc((void**)&st->dRaw_all, 2 * in_px * depth) == hipSuccess && upload_maps(st, raw->rect);
+        if (raw->resized)
+            ok = ok && hipMalloc((void**)&st->dCropL, crop_px * depth) == hipSuccess &&
+                 hipMalloc((void**)&st->dCropR, crop_px * depth) == hipSuccess;
+    }
     ok = ok && hipMalloc((void**)&st->dL_all, px * depth) == hipSuccess &&
          hipMalloc((void**)&st->dR_all, px * depth) == hipSuccess &&
          hipMalloc((void**)&st->dOut_all, px * 2 * depth) == hipSuccess &&
@@ -225,8 +296,12 @@ int mvsv_stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, i
         s.dR = st->dR_all + i * px;
         s.dOut = st->dOut_all + i * px;
         s.dMeans = st->dMeans_all + i * 81;
-        ok = hipHostMalloc((void**)&s.hL, px, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void**)&s.hR, px, hipHostMallocDefault) == hipSuccess &&
+        if (raw) s.dRaw = st->dRaw_all + i * 2 * in_px;
+        if (st->keep)
+            ok = hipHostMalloc((void**)&s.hRectL, px, hipHostMallocDefault) == hipSuccess &&
+                 hipHostMalloc((void**)&s.hRectR, px, hipHostMallocDefault) == hipSuccess;
+        ok = ok && hipHostMalloc((void**)&s.hL, in_px, hipHostMallocDefault) == hipSuccess &&
+             hipHostMalloc((void**)&s.hR, in_px, hipHostMallocDefault) == hipSuccess &&
              hipHostMalloc((void**)&s.hOut, px * 2, hipHostMallocDefault) == hipSuccess &&
              hipHostMalloc((void**)&s.hMeans, 81 * sizeof(float), hipHostMallocDefault) == hipSuccess &&
              hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming) == hipSuccess &&
@@ -234,7 +309,7 @@ int mvsv_stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, i
              hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
     }
     ok = ok && alloc_report(ctx, depth, &st->rep, &st->rep_dev) == MVSV_OK;
-    if (ok && px * 2 >= kPoolMinBytes) {
+    if (ok && std::max(px, in_px) * 2 >= kPoolMinBytes) {
         int threads = 4;
         if (const char* v = std::getenv("MVSV_STREAM_COPY_THREADS")) threads = std::max(1, std::min(16, std::atoi(v)));
         if (threads > 1) {
@@ -252,6 +327,69 @@ int mvsv_stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, i
     }
     *out = st;
     return MVSV_OK;
+}
+
+int mvsv_stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, int depth,
+                       const mvsv_rect* grid_roi, mvsv_stream** out)
+{
+    if (!ctx || !out) return MVSV_E_INVALID_ARG;
+    *out = nullptr;
+    return stream_create(ctx, W, H, p, depth, grid_roi, nullptr, out);
+}
+
+int mvsv_stream_create_raw(mvsv_ctx* ctx, const mvsv_rectification* r, const mvsv_sgbm_params* p, int depth,
+                           const mvsv_rect* grid_roi, mvsv_stream** out)
+{
+    if (!ctx || !out) return MVSV_E_INVALID_ARG;
+    *out = nullptr;
+    if (!r) return set_error(ctx, MVSV_E_INVALID_ARG, "null rectification");
+    // the kernel's tap coordinates are shorts (cv::remap's own limit)
+    if (r->raw_width < 1 || r->raw_height < 1 || r->raw_width > 32767 || r->raw_height > 32767)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "raw frame size must be 1..32767 each way");
+    for (int i = 0; i < 4; i++)
+        if (!r->maps[i]) return set_error(ctx, MVSV_E_INVALID_ARG, "null map");
+    if (r->map_stride < (size_t)r->raw_width)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "map stride smaller than the raw width");
+    const mvsv_rect& q = r->roi;
+    if (q.x0 < 0 || q.y0 < 0 || q.x1 > r->raw_width || q.y1 > r->raw_height || q.x1 <= q.x0 || q.y1 <= q.y0)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "display ROI empty or outside the raw frame");
+    RawSetup raw{r, q.x1 - q.x0, q.y1 - q.y0, false};
+    int W = raw.cropW, H = raw.cropH;
+    if (r->factor != 0 && r->factor != 1) {
+        if (resize_size(raw.cropW, raw.cropH, r->factor, r->factor, &W, &H))
+            return set_error(ctx, MVSV_E_INVALID_ARG, "bad resize factor");
+        raw.resized = true;
+    }
+    return stream_create(ctx, W, H, p, depth, grid_roi, &raw, out);
+}
+
+int mvsv_stream_size(const mvsv_stream* st, int* width, int* height)
+{
+    if (!st || !width || !height) return MVSV_E_INVALID_ARG;
+    *width = st->W;
+    *height = st->H;
+    return MVSV_OK;
+}
+
+// A raw stream's run of n slots from slot i0: the raw pairs rectified into the
+// slots' dL / dR on the lane's stream -- through the crop buffer and cv::resize
+// with a factor.
+static int stream_rectify(mvsv_stream* st, mvsv_ctx* ctx, long i0, int n)
+{
+    const size_t px = (size_t)st->W * st->H, crop_px = (size_t)st->cropW * st->cropH;
+    auto& first = st->slots[i0];
+    if (!st->dCropL)
+        return rectify_pair_device(ctx, n, first.dRaw, st->rawW, st->rawH, st->dMapXY, st->dMapFrac, st->mapStride,
+                                   st->cropW, st->cropH, first.dL, first.dR, st->W, px);
+    uint8_t *cL = st->dCropL + i0 * crop_px, *cR = st->dCropR + i0 * crop_px;
+    int rc;
+    if ((rc = rectify_pair_device(ctx, n, first.dRaw, st->rawW, st->rawH, st->dMapXY, st->dMapFrac, st->mapStride,
+                                  st->cropW, st->cropH, cL, cR, st->cropW, crop_px)) ||
+        (rc = resize_device(ctx, n, cL, st->cropW, crop_px, st->cropW, st->cropH, st->factor, st->factor, first.dL,
+                            st->W, px)))
+        return rc;
+    return resize_device(ctx, n, cR, st->cropW, crop_px, st->cropW, st->cropH, st->factor, st->factor, first.dR,
+                         st->W, px);
 }
 
 // Enqueue compute + download for the pushed frames [launched, head): one
@@ -277,7 +415,9 @@ static int stream_launch(mvsv_stream* st)
         first.run_len = n;
         int* prev_target = ctx->report_target;
         ctx->report_target = st->rep_dev + i0;
-        int status = sgbm_device(ctx, n, first.dL, W, px, first.dR, W, px, W, H, st->eff, first.dOut, W, px);
+        int status = st->raw ? stream_rectify(st, ctx, i0, n) : MVSV_OK;
+        if (status == MVSV_OK)
+            status = sgbm_device(ctx, n, first.dL, W, px, first.dR, W, px, W, H, st->eff, first.dOut, W, px);
         ctx->report_target = prev_target;
         if (status == MVSV_OK && st->grid) {
             const mvsv_rect& q = st->roi;
@@ -302,6 +442,12 @@ static int stream_launch(mvsv_stream* st)
             if (st->grid &&
                 (rc = check_hip(c, hipMemcpyAsync(s.hMeans, s.dMeans, 81 * sizeof(float),
                                                   hipMemcpyDeviceToHost, st->down), "stream D2H")))
+                return rc;
+            if (st->keep &&
+                ((rc = check_hip(c, hipMemcpyAsync(s.hRectL, s.dL, px, hipMemcpyDeviceToHost, st->down),
+                                 "stream D2H")) ||
+                 (rc = check_hip(c, hipMemcpyAsync(s.hRectR, s.dR, px, hipMemcpyDeviceToHost, st->down),
+                                 "stream D2H"))))
                 return rc;
             if ((rc = check_hip(c, hipEventRecord(s.done, st->down), "stream event"))) return rc;
         }
@@ -388,6 +534,7 @@ int mvsv_stream_push(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t
 {
     if (!st) return MVSV_E_INVALID_ARG;
     mvsv_ctx* ctx = st->ctx;
+    if (st->raw) return set_error(ctx, MVSV_E_INVALID_ARG, "raw stream: push raw pairs with mvsv_stream_push_raw");
     if (!L || !R || ls < (size_t)st->W || rs < (size_t)st->W)
         return set_error(ctx, MVSV_E_INVALID_ARG, "null frame or stride smaller than width");
     if (ring_full(st->head, st->tail, (long)st->slots.size()))
@@ -412,6 +559,40 @@ int mvsv_stream_push(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t
         return rc;
     st->head++;
     // a full group, or a group that would otherwise wrap past the ring's end
+    if (ring_launch_after_push(st->head, st->launched, st->batch, (long)st->slots.size()))
+        return stream_launch(st);
+    return MVSV_OK;
+}
+
+int mvsv_stream_push_raw(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (!st->raw)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "stream of rectified pairs: push them with mvsv_stream_push");
+    const int W = st->rawW, H = st->rawH;
+    if (!L || !R || ls < (size_t)W || rs < (size_t)W)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "null frame or stride smaller than the raw width");
+    if (ring_full(st->head, st->tail, (long)st->slots.size()))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "stream full: pop a frame first");
+    DeviceGuard dev_guard(ctx->device);
+    auto& s = st->slots[st->head % st->slots.size()];
+    // the slot's previous frame was popped, so its copies and its rectification are complete
+    auto copy_in = [&](int part, int parts) {
+        copy_rows(s.hL, W, L, ls, W, H, part, parts);
+        copy_rows(s.hR, W, R, rs, W, H, part, parts);
+    };
+    if (st->pool)
+        st->pool->run(copy_in);
+    else
+        copy_in(0, 1);
+    const size_t px = (size_t)W * H;
+    int rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(s.dRaw, s.hL, px, hipMemcpyHostToDevice, st->up), "stream H2D")) ||
+        (rc = check_hip(ctx, hipMemcpyAsync(s.dRaw + px, s.hR, px, hipMemcpyHostToDevice, st->up), "stream H2D")) ||
+        (rc = check_hip(ctx, hipEventRecord(s.uploaded, st->up), "stream event")))
+        return rc;
+    st->head++;
     if (ring_launch_after_push(st->head, st->launched, st->batch, (long)st->slots.size()))
         return stream_launch(st);
     return MVSV_OK;
@@ -454,19 +635,27 @@ static void stream_means(const mvsv_stream* st, const mvsv_stream::Slot& s, floa
         std::memset(means, 0, 81 * sizeof(float));
 }
 
-int mvsv_stream_pop(mvsv_stream* st, int16_t* out, size_t os, float* means)
+int mvsv_stream_pop_pair(mvsv_stream* st, int16_t* out, size_t os, float* means, uint8_t* rl, size_t rls,
+                         uint8_t* rr, size_t rrs)
 {
     if (!st) return MVSV_E_INVALID_ARG;
     if (out && os < (size_t)st->W) return set_error(st->ctx, MVSV_E_INVALID_ARG, "stride smaller than width");
+    if ((rl || rr) && !st->keep)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the stream was not created with keep_rectified");
+    if ((rl && rls < (size_t)st->W) || (rr && rrs < (size_t)st->W))
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "stride smaller than width");
     DeviceGuard dev_guard(st->ctx->device);
     mvsv_stream::Slot* sp = nullptr;
     int rc = stream_pop_slot(st, &sp);
     if (rc) return rc;
     const auto& s = *sp;
-    if (out) {
+    if (out || rl || rr) {
         auto copy_out = [&](int part, int parts) {
-            copy_rows((uint8_t*)out, os * 2, (const uint8_t*)s.hOut, (size_t)st->W * 2, (size_t)st->W * 2, st->H,
-                      part, parts);
+            if (out)
+                copy_rows((uint8_t*)out, os * 2, (const uint8_t*)s.hOut, (size_t)st->W * 2, (size_t)st->W * 2,
+                          st->H, part, parts);
+            if (rl) copy_rows(rl, rls, s.hRectL, (size_t)st->W, (size_t)st->W, st->H, part, parts);
+            if (rr) copy_rows(rr, rrs, s.hRectR, (size_t)st->W, (size_t)st->W, st->H, part, parts);
         };
         if (st->pool)
             st->pool->run(copy_out);
@@ -475,6 +664,11 @@ int mvsv_stream_pop(mvsv_stream* st, int16_t* out, size_t os, float* means)
     }
     stream_means(st, s, means);
     return MVSV_OK;
+}
+
+int mvsv_stream_pop(mvsv_stream* st, int16_t* out, size_t os, float* means)
+{
+    return mvsv_stream_pop_pair(st, out, os, means, nullptr, 0, nullptr, 0);
 }
 
 int mvsv_stream_pop_view(mvsv_stream* st, const int16_t** map, float* means)

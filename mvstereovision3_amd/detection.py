@@ -210,6 +210,8 @@ class DisparityStream:
     in push order.  `depth` frames may be in flight; with batch > 1 they are
     computed in groups of `batch` frames (frame-batch kernels); with inflight > 1
     up to that many groups run concurrently on the stream's compute lanes.
+    DisparityStream.raw(...) opens the same pipeline for raw camera pairs
+    (push_raw): rectification, crop and resize run on the device too.
     """
 
     def __init__(self, matcher, width, height, depth=3, grid_roi=None, device=0, batch=1,
@@ -223,6 +225,71 @@ class DisparityStream:
         check(lib().mvsv_stream_create(self._ctx.handle, width, height, ctypes.byref(self._params),
                                        depth, ctypes.byref(roi) if roi is not None else None,
                                        ctypes.byref(h)), self._ctx.handle)
+        self._raw_shape = None
+        self._keep = False
+        self._opened(h, batch, inflight)
+
+    @classmethod
+    def raw(cls, matcher, stereosystem_or_maps, roi=None, factor=None, depth=3, grid_roi=None,
+            batch=1, inflight=1, keep_rectified=False, device=0):
+        """A stream that takes the raw camera pair (mvsv_stream_create_raw): the
+        camera loop of trgt/liveDisparity.cpp:82-101 as push_raw / pop.
+
+        stereosystem_or_maps: a calibration.Stereosystem (initialised here if it
+        is not yet; its mMap1 / mMap2 / mDisplayROI are used), or the four float32
+        maps (left x, left y, right x, right y) of the raw frame's size with
+        roi = (x0, y0, x1, y1) (default: the whole frame).  The maps are converted
+        once to fixed point and stay on the device; each push_raw uploads the raw
+        pair only, and remap, crop and (with factor) cv::resize run on the device
+        ahead of SGBM.  The stream's frames (.width x .height) are the ROI, or
+        resize_size(ROI, factor) with a factor (taken as a float, like the
+        reference's parameter).  Every frame is resized: the reference's quirk
+        that the *initialising* call of getRectifiedImagepair(pair, factor)
+        returns the unresized crop (src/Stereosystem.cpp:298-311) does not apply
+        here.  keep_rectified: pop(rectified=True) also returns the rectified pair.
+        """
+        s = stereosystem_or_maps
+        if hasattr(s, "initRectification"):
+            if not s.mIsInit and not s.initRectification():
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "raw stream: the rectification cannot be initialised")
+            maps = (s.mMap1[0], s.mMap2[0], s.mMap1[1], s.mMap2[1])
+            roi = s.mDisplayROI if roi is None else roi
+        else:
+            maps = tuple(s)
+        if len(maps) != 4 or any(m is None for m in maps):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "raw stream: four maps expected")
+        ms = [np.ascontiguousarray(m, np.float32) for m in maps]
+        if ms[0].ndim != 2 or any(m.shape != ms[0].shape for m in ms):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "raw stream: four maps of the raw frame's size expected")
+        rh, rw = ms[0].shape
+        roi = (0, 0, rw, rh) if roi is None else tuple(int(v) for v in roi)
+        r = _lib.Rectification()
+        r.raw_width, r.raw_height, r.map_stride = rw, rh, rw
+        for i, m in enumerate(ms):
+            r.maps[i] = m.ctypes.data
+        r.roi = Rect(*roi)
+        r.factor = 0.0 if factor is None else float(np.float32(factor))
+        r.keep_rectified = 1 if keep_rectified else 0
+        self = cls.__new__(cls)
+        self._ctx = context(device)
+        self._params = matcher._params
+        self._grid = grid_roi is not None
+        g = Rect(*grid_roi) if grid_roi is not None else None
+        h = ctypes.c_void_p()
+        self._h = None
+        self._close_pending = False
+        check(lib().mvsv_stream_create_raw(self._ctx.handle, ctypes.byref(r), ctypes.byref(self._params),
+                                           depth, ctypes.byref(g) if g is not None else None,
+                                           ctypes.byref(h)), self._ctx.handle)
+        w, hh = ctypes.c_int(), ctypes.c_int()
+        check(lib().mvsv_stream_size(h, ctypes.byref(w), ctypes.byref(hh)), self._ctx.handle)
+        self.width, self.height = w.value, hh.value
+        self._raw_shape = (rh, rw)
+        self._keep = bool(keep_rectified)
+        self._opened(h, batch, inflight)
+        return self
+
+    def _opened(self, h, batch, inflight):
         self._h = h
         # pinned host slots stay allocated while pop views are alive: a view's
         # buffer references the stream, and close() defers the destroy until
@@ -271,11 +338,42 @@ class DisparityStream:
         check(lib().mvsv_stream_push(self._h, L.ctypes.data, L.strides[0], R.ctypes.data,
                                      R.strides[0]), self._ctx.handle)
 
-    def pop(self, copy_map=True):
+    def push_raw(self, left, right):
+        """Push a raw camera pair (a stream made by DisparityStream.raw)."""
+        self._live()
+        L = np.asarray(left)
+        R = np.asarray(right)
+        if self._raw_shape is None:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "push_raw: a stream of rectified pairs takes push")
+        if L.shape != self._raw_shape or R.shape != L.shape or L.dtype != np.uint8 or R.dtype != np.uint8:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "push_raw: uint8 pair of the raw frame's size expected")
+        if L.strides[1] != 1:
+            L = np.ascontiguousarray(L)
+        if R.strides[1] != 1:
+            R = np.ascontiguousarray(R)
+        check(lib().mvsv_stream_push_raw(self._h, L.ctypes.data, L.strides[0], R.ctypes.data,
+                                         R.strides[0]), self._ctx.handle)
+
+    def pop(self, copy_map=True, rectified=False):
         """(map, means) of the oldest frame; copy_map=False returns (None, means);
         copy_map="view" returns a read-only view of the map in the stream's pinned
-        host slot (no host copy), valid until the next push."""
+        host slot (no host copy), valid until the next push.  rectified=True (a raw
+        stream with keep_rectified) returns (map, means, (left, right)) with the
+        frame's rectified pair."""
         self._live()
+        if rectified:
+            if not self._keep or copy_map == "view":
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG,
+                                "pop(rectified=True): a raw stream with keep_rectified and a copied map expected")
+            out = np.empty((self.height, self.width), np.int16) if copy_map else None
+            means = np.empty(81, np.float32) if self._grid else None
+            rl = np.empty((self.height, self.width), np.uint8)
+            rr = np.empty_like(rl)
+            check(lib().mvsv_stream_pop_pair(self._h, out.ctypes.data if out is not None else None, self.width,
+                                             means.ctypes.data if means is not None else None,
+                                             rl.ctypes.data, self.width, rr.ctypes.data, self.width),
+                  self._ctx.handle)
+            return out, means, (rl, rr)
         if copy_map == "view":
             ptr = ctypes.c_void_p()
             means = np.empty(81, np.float32) if self._grid else None

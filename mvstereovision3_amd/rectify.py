@@ -65,6 +65,28 @@ def remap(src, map_x, map_y):
     return out if batched else out[0]
 
 
+def convert_maps(map_x, map_y):
+    """cv::convertMaps(map_x, map_y, CV_16SC2, CV_16UC1) -> (xy int16 (H, W, 2), frac uint16 (H, W)).
+
+    The fixed-point form in which cv::remap (and the raw frame stream's kernel)
+    consumes float maps: xy = (X >> 5, Y >> 5) saturated to short and
+    frac = (Y & 31) * 32 + (X & 31) with X = cvRound(map_x * 32), Y likewise.
+    Host only; maps must be finite with |value * 32| < 2^31.
+    """
+    mx = np.asarray(map_x, np.float32)
+    my = np.asarray(map_y, np.float32)
+    if mx.ndim != 2 or mx.shape != my.shape or mx.size == 0:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "convert_maps: two float32 maps of one size expected")
+    if mx.strides[1] != 4 or mx.strides[0] % 4 or mx.strides[0] < 4 * mx.shape[1] or mx.strides != my.strides:
+        mx, my = np.ascontiguousarray(mx), np.ascontiguousarray(my)
+    h, w = mx.shape
+    xy = np.empty((h, w, 2), np.int16)
+    frac = np.empty((h, w), np.uint16)
+    check(lib().mvsv_convert_maps(mx.ctypes.data, my.ctypes.data, mx.strides[0] // 4, w, h,
+                                  xy.ctypes.data, w, frac.ctypes.data, w))
+    return xy, frac
+
+
 def rectify_pair(left, right, maps, roi):
     """Stereosystem::getRectifiedImagepair on host images.
 
