@@ -24,6 +24,11 @@
  *                                     src/MeanDisparityDetection.cpp:159-206 +
  *                                     Utility::calcMeanDisparity src/utility.cpp:265-285
  *   mvsv_mean_disparity_grid          same, host map (MeanDisparityDetection::build)
+ *   mvsv_samplepoint_layout /         SamplepointDetection::init / build /
+ *   _values(_device) / _detect_device detectObstacles src/SamplePointDetection.cpp:29-178,
+ *                                     Samplepoint inc/Samplepoint.h:17-40
+ *   mvsv_stream_enable_samplepoints / both detectors on every frame of a stream
+ *   _front_samples                    (trgt/demo.cpp:206-209,271-276)
  *   mvsv_stream_*                     the disparity worker thread + main loop of
  *                                     trgt/mean_test.cpp:61-70,258-318 (condvar
  *                                     hand-off, Disparity::sgbm, build(MEAN_VALUE))
@@ -262,6 +267,49 @@ MVSV_API int mvsv_mean_disparity_grid_device(mvsv_ctx* ctx, int n, const int16_t
 MVSV_API int mvsv_mean_disparity_grid(mvsv_ctx* ctx, const int16_t* dmap, size_t stride,
                                       int width, int height, float* means);
 
+/* ---- SamplepointDetection: the lattice detector (src/SamplePointDetection.cpp) ----
+ * Layout (init, :38-47): dX = width / 8, dY = height / 8, step_x = width / dX,
+ * step_y = height / dY (integer divisions: steps of 8..15), centres
+ * (c * step_x, r * step_y) for c = 1..dX-1 (outer loop), r = 1..dY-1 (inner), so
+ * nx = dX - 1, ny = dY - 1 and point (c, r) has index (c - 1) * ny + (r - 1).
+ * A map narrower or lower than 16 has no point (nx * ny == 0; a step is 0 where
+ * its dX / dY is): valid, the calls below then return MVSV_OK and do nothing.
+ * Host only, no device needed. */
+MVSV_API int mvsv_samplepoint_layout(int width, int height, int* step_x, int* step_y, int* nx,
+                                     int* ny);
+
+/* Samplepoint::calculateSamplepointValue (inc/Samplepoint.h:32-40) of every
+ * lattice point of n int16 maps (device pointers, strides in elements; any
+ * 2-byte-aligned view): the patch [cx - radius, cx + radius] x [cy - radius,
+ * cy + radius] through Utility::calcMeanDisparity (mean of the values > 1 with
+ * integer division, 0 for none) for radius > 0, the raw centre value for
+ * radius 0.  The reference's radius is 2; 0 .. min(step_x, step_y) - 1 keeps the
+ * patches inside the map, anything else is MVSV_E_INVALID_ARG.
+ * values: nx * ny floats per frame (device pointer), frames back to back. */
+MVSV_API int mvsv_samplepoint_values_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t stride,
+                                            size_t frame_stride, int width, int height, int radius,
+                                            float* values);
+/* Same for one host map into a host array (synchronous). */
+MVSV_API int mvsv_samplepoint_values(mvsv_ctx* ctx, const int16_t* dmap, size_t stride, int width,
+                                     int height, int radius, float* values);
+
+/* SamplepointDetection::detectObstacles (:134-178) on the device: a point is a
+ * hit when value < range_first && value > range_second (float compares); each
+ * hit carries Utility::calcCoordinate(value, centre x, centre y, Q) -- the
+ * arithmetic of mvsv_calc_coordinate, bit for bit.  Per frame: counts[f] = the
+ * number of hits (it may exceed max_hits), hits[f * max_hits ..] = the first
+ * min(count, max_hits) of them in index order.  values as written by
+ * mvsv_samplepoint_values_device for a width x height map; all device
+ * pointers; max_hits >= 0 (0: count only, hits may be NULL). */
+typedef struct {
+    int32_t index; /* lattice point, (c - 1) * ny + (r - 1) */
+    float x, y, z; /* calcCoordinate's X, Y, Z */
+} mvsv_sample_hit;
+MVSV_API int mvsv_samplepoint_detect_device(mvsv_ctx* ctx, int n, const float* values, int width,
+                                            int height, const float* Q, float range_first,
+                                            float range_second, int max_hits, int* counts,
+                                            mvsv_sample_hit* hits);
+
 /* ---- frame stream ------------------------------------------
  * A camera loop pushes rectified pairs from host memory and pops int16 maps in
  * push order.  Up to `depth` frames are in flight: the upload of one frame, the
@@ -339,6 +387,30 @@ MVSV_API int mvsv_stream_push_raw(mvsv_stream* s, const uint8_t* left, size_t le
 MVSV_API int mvsv_stream_pop_pair(mvsv_stream* s, int16_t* out, size_t out_stride, float* means,
                                   uint8_t* rect_left, size_t rect_left_stride, uint8_t* rect_right,
                                   size_t rect_right_stride);
+
+/* The lattice detector in the stream (either kind): every frame's sample point
+ * values and hits are computed after its SGBM, on the same device stream as the
+ * mean grid, and come back with the frame -- the reference's loop with both
+ * detectors (trgt/demo.cpp:206-209,271-276) without the map visiting the host
+ * first.  roi: the part of the map the lattice is laid over (NULL: the whole map;
+ * it must lie inside the stream's frame), radius as for
+ * mvsv_samplepoint_values_device, Q / range_first / range_second as for
+ * mvsv_samplepoint_detect_device; max_hits <= 0: room for every point.  Allowed
+ * only while no frame is pending (MVSV_E_INVALID_ARG otherwise); a second call
+ * replaces the first.  A stream that never enables it enqueues nothing extra. */
+MVSV_API int mvsv_stream_enable_samplepoints(mvsv_stream* s, const mvsv_rect* roi, int radius,
+                                             const float* Q, float range_first, float range_second,
+                                             int max_hits);
+MVSV_API int mvsv_stream_disable_samplepoints(mvsv_stream* s);
+/* Waits for the oldest pending frame and copies its lattice results out without
+ * popping it (so it composes with pop, pop_view and pop_pair): values (nx * ny
+ * floats of the roi's layout), *count (all hits) and the first min(count,
+ * max_hits, capacity) hit records.  Every output may be NULL.
+ * MVSV_E_INVALID_ARG when the lattice is not enabled or no frame is pending; the
+ * frame's own error when its launch failed (as pop reports it).  The frame stays
+ * pending either way. */
+MVSV_API int mvsv_stream_front_samples(mvsv_stream* s, float* values, int* count,
+                                       mvsv_sample_hit* hits, int capacity);
 
 /* ---- before the path: rectification ---------------------------
  * cv::remap(src, dst, map_x, map_y, INTER_LINEAR) with BORDER_CONSTANT 0 for CV_8UC1

@@ -6,6 +6,9 @@
 //   struct Subimage                             inc/Subimage.h:17-47
 //   class MeanDisparityDetection                inc/MeanDisparityDetection.h,
 //                                               src/MeanDisparityDetection.cpp:71-266
+//   struct Samplepoint                          inc/Samplepoint.h:17-40
+//   class SamplepointDetection                  inc/SamplepointDetection.h,
+//                                               src/SamplePointDetection.cpp:29-178
 //   createDMapROIS                              trgt/mean_test.cpp:80-106
 //   mvsv::DisparityStream                       replaces the worker thread +
 //                                               condition variable of
@@ -18,6 +21,7 @@
 #ifndef MVSV_DETECTION_HPP
 #define MVSV_DETECTION_HPP
 
+#include <algorithm>
 #include <array>
 #include <map>
 #include <string>
@@ -252,6 +256,190 @@ private:
     std::pair<float, float> mRange{0, 0}, mRangeDisparity{0, 0};
 };
 
+struct Samplepoint {  // inc/Samplepoint.h:17-40
+    Samplepoint() = default;
+    Samplepoint(Point center_, int radius_)
+        : center(center_), radius(radius_),
+          roi{center_.x - radius_, center_.y - radius_, 2 * radius_ + 1, 2 * radius_ + 1}
+    {
+    }
+    void calculateSamplepointValue(const Mat& dMap)
+    {
+        if (radius > 0)
+            value = Utility::calcMeanDisparity(dMap(roi));
+        else
+            value = dMap.ptr<int16_t>(center.y)[center.x];
+    }
+    Point center;
+    int radius = 0;
+    Rect roi{0, 0, 0, 0};
+    float value = 0;
+};
+
+// A stream frame's lattice results (frontSamples of either stream class)
+struct SampleFrame {
+    std::vector<float> values;          // one per lattice point
+    int count = 0;                      // all hits of the frame (may exceed hits.size())
+    std::vector<mvsv_sample_hit> hits;  // exactly the first min(count, max_hits), index order
+};
+
+// The lattice detector: 5x5 patches every step_x x step_y pixels, in the
+// reference's order (columns in the outer loop).  The values come from the GPU
+// (mvsv_samplepoint_values, or a stream frame's); the decisions stay on the host
+// in the reference's order, or come from the stream as hit records.
+class SamplepointDetection {  // src/SamplePointDetection.cpp
+public:
+    static constexpr int kRadius = 2;  // :43
+
+    explicit SamplepointDetection(std::string pcl_dir = "pcl/samplepoint_detection") : mPclDir(std::move(pcl_dir)) {}
+
+    // :29-75
+    void init(const Mat& reference, const QMatrix& Q, float min_distance, float max_distance)
+    {
+        mSPVec.clear();
+        mQ = Q;
+        mRows = reference.rows;
+        mCols = reference.cols;
+        int distanceX = reference.cols / 8, distanceY = reference.rows / 8;
+        for (int c = 1; c < distanceX; ++c)
+            for (int r = 1; r < distanceY; ++r) {
+                Point center{c * (reference.cols / distanceX), r * (reference.rows / distanceY)};
+                mSPVec.emplace_back(center, kRadius);
+                mFoundObstacles.emplace_back(center, kRadius);  // the layout, for the visualisation
+            }
+        mCenterVec = {0.0f, 0.0f, 1.0f, 0.0f};
+        mImageCenter = {(int)mQ[3], (int)mQ[7]};
+        dMapValues lo = Utility::calcDMapValues({0, 0, min_distance * 1000}, mQ);
+        dMapValues hi = Utility::calcDMapValues({0, 0, max_distance * 1000}, mQ);
+        mRangeDisparity = {lo.dValue, hi.dValue};
+    }
+
+    // :117-129 (binning and mode are ignored there too); values: one float per
+    // sample point where they are at hand (a stream frame's), else computed here
+    void build(const Mat& dMap, int /*binning*/, int /*mode*/, const float* values = nullptr)
+    {
+        mDMap = dMap;
+        mDistanceVec.assign(mSPVec.size(), 0.0f);
+        if (values) {
+            std::copy(values, values + mSPVec.size(), mDistanceVec.begin());
+        } else {
+            if (dMap.type != MAT_16SC1 || dMap.rows != mRows || dMap.cols != mCols)
+                throw Error(MVSV_E_INVALID_ARG, "build: CV_16S map of init's size expected");
+            mvsv_ctx* c = thread_context();
+            check(mvsv_samplepoint_values(c, reinterpret_cast<const int16_t*>(dMap.data), dMap.step / 2, dMap.cols,
+                                          dMap.rows, kRadius, mDistanceVec.data()),
+                  c);
+        }
+        for (size_t i = 0; i < mSPVec.size(); ++i) mSPVec[i].value = mDistanceVec[i];
+    }
+
+    // :134-178
+    void detectObstacles()
+    {
+        mFoundObstacles.clear();
+        mFoundPoints.clear();
+        for (size_t i = 0; i < mDistanceVec.size(); ++i) {
+            if (mDistanceVec[i] < mRangeDisparity.first && mDistanceVec[i] > mRangeDisparity.second) {
+                Samplepoint s = mSPVec[i];
+                s.value = mDistanceVec[i];
+                mFoundObstacles.push_back(s);
+                dMapValues v{mDistanceVec[i], (float)s.center.x, (float)s.center.y};
+                mFoundPoints.push_back(Utility::calcCoordinate(v, mQ));
+            }
+        }
+        writeFound();
+    }
+    // the decisions of a stream frame (frontSamples) instead of the host's.
+    // count: the number of records that hits holds -- SampleFrame::hits.size(),
+    // i.e. min(the frame's hit count, the stream's max_hits), NOT SampleFrame::count
+    // when the stream caps the records.  Needs build() first (the values).
+    void detectObstacles(int count, const mvsv_sample_hit* hits)
+    {
+        if (mDistanceVec.size() != mSPVec.size())
+            throw Error(MVSV_E_INVALID_ARG, "detectObstacles: build() has not run");
+        if (count < 0 || (count > 0 && !hits)) throw Error(MVSV_E_INVALID_ARG, "detectObstacles: bad hit records");
+        mFoundObstacles.clear();
+        mFoundPoints.clear();
+        for (int k = 0; k < count; ++k) {
+            const mvsv_sample_hit& h = hits[k];
+            if (h.index < 0 || (size_t)h.index >= mSPVec.size())
+                throw Error(MVSV_E_INVALID_ARG, "detectObstacles: hit outside the lattice");
+            Samplepoint s = mSPVec[h.index];
+            s.value = mDistanceVec[h.index];
+            mFoundObstacles.push_back(s);
+            // the fourth element, which a record does not carry, from the point itself
+            dMapValues v{s.value, (float)s.center.x, (float)s.center.y};
+            mFoundPoints.push_back({h.x, h.y, h.z, Utility::calcCoordinate(v, mQ)[3]});
+        }
+        writeFound();
+    }
+    // the same from a frame as frontSamples filled it: the records it holds
+    void detectObstacles(const SampleFrame& f) { detectObstacles((int)f.hits.size(), f.hits.data()); }
+
+    void setRange(float min_distance, float max_distance) { mRange = {min_distance, max_distance}; }
+    std::pair<int, int> getRange() const { return {(int)mRange.first, (int)mRange.second}; }
+    const std::vector<Samplepoint>& getSamplepointVec() const { return mSPVec; }
+    const std::array<float, 4>& getCenterPoint() const { return mCenterVec; }
+    const std::vector<Samplepoint>& getFoundObstacles() const { return mFoundObstacles; }
+    int getObstacleCounter() const { return mObstacleCounter; }
+    std::pair<float, float> getRangeDisparity() const { return mRangeDisparity; }
+    const std::vector<std::array<float, 4>>& getFoundPoints() const { return mFoundPoints; }
+    const QMatrix& getQ() const { return mQ; }
+
+private:
+    void writeFound()
+    {
+        if (mFoundPoints.empty()) return;
+        ply p("Hagen Hiller", "obstacle pointcloud", mDMap);
+        std::string prefix = mObstacleCounter < 10 ? "000" : (mObstacleCounter < 100 ? "00" : "0");
+        p.write(mPclDir + "/pcl_" + prefix + std::to_string(mObstacleCounter) + ".ply", mFoundPoints,
+                ply::WITH_COLOR);
+        ++mObstacleCounter;
+    }
+
+    std::string mPclDir;
+    Mat mDMap;
+    std::vector<Samplepoint> mSPVec, mFoundObstacles;
+    std::vector<float> mDistanceVec;
+    std::vector<std::array<float, 4>> mFoundPoints;
+    std::array<float, 4> mCenterVec{0.0f, 0.0f, 1.0f, 0.0f};
+    Point mImageCenter;
+    QMatrix mQ{};
+    int mRows = 0, mCols = 0;
+    int mObstacleCounter = 0;
+    std::pair<float, float> mRange{0, 0}, mRangeDisparity{0, 0};
+};
+
+// what a stream class remembers of its enabled lattice
+struct SampleLayout {
+    int npts = 0;  // lattice points of the roi
+    int cap = 0;   // hit records a frame brings back at most (the effective max_hits)
+};
+
+// the lattice calls shared by DisparityStream and RawDisparityStream
+inline SampleLayout stream_enable_samplepoints(mvsv_ctx* ctx, mvsv_stream* s, int width, int height,
+                                               const SamplepointDetection& d, const Rect* roi, int max_hits)
+{
+    mvsv_rect r{0, 0, width, height};
+    if (roi) r = {roi->x, roi->y, roi->x + roi->width, roi->y + roi->height};
+    const std::pair<float, float> range = d.getRangeDisparity();
+    check(mvsv_stream_enable_samplepoints(s, &r, SamplepointDetection::kRadius, d.getQ().data(), range.first,
+                                          range.second, max_hits),
+          ctx);
+    int sx, sy, nx, ny;
+    check(mvsv_samplepoint_layout(r.x1 - r.x0, r.y1 - r.y0, &sx, &sy, &nx, &ny), ctx);
+    const int npts = nx * ny;
+    return {npts, max_hits <= 0 ? npts : std::min(max_hits, npts)};  // as the stream sizes its records
+}
+inline void stream_front_samples(mvsv_ctx* ctx, mvsv_stream* s, const SampleLayout& l, SampleFrame& out)
+{
+    out.values.resize((size_t)l.npts);
+    out.hits.resize((size_t)l.cap);
+    out.count = 0;
+    check(mvsv_stream_front_samples(s, out.values.data(), &out.count, out.hits.data(), l.cap), ctx);
+    out.hits.resize((size_t)std::max(0, std::min(out.count, l.cap)));  // only records that were written
+}
+
 // Camera loop without the worker thread: push rectified pairs, pop maps (and the
 // 9x9 means of the work ROI) in order; up to `depth` frames in flight.
 class DisparityStream {
@@ -296,11 +484,22 @@ public:
         check(mvsv_stream_pop_view(s_, &map, means81), ctx_);
         return map;
     }
+    // the lattice detector on every frame pushed from now on (no frame may be
+    // pending): d's Q and disparity range, over roi (d's init size; default the
+    // whole map); at most max_hits hit records per frame (<= 0: all)
+    void enableSamplepoints(const SamplepointDetection& d, const Rect* roi = nullptr, int max_hits = 0)
+    {
+        lattice_ = stream_enable_samplepoints(ctx_, s_, w_, h_, d, roi, max_hits);
+    }
+    void disableSamplepoints() { check(mvsv_stream_disable_samplepoints(s_), ctx_); }
+    // the oldest pending frame's lattice results; the frame stays pending (pop it next)
+    void frontSamples(SampleFrame& out) { stream_front_samples(ctx_, s_, lattice_, out); }
 
 private:
     mvsv_ctx* ctx_;
     mvsv_stream* s_ = nullptr;
     int w_, h_;
+    SampleLayout lattice_;
 };
 
 }  // namespace mvsv

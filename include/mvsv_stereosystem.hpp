@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "mvsv.h"
+#include "mvsv_detection.hpp"
 #include "mvsv_disparity.hpp"
 
 namespace mvsv {
@@ -364,11 +365,19 @@ public:
                                    rectified ? rectified->mRight.step : 0),
               mCtx);
     }
+    // the lattice detector on every frame, as on DisparityStream
+    void enableSamplepoints(const SamplepointDetection& d, const Rect* roi = nullptr, int max_hits = 0)
+    {
+        mLattice = stream_enable_samplepoints(mCtx, mStream, mW, mH, d, roi, max_hits);
+    }
+    void disableSamplepoints() { check(mvsv_stream_disable_samplepoints(mStream), mCtx); }
+    void frontSamples(SampleFrame& out) { stream_front_samples(mCtx, mStream, mLattice, out); }
 
 private:
     mvsv_ctx* mCtx = nullptr;
     mvsv_stream* mStream = nullptr;
     int mRawW, mRawH, mW = 0, mH = 0;
+    SampleLayout mLattice;
     bool mKeep;
 };
 

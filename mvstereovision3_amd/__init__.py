@@ -10,9 +10,10 @@ from ._lib import (MODE_HH, MODE_SGBM, MVSV_E_TIMEOUT, OPT_BITSLICE, OPT_BM_TILE
                    OPT_STRIP_SPIN_LIMIT, OPT_STRIP_WAVES,
                    PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, VARIANT_FIRSTCOL_FIX,
                    VARIANT_WTA_MIN_D, MvsvError, set_option, synchronize)
-from .disparity import (Disparity, StereoBM, StereoSGBM, Stereopair, mean_disparity_grid,
-                        sgbmParameters, synth_pair)
-from .detection import DisparityStream, MeanDisparityDetection, Subimage, create_dmap_rois
+from .disparity import (SAMPLE_HIT_DTYPE, Disparity, StereoBM, StereoSGBM, Stereopair, mean_disparity_grid,
+                        samplepoint_detect, samplepoint_layout, samplepoint_values, sgbmParameters, synth_pair)
+from .detection import (DisparityStream, MeanDisparityDetection, Samplepoint, SamplepointDetection, Subimage,
+                        create_dmap_rois)
 from .calibration import Stereosystem, read_matrix, stereo_rectify, write_matrices
 from .rectify import convert_maps, init_undistort_rectify_map, rectify_pair, remap
 from .utility import Utility, dMapValues, ply, reproject
@@ -25,6 +26,7 @@ __all__ = [
     "dMapValues", "ply", "reproject", "init_undistort_rectify_map", "rectify_pair", "remap",
     "synchronize", "set_option", "Stereosystem", "read_matrix", "write_matrices",
     "stereo_rectify", "convert_maps", "MVSV_E_TIMEOUT", "OPT_STRIP_SPIN_LIMIT", "OPT_STRIP_WAVES", "OPT_BM_TILE_ROWS",
-    "OPT_PATH_SCHEDULE", "OPT_BITSLICE",
+    "OPT_PATH_SCHEDULE", "OPT_BITSLICE", "Samplepoint", "SamplepointDetection", "samplepoint_layout",
+    "samplepoint_values", "samplepoint_detect", "SAMPLE_HIT_DTYPE",
 ]
 __version__ = "1.0.0"

@@ -154,6 +154,13 @@ def _declare(lib, strict=True):
         "mvsv_stream_size": ([P, ctypes.POINTER(I), ctypes.POINTER(I)], I),
         "mvsv_stream_push_raw": ([P, P, Z, P, Z], I),
         "mvsv_stream_pop_pair": ([P, P, Z, P, P, Z, P, Z], I),
+        "mvsv_samplepoint_layout": ([I, I] + [ctypes.POINTER(I)] * 4, I),
+        "mvsv_samplepoint_values_device": ([P, I, P, Z, Z, I, I, I, P], I),
+        "mvsv_samplepoint_values": ([P, P, Z, I, I, I, P], I),
+        "mvsv_samplepoint_detect_device": ([P, I, P, I, I, P, ctypes.c_float, ctypes.c_float, I, P, P], I),
+        "mvsv_stream_enable_samplepoints": ([P, P, I, P, ctypes.c_float, ctypes.c_float, I], I),
+        "mvsv_stream_disable_samplepoints": ([P], I),
+        "mvsv_stream_front_samples": ([P, P, ctypes.POINTER(I), P, I], I),
         "mvsv_convert_maps": ([P, P, Z, I, I, P, Z, P, Z], I),
         "mvsv_remap_device": ([P, I, P, Z, Z, I, I, P, P, Z, P, Z, Z, I, I], I),
         "mvsv_rectify_pair": ([P, P, Z, P, Z, I, I, P, P, P, Z, P, Z], I),

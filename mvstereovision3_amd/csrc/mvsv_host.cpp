@@ -696,6 +696,69 @@ int mvsv_mean_disparity_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, s
     return mark_last_use(ctx, mean_grid_device(ctx, n, dmap, st, fs, W, H, means));
 }
 
+int mvsv_samplepoint_layout(int W, int H, int* step_x, int* step_y, int* nx, int* ny)
+{
+    if (!step_x || !step_y || !nx || !ny) return MVSV_E_INVALID_ARG;
+    return sample_layout(W, H, step_x, step_y, nx, ny);
+}
+
+int mvsv_samplepoint_values_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
+                                   int radius, float* values)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0 || !dmap || W <= 0 || H <= 0 || st < (size_t)W)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point arguments");
+    int sx, sy, nx, ny;
+    sample_layout(W, H, &sx, &sy, &nx, &ny);
+    if (nx == 0 || ny == 0) return MVSV_OK;
+    if (!values) return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, sample_grid_device(ctx, n, dmap, st, fs, W, H, radius, values));
+}
+
+int mvsv_samplepoint_values(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, int radius, float* values)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (!dmap || W <= 0 || H <= 0 || st < (size_t)W)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point arguments");
+    int sx, sy, nx, ny;
+    sample_layout(W, H, &sx, &sy, &nx, &ny);
+    if (nx == 0 || ny == 0) return MVSV_OK;
+    if (!values) return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point arguments");
+    if (radius < 0 || radius >= std::min(sx, sy))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "sample point radius must be 0 .. min(step_x, step_y) - 1");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, [&]() -> int {  // every exit after an enqueue
+    const size_t px = (size_t)W * H, npts = (size_t)nx * ny;
+    int rc;
+    if ((rc = ensure(ctx, ctx->h_out, px * 2 + 4 + npts * sizeof(float), "sample point staging"))) return rc;
+    int16_t* d = (int16_t*)ctx->h_out.ptr;
+    float* v = (float*)(d + px + (px & 1));
+    hipStream_t s = ctx->stream;
+    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, (size_t)W * 2, dmap, st * 2, (size_t)W * 2, H,
+                                              hipMemcpyHostToDevice, s), "H2D map")) ||
+        (rc = sample_grid_device(ctx, 1, d, W, px, W, H, radius, v)) ||
+        (rc = check_hip(ctx, hipMemcpyAsync(values, v, npts * sizeof(float), hipMemcpyDeviceToHost, s),
+                        "D2H sample point values")))
+        return rc;
+    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
+    }());
+}
+
+int mvsv_samplepoint_detect_device(mvsv_ctx* ctx, int n, const float* values, int W, int H, const float* Q,
+                                   float first, float second, int max_hits, int* counts, mvsv_sample_hit* hits)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0 || W <= 0 || H <= 0 || !Q || max_hits < 0 || (max_hits > 0 && !hits))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point detection arguments");
+    int sx, sy, nx, ny;
+    sample_layout(W, H, &sx, &sy, &nx, &ny);
+    if (nx == 0 || ny == 0) return MVSV_OK;
+    if (!values || !counts) return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point detection arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, sample_detect_device(ctx, n, values, W, H, Q, first, second, max_hits, counts, hits));
+}
+
 // Host-pointer path: stage through cached device buffers, run, copy back, sync.
 static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs,
                      int W, int H, int16_t* out, size_t os, bool sgbm, const void* params)

@@ -266,5 +266,14 @@ int reproject_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_
                      const float* Q, float* out, size_t os, size_t ofs);
 int mean_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W,
                      int H, float* means);
+// SamplepointDetection's lattice (mvsv_post.hip).  sample_layout: steps and point
+// counts of a W x H map (nx * ny == 0: no point); the launches return MVSV_OK
+// without a launch for such a map.  values: nx * ny floats per frame, point
+// (c, r) at c * ny + r; hits: max_hits records per frame, counts: one int each.
+int sample_layout(int W, int H, int* step_x, int* step_y, int* nx, int* ny);
+int sample_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H, int radius,
+                       float* values);
+int sample_detect_device(mvsv_ctx* ctx, int n, const float* values, int W, int H, const float* Q, float first,
+                         float second, int max_hits, int* counts, mvsv_sample_hit* hits);
 
 }  // namespace mvsv

@@ -8,6 +8,8 @@
 //     yields exactly the same components as OpenCV's raster-order flood fill.
 //   * MeanDisparityDetection grid   (src/MeanDisparityDetection.cpp:159-206,
 //     Utility::calcMeanDisparity src/utility.cpp:265-285)
+//   * SamplepointDetection lattice  (src/SamplePointDetection.cpp: values of the
+//     5x5 patches, range test + ordered compaction + calcCoordinate of the hits)
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -652,6 +654,27 @@ struct QMat {
     float q[16];
 };
 
+// one point: (X, Y, Z) of (x, y, v) -- shared by the per-pixel kernel and the
+// lattice detector, so both round exactly as mvsv_calc_coordinate does
+__device__ __forceinline__ void calc_coordinate_dev(const QMat& Q, float x, float y, float v, float& X, float& Y,
+                                                    float& Z)
+{
+    const float c[4] = {x, y, v / 16.0f, 1.0f};
+    float r[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) acc = __dadd_rn(acc, __dmul_rn((double)Q.q[4 * i + k], (double)c[k]));
+        r[i] = (float)acc;
+    }
+    const float alpha = (float)(1.0 / (double)r[3]);
+    X = __fmul_rn(r[0], alpha);
+    Y = __fmul_rn(r[1], alpha);
+    Z = __fmul_rn(r[2], alpha);
+    if (isinf(__fdiv_rn(Z, 1000.0f))) Z = 0.0f;
+}
+
 __global__ __launch_bounds__(256) void reproject_kernel(const int16_t* __restrict__ dmap, size_t st,
                                                         size_t fs, int W, int H, QMat Q,
                                                         float4* __restrict__ out, size_t os,
@@ -662,19 +685,112 @@ __global__ __launch_bounds__(256) void reproject_kernel(const int16_t* __restric
     const int f = blockIdx.z;
     if (x >= W || y >= H) return;
     const float v = (float)dmap[f * fs + (size_t)y * st + x];
-    const float c[4] = {(float)x, (float)y, v / 16.0f, 1.0f};
-    float r[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) acc = __dadd_rn(acc, __dmul_rn((double)Q.q[4 * i + k], (double)c[k]));
-        r[i] = (float)acc;
-    }
-    const float alpha = (float)(1.0 / (double)r[3]);
-    float X = __fmul_rn(r[0], alpha), Y = __fmul_rn(r[1], alpha), Z = __fmul_rn(r[2], alpha);
-    if (isinf(__fdiv_rn(Z, 1000.0f))) Z = 0.0f;
+    float X, Y, Z;
+    calc_coordinate_dev(Q, (float)x, (float)y, v, X, Y, Z);
     out[f * ofs + (size_t)y * os + x] = make_float4(X, Y, Z, v > 0.0f ? 1.0f : 0.0f);
+}
+
+// ---- SamplepointDetection (src/SamplePointDetection.cpp:29-75,117-178) -------------
+// The lattice: dX = W / 8, dY = H / 8, steps W / dX, H / dY (8..15), centres
+// ((c + 1) * step_x, (r + 1) * step_y) for c < nx = dX - 1, r < ny = dY - 1, point
+// index c * ny + r (the reference's loops: columns outside, rows inside).
+//
+// Values (Samplepoint::calculateSamplepointValue, inc/Samplepoint.h:32-40): a
+// block takes up to kSpPts neighbouring points of one lattice row.  Its threads
+// walk the map columns of that stretch -- lane j reads column x0 + j of each of
+// the 2r + 1 map rows, so a wave reads contiguous row segments -- and leave each
+// column's filtered sum and count in LDS; columns between two patches are
+// skipped.  Then one lane per point adds its patch's 2r + 1 columns.  Radius 0
+// is the raw centre value (no > 1 filter).  The host checks radius <
+// min(step_x, step_y), which keeps every patch inside the map.
+constexpr int kSpPts = 32;
+constexpr int kSpSpan = 512;  // >= (kSpPts - 1) * 15 + 2 * 14 + 1 columns
+
+__global__ __launch_bounds__(256) void sample_grid_kernel(const int16_t* __restrict__ dmap, size_t st,
+                                                          size_t fs, int step_x, int step_y, int nx, int ny,
+                                                          int radius, float* __restrict__ values)
+{
+    __shared__ int s_tot[kSpSpan], s_cnt[kSpSpan];
+    const int c0 = blockIdx.x * kSpPts;
+    const int r = blockIdx.y, f = blockIdx.z;
+    const int pts = min(kSpPts, nx - c0);
+    const int rows = 2 * radius + 1;
+    const int span = (pts - 1) * step_x + rows;
+    const int16_t* m = dmap + f * fs + (size_t)((r + 1) * step_y - radius) * st + ((c0 + 1) * step_x - radius);
+    for (int j = threadIdx.x; j < span; j += 256) {
+        if (j % step_x >= rows) continue;  // between two patches
+        int tot = 0, cnt = 0;
+        if (radius == 0) {
+            tot = m[j];
+        } else {
+            for (int k = 0; k < rows; k++) {
+                const int v = m[(size_t)k * st + j];
+                if (v > 1) {
+                    tot += v;
+                    cnt++;
+                }
+            }
+        }
+        s_tot[j] = tot;
+        s_cnt[j] = cnt;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < pts) {
+        const int b = threadIdx.x * step_x;
+        int T = 0, N = 0;
+        for (int k = 0; k < rows; k++) {
+            T += s_tot[b + k];
+            N += s_cnt[b + k];
+        }
+        const float v = radius == 0 ? (float)T : ((T == 0 || N == 0) ? 0.0f : (float)(T / N));
+        values[(size_t)f * nx * ny + (size_t)(c0 + threadIdx.x) * ny + r] = v;
+    }
+}
+
+// Detection (SamplepointDetection::detectObstacles, :134-178): value < first &&
+// value > second, hits in index order with their calcCoordinate.  One block per
+// frame walks the points in chunks of its 1024 threads; a hit's output position
+// is the hits of earlier chunks + of earlier waves of the chunk (LDS) + of lower
+// lanes of its wave (ballot), so the order never depends on timing.  count is
+// the total; records beyond max_hits are dropped.
+__global__ __launch_bounds__(1024) void sample_detect_kernel(const float* __restrict__ values, int npts, int ny,
+                                                             int step_x, int step_y, QMat Q, float first,
+                                                             float second, int max_hits, int* __restrict__ counts,
+                                                             mvsv_sample_hit* __restrict__ hits)
+{
+    __shared__ int s_wave[16];
+    const int f = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const float* v = values + (size_t)f * npts;
+    mvsv_sample_hit* out = hits + (size_t)f * max_hits;
+    int base = 0;
+    for (int i0 = 0; i0 < npts; i0 += 1024) {
+        const int i = i0 + threadIdx.x;
+        const float val = i < npts ? v[i] : 0.0f;
+        const bool hit = i < npts && val < first && val > second;
+        const unsigned long long m = __ballot(hit);
+        if (lane == 0) s_wave[w] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const int c = s_wave[k];
+            before += k < w ? c : 0;
+            total += c;
+        }
+        const int pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
+        if (hit && pos < max_hits) {
+            const int c = i / ny, r = i - c * ny;
+            float X, Y, Z;
+            calc_coordinate_dev(Q, (float)((c + 1) * step_x), (float)((r + 1) * step_y), val, X, Y, Z);
+            out[pos].index = i;
+            out[pos].x = X;
+            out[pos].y = Y;
+            out[pos].z = Z;
+        }
+        base += total;
+        __syncthreads();  // s_wave is rewritten by the next chunk
+    }
+    if (threadIdx.x == 0) counts[f] = base;
 }
 
 }  // namespace
@@ -762,6 +878,44 @@ int mean_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_
     hipLaunchKernelGGL(mean_grid_kernel, dim3(81, n), dim3(256), 0, ctx->stream, dmap, st, fs, W,
                        H, means);
     return check_hip(ctx, hipGetLastError(), "mean disparity grid");
+}
+
+int sample_layout(int W, int H, int* step_x, int* step_y, int* nx, int* ny)
+{
+    if (W <= 0 || H <= 0) return MVSV_E_INVALID_ARG;
+    const int dX = W / 8, dY = H / 8;
+    *step_x = dX ? W / dX : 0;
+    *step_y = dY ? H / dY : 0;
+    *nx = std::max(dX - 1, 0);
+    *ny = std::max(dY - 1, 0);
+    return MVSV_OK;
+}
+
+int sample_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H, int radius,
+                       float* values)
+{
+    int sx, sy, nx, ny;
+    if (sample_layout(W, H, &sx, &sy, &nx, &ny)) return set_error(ctx, MVSV_E_INVALID_ARG, "empty map");
+    if (nx == 0 || ny == 0) return MVSV_OK;  // narrower or lower than 16: no lattice point
+    if (radius < 0 || radius >= std::min(sx, sy))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "sample point radius must be 0 .. min(step_x, step_y) - 1");
+    dim3 grid((nx + kSpPts - 1) / kSpPts, ny, n);
+    hipLaunchKernelGGL(sample_grid_kernel, grid, dim3(256), 0, ctx->stream, dmap, st, fs, sx, sy, nx, ny, radius,
+                       values);
+    return check_hip(ctx, hipGetLastError(), "sample point values");
+}
+
+int sample_detect_device(mvsv_ctx* ctx, int n, const float* values, int W, int H, const float* Q, float first,
+                         float second, int max_hits, int* counts, mvsv_sample_hit* hits)
+{
+    int sx, sy, nx, ny;
+    if (sample_layout(W, H, &sx, &sy, &nx, &ny)) return set_error(ctx, MVSV_E_INVALID_ARG, "empty map");
+    if (nx == 0 || ny == 0) return MVSV_OK;
+    QMat q;
+    for (int i = 0; i < 16; i++) q.q[i] = Q[i];
+    hipLaunchKernelGGL(sample_detect_kernel, dim3(n), dim3(1024), 0, ctx->stream, values, nx * ny, ny, sx, sy, q,
+                       first, second, max_hits, counts, hits);
+    return check_hip(ctx, hipGetLastError(), "sample point detection");
 }
 
 int remap_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh,

@@ -8,6 +8,9 @@
 // upload of frame i+1 (copy stream), the compute of frame i (context stream:
 // SGBM + the 9x9 mean grid of the ROI) and the download of frame i-1 (second
 // copy stream) overlap, and frames come back in push order.
+// With mvsv_stream_enable_samplepoints, SamplepointDetection's lattice values and
+// hits of every frame (trgt/demo.cpp:206-209,271-276 runs both detectors) are
+// computed next to the mean grid and come back with the frame (front_samples).
 // With mvsv_stream_set_batch(b), pushed frames are computed b at a time: the
 // slots' device buffers are one contiguous [depth][frame] array, so a group of
 // consecutive slots is one frame-batch launch (sustained rate of the batch
@@ -176,7 +179,35 @@ struct mvsv_stream {
     uint16_t* dMapFrac = nullptr; // [2][cropH][mapStride] ay * 32 + ax
     size_t mapStride = 0;         // entries per map row: cropW rounded up to 4, padding zero
     uint8_t *dCropL = nullptr, *dCropR = nullptr;  // [depth][cropH][cropW] each, with a factor
+    // SamplepointDetection's lattice over sp_roi of every frame
+    // (mvsv_stream_enable_samplepoints): values, hit count and hit records per
+    // slot, on the device and in one pinned host block
+    bool sp = false;
+    mvsv_rect sp_roi{};
+    int sp_radius = 0, sp_max = 0, sp_npts = 0;
+    float sp_Q[16] = {}, sp_first = 0, sp_second = 0;
+    float* dSpVal = nullptr;            // [depth][sp_npts]
+    int* dSpCnt = nullptr;              // [depth]
+    mvsv_sample_hit* dSpHits = nullptr; // [depth][sp_max]
+    uint8_t* hSp = nullptr;             // pinned: [depth] x (values, count, hits), sp_slot_bytes each
+    size_t sp_slot_bytes = 0;
+    float* sp_values(long i) const { return (float*)(hSp + (size_t)i * sp_slot_bytes); }
+    int* sp_count(long i) const { return (int*)(sp_values(i) + sp_npts); }
+    mvsv_sample_hit* sp_hits(long i) const { return (mvsv_sample_hit*)(sp_count(i) + 1); }
 };
+
+static void samplepoints_free(mvsv_stream* st)
+{
+    if (st->dSpVal) (void)hipFree(st->dSpVal);
+    if (st->dSpCnt) (void)hipFree(st->dSpCnt);
+    if (st->dSpHits) (void)hipFree(st->dSpHits);
+    if (st->hSp) (void)hipHostFree(st->hSp);
+    st->dSpVal = nullptr;
+    st->dSpCnt = nullptr;
+    st->dSpHits = nullptr;
+    st->hSp = nullptr;
+    st->sp = false;
+}
 
 // what mvsv_stream_create_raw adds to a stream's creation
 struct RawSetup {
@@ -207,6 +238,7 @@ static void stream_free(mvsv_stream* st)
     if (st->dMapFrac) (void)hipFree(st->dMapFrac);
     if (st->dCropL) (void)hipFree(st->dCropL);
     if (st->dCropR) (void)hipFree(st->dCropR);
+    samplepoints_free(st);
     if (st->rep) (void)hipHostFree(st->rep);
     if (st->up) (void)hipStreamDestroy(st->up);
     if (st->down) (void)hipStreamDestroy(st->down);
@@ -424,6 +456,16 @@ static int stream_launch(mvsv_stream* st)
             status = mean_grid_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, q.x1 - q.x0,
                                       q.y1 - q.y0, first.dMeans);
         }
+        if (status == MVSV_OK && st->sp && st->sp_npts > 0) {
+            const mvsv_rect& q = st->sp_roi;
+            const int rw = q.x1 - q.x0, rh = q.y1 - q.y0;
+            float* vals = st->dSpVal + (size_t)i0 * st->sp_npts;
+            status = sample_grid_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, rw, rh, st->sp_radius,
+                                        vals);
+            if (status == MVSV_OK)
+                status = sample_detect_device(ctx, n, vals, rw, rh, st->sp_Q, st->sp_first, st->sp_second,
+                                              st->sp_max, st->dSpCnt + i0, st->dSpHits + (size_t)i0 * st->sp_max);
+        }
         if (status != MVSV_OK && ctx != st->ctx) st->ctx->err = ctx->err;  // reported by pop
         st->runs++;
         if ((rc = mark_last_use(ctx, MVSV_OK)) ||
@@ -449,6 +491,19 @@ static int stream_launch(mvsv_stream* st)
                  (rc = check_hip(c, hipMemcpyAsync(s.hRectR, s.dR, px, hipMemcpyDeviceToHost, st->down),
                                  "stream D2H"))))
                 return rc;
+            if (st->sp && st->sp_npts > 0) {
+                // values, count and hit records are adjacent in the pinned slot
+                const long i = i0 + k;
+                if ((rc = check_hip(c, hipMemcpyAsync(st->sp_values(i), st->dSpVal + (size_t)i * st->sp_npts,
+                                                      (size_t)st->sp_npts * sizeof(float), hipMemcpyDeviceToHost,
+                                                      st->down), "stream D2H")) ||
+                    (rc = check_hip(c, hipMemcpyAsync(st->sp_count(i), st->dSpCnt + i, sizeof(int),
+                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")) ||
+                    (rc = check_hip(c, hipMemcpyAsync(st->sp_hits(i), st->dSpHits + (size_t)i * st->sp_max,
+                                                      (size_t)st->sp_max * sizeof(mvsv_sample_hit),
+                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")))
+                    return rc;
+            }
             if ((rc = check_hip(c, hipEventRecord(s.done, st->down), "stream event"))) return rc;
         }
         st->launched += n;
@@ -681,6 +736,89 @@ int mvsv_stream_pop_view(mvsv_stream* st, const int16_t** map, float* means)
     if (rc) return rc;
     *map = sp->hOut;
     stream_means(st, *sp, means);
+    return MVSV_OK;
+}
+
+int mvsv_stream_disable_samplepoints(mvsv_stream* st)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (st->head != st->tail)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "sample points change only while no frame is pending");
+    DeviceGuard dev_guard(st->ctx->device);
+    samplepoints_free(st);  // every frame was popped: nothing in flight uses the buffers
+    return MVSV_OK;
+}
+
+int mvsv_stream_enable_samplepoints(mvsv_stream* st, const mvsv_rect* roi, int radius, const float* Q, float first,
+                                    float second, int max_hits)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (!Q) return set_error(ctx, MVSV_E_INVALID_ARG, "null Q");
+    if (st->head != st->tail)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "sample points change only while no frame is pending");
+    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, st->W, st->H};
+    if (q.x0 < 0 || q.y0 < 0 || q.x1 > st->W || q.y1 > st->H || q.x1 <= q.x0 || q.y1 <= q.y0)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "sample point ROI empty or outside the image");
+    int sx, sy, nx, ny;
+    sample_layout(q.x1 - q.x0, q.y1 - q.y0, &sx, &sy, &nx, &ny);
+    const int npts = nx * ny;
+    if (npts > 0 && (radius < 0 || radius >= std::min(sx, sy)))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "sample point radius must be 0 .. min(step_x, step_y) - 1");
+    DeviceGuard dev_guard(ctx->device);
+    samplepoints_free(st);
+    st->sp_roi = q;
+    st->sp_radius = radius;
+    st->sp_npts = npts;
+    st->sp_max = max_hits <= 0 ? npts : std::min(max_hits, npts);
+    std::memcpy(st->sp_Q, Q, sizeof(st->sp_Q));
+    st->sp_first = first;
+    st->sp_second = second;
+    const size_t depth = st->slots.size();
+    st->sp_slot_bytes = ((size_t)npts * sizeof(float) + sizeof(int) + (size_t)st->sp_max * sizeof(mvsv_sample_hit) + 15) &
+                        ~(size_t)15;
+    if (npts > 0) {
+        const bool ok = hipMalloc((void**)&st->dSpVal, depth * npts * sizeof(float)) == hipSuccess &&
+                        hipMalloc((void**)&st->dSpCnt, depth * sizeof(int)) == hipSuccess &&
+                        hipMalloc((void**)&st->dSpHits, depth * st->sp_max * sizeof(mvsv_sample_hit)) == hipSuccess &&
+                        hipHostMalloc((void**)&st->hSp, depth * st->sp_slot_bytes, hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            samplepoints_free(st);
+            return set_error(ctx, MVSV_E_OOM, "sample point buffer allocation failed");
+        }
+    }
+    st->sp = true;
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_samples(mvsv_stream* st, float* values, int* count, mvsv_sample_hit* hits, int capacity)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (!st->sp) return set_error(ctx, MVSV_E_INVALID_ARG, "sample points are not enabled on this stream");
+    if (st->head == st->tail) return set_error(ctx, MVSV_E_INVALID_ARG, "stream empty");
+    if (hits && capacity < 0) return set_error(ctx, MVSV_E_INVALID_ARG, "negative capacity");
+    DeviceGuard dev_guard(ctx->device);
+    const long idx = st->tail % (long)st->slots.size();
+    auto& s = st->slots[idx];
+    int rc;
+    if (st->tail >= st->launched && (rc = stream_launch(st))) return rc;  // partial group
+    if ((rc = check_hip(ctx, hipEventSynchronize(s.done), "stream sync"))) return rc;
+    if (s.status) return s.status;
+    // the report word is left for pop to read and clear
+    if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[idx], __ATOMIC_ACQUIRE) != 0))
+        return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
+    if (st->sp_npts == 0) {
+        if (count) *count = 0;
+        return MVSV_OK;
+    }
+    const int total = *st->sp_count(idx);
+    if (values) std::memcpy(values, st->sp_values(idx), (size_t)st->sp_npts * sizeof(float));
+    if (count) *count = total;
+    if (hits)
+        std::memcpy(hits, st->sp_hits(idx),
+                    (size_t)std::min(std::min(total, st->sp_max), capacity) * sizeof(mvsv_sample_hit));
     return MVSV_OK;
 }
 

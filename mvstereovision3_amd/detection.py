@@ -1,4 +1,4 @@
-"""MeanDisparityDetection, Subimage and the camera-loop frame stream.
+"""MeanDisparityDetection, SamplepointDetection and the camera-loop frame stream.
 
 Mirrors src/MeanDisparityDetection.cpp:71-266, inc/Subimage.h:17-47,
 trgt/mean_test.cpp:80-106 (createDMapROIS) and replaces the disparity worker
@@ -6,6 +6,9 @@ thread of trgt/mean_test.cpp:61-70 with DisparityStream (mvsv_stream_*: upload,
 SGBM + 9x9 mean grid on the device, download, overlapped on HIP streams).
 The 81 tile means are computed on the GPU (mean_grid_kernel); the 81-element
 decisions stay on the host, exactly as the reference orders them.
+SamplepointDetection (src/SamplePointDetection.cpp:29-178, inc/Samplepoint.h:17-40) is
+the lattice detector: its values come from sample_grid_kernel, its decisions from the
+host or, on a stream, from sample_detect_kernel's hit records.
 """
 from __future__ import annotations
 
@@ -202,6 +205,189 @@ class MeanDisparityDetection:
         return printed
 
 
+class Samplepoint:
+    """inc/Samplepoint.h: a (2 * radius + 1)^2 patch around a lattice point."""
+
+    def __init__(self, center=(0, 0), radius=0):
+        self.center = (int(center[0]), int(center[1]))
+        self.radius = int(radius)
+        # cv::Rect(p1, p2) as (x, y, width, height)
+        self.roi = (self.center[0] - self.radius, self.center[1] - self.radius, 2 * self.radius + 1,
+                    2 * self.radius + 1)
+        self.value = 0.0
+
+    def calculateSamplepointValue(self, dMap):
+        d = np.asarray(dMap)
+        if self.radius > 0:
+            x, y, w, h = self.roi
+            self.value = Utility.calcMeanDisparity(d[y:y + h, x:x + w])
+        else:
+            self.value = float(d[self.center[1], self.center[0]])
+
+
+class SamplepointDetection:
+    """src/SamplePointDetection.cpp with the lattice values computed on the GPU.
+
+    A lattice of 5x5 patches, one every step_x x step_y pixels (8 for most
+    sizes), in the reference's order: columns in the outer loop, rows inside.
+    build() fills the values (sample_grid_kernel, or `values` from a
+    DisparityStream frame); detectObstacles() keeps the points whose value lies
+    inside the disparity range of [min, max] metres and reprojects them.
+    """
+
+    RADIUS = 2  # src/SamplePointDetection.cpp:43
+
+    def __init__(self, pcl_dir="pcl/samplepoint_detection"):
+        self.mSPVec: list[Samplepoint] = []
+        self.mFoundObstacles: list[Samplepoint] = []
+        self.mDistanceVec: list[float] = []
+        self.mFoundPoints: list[np.ndarray] = []
+        self.mCenterVec = np.array([0.0, 0.0, 1.0, 0.0], np.float32)
+        self.mImageCenter = (0, 0)
+        self.mObstacleCounter = 0
+        self.mRange = (0.0, 0.0)
+        self.mRangeDisparity = (0.0, 0.0)
+        self.mQ_32F = None
+        self.mDMap = None
+        self.pcl_dir = pcl_dir
+        self._shape = None
+        self._centers = np.empty((0, 2), np.float32)
+        self._q16 = None
+
+    def init(self, reference, Q, min_distance, max_distance):
+        """:29-75 — the lattice of `reference`'s size and the disparity range of [min, max] m."""
+        shape = reference if isinstance(reference, tuple) else np.asarray(reference).shape
+        rows, cols = int(shape[0]), int(shape[1])
+        self._shape = (rows, cols)
+        self.mSPVec = []
+        self.mQ_32F = np.asarray(Q, np.float32).reshape(4, 4)
+        distance_x, distance_y = cols // 8, rows // 8
+        for c in range(1, distance_x):
+            for r in range(1, distance_y):
+                center = (c * (cols // distance_x), r * (rows // distance_y))
+                self.mSPVec.append(Samplepoint(center, self.RADIUS))
+                # the layout, for the visualisation, until the first detectObstacles
+                self.mFoundObstacles.append(Samplepoint(center, self.RADIUS))
+        self.mCenterVec = np.array([0.0, 0.0, 1.0, 0.0], np.float32)
+        self.mImageCenter = (int(self.mQ_32F[0, 3]), int(self.mQ_32F[1, 3]))  # cv::Point = Point2i
+        self._centers = np.array([s.center for s in self.mSPVec], np.float32).reshape(len(self.mSPVec), 2)
+        self._q16 = np.ascontiguousarray(self.mQ_32F.reshape(16))
+        lo = Utility.calcDMapValues([0, 0, np.float32(min_distance) * np.float32(1000)], self.mQ_32F)
+        hi = Utility.calcDMapValues([0, 0, np.float32(max_distance) * np.float32(1000)], self.mQ_32F)
+        self.mRangeDisparity = (lo.dValue, hi.dValue)
+
+    def setRange(self, min_distance, max_distance):
+        """Stored only: detection uses the disparity range set by init, as in the reference."""
+        self.mRange = (float(np.float32(min_distance)), float(np.float32(max_distance)))
+
+    def getRange(self):
+        return int(self.mRange[0]), int(self.mRange[1])
+
+    def getRangeDisparity(self):
+        return self.mRangeDisparity
+
+    def getSamplepointVec(self):
+        return self.mSPVec
+
+    def getCenterPoint(self):
+        return self.mCenterVec
+
+    def getFoundObstacles(self):
+        return self.mFoundObstacles
+
+    def getFoundPoints(self):
+        return self.mFoundPoints
+
+    def getObstacleCounter(self):
+        return self.mObstacleCounter
+
+    def build(self, dMap, binning=0, mode=0, values=None):
+        """:117-129 (binning and mode are ignored there too).  dMap: host int16 map
+        or torch device tensor of init's size; values: the lattice values if they
+        are at hand already (DisparityStream.front_samples)."""
+        self.mDMap = dMap
+        n = len(self.mSPVec)
+        if values is not None:
+            v = np.asarray(values, np.float32).reshape(-1)
+            if v.size != n:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "build: one value per sample point expected")
+        else:
+            shape = tuple(dMap.shape)
+            if shape != self._shape:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "build: a map of init's size expected")
+            v = self._values(dMap, n)
+        self.mDistanceVec = v.tolist()
+        for s, x in zip(self.mSPVec, self.mDistanceVec):
+            s.value = x
+
+    def _values(self, dMap, n):
+        if type(dMap).__module__.startswith("torch"):
+            from .disparity import samplepoint_values
+            return samplepoint_values(dMap, self.RADIUS).cpu().numpy()
+        d = np.asarray(dMap)
+        if d.dtype != np.int16 or d.ndim != 2:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "build: 2-D int16 map expected")
+        if d.strides[1] != 2:
+            d = np.ascontiguousarray(d)
+        out = np.empty(n, np.float32)
+        if n:
+            ctx = context(0)
+            check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+            check(lib().mvsv_samplepoint_values(ctx.handle, d.ctypes.data, d.strides[0] // 2, d.shape[1],
+                                                d.shape[0], self.RADIUS, out.ctypes.data), ctx.handle)
+        return out
+
+    def detectObstacles(self, write_pcl=True, hits=None):
+        """:134-178.  hits: the (count, records) a DisparityStream frame brought
+        back (front_samples) instead of the host decision; records beyond the
+        stream's max_hits are not in it, so neither in the result."""
+        values = np.asarray(self.mDistanceVec, np.float32)
+        if hits is not None:
+            if values.size != len(self.mSPVec):
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "detectObstacles: build() has not run")
+            count, rec = hits
+            rec = np.asarray(rec)[:int(count)]
+            found = rec["index"].astype(np.int64)
+            if found.size and (found.min() < 0 or found.max() >= values.size):
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "detectObstacles: hit outside the lattice")
+            pts = np.empty((found.size, 4), np.float32)
+            pts[:, 0], pts[:, 1], pts[:, 2] = rec["x"], rec["y"], rec["z"]
+            # calcCoordinate's fourth element W * (float)(1 / W), which a record does
+            # not carry: Q's last row in mvsv_calc_coordinate's arithmetic
+            q = self._q16[12:].astype(np.float64)
+            c = self._centers[found].astype(np.float64)
+            d = (values[found] / np.float32(16)).astype(np.float64)
+            w = (((0.0 + q[0] * c[:, 0]) + q[1] * c[:, 1]) + q[2] * d + q[3]).astype(np.float32)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                pts[:, 3] = w * (1.0 / w.astype(np.float64)).astype(np.float32)
+        else:
+            lo, hi = np.float32(self.mRangeDisparity[0]), np.float32(self.mRangeDisparity[1])
+            # the reference's per-point test (float32 compares) over the lattice at
+            # once, then every found point's coordinate in one native call
+            found = np.flatnonzero((values < lo) & (values > hi))
+            pts = np.empty((found.size, 4), np.float32)
+            if found.size:
+                xyd = np.empty((found.size, 3), np.float32)
+                xyd[:, :2] = self._centers[found]
+                xyd[:, 2] = values[found]
+                lib().mvsv_calc_coordinates(int(found.size), xyd.ctypes.data, self._q16.ctypes.data,
+                                            pts.ctypes.data)
+        self.mFoundObstacles = []
+        for i in found:
+            s = Samplepoint(self.mSPVec[i].center, self.mSPVec[i].radius)
+            s.value = float(values[i])
+            self.mFoundObstacles.append(s)
+        self.mFoundPoints = list(pts)
+        if self.mFoundPoints and write_pcl:
+            c = self.mObstacleCounter
+            prefix = "000" if c < 10 else ("00" if c < 100 else "0")
+            path = os.path.join(self.pcl_dir, f"pcl_{prefix}{c}.ply")
+            dm = self.mDMap.cpu().numpy() if type(self.mDMap).__module__.startswith("torch") \
+                else np.asarray(self.mDMap)
+            ply("Hagen Hiller", "obstacle pointcloud", dm).write(path, pts, PLY_WITH_COLOR)
+            self.mObstacleCounter += 1
+
+
 class DisparityStream:
     """Double-buffered camera-loop pipeline over mvsv_stream (include/mvsv.h).
 
@@ -395,6 +581,56 @@ class DisparityStream:
                                     means.ctypes.data if means is not None else None),
               self._ctx.handle)
         return out, means
+
+    def enable_samplepoints(self, detector_or_args, roi=None, max_hits=None):
+        """SamplepointDetection's lattice on every frame from now on, computed
+        after SGBM on the device (mvsv_stream_enable_samplepoints); only while
+        no frame is pending.  detector_or_args: an initialised SamplepointDetection
+        (its Q, radius and disparity range), or (Q, range_first, range_second[,
+        radius]).  roi = (x0, y0, x1, y1): the part of the map the lattice is
+        laid over -- the detector's init size (default: the whole map).
+        max_hits: at most that many hit records per frame (default: all)."""
+        self._live()
+        d = detector_or_args
+        if hasattr(d, "mRangeDisparity"):
+            Q, first, second, radius = d._q16, d.mRangeDisparity[0], d.mRangeDisparity[1], d.RADIUS
+            if Q is None:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "enable_samplepoints: init() the detector first")
+        else:
+            Q, first, second = d[0], d[1], d[2]
+            radius = d[3] if len(d) > 3 else SamplepointDetection.RADIUS
+        q = np.ascontiguousarray(np.asarray(Q, np.float32).reshape(16))
+        r = Rect(*(int(v) for v in roi)) if roi is not None else None
+        check(lib().mvsv_stream_enable_samplepoints(self._h, ctypes.byref(r) if r is not None else None,
+                                                    int(radius), q.ctypes.data, float(first), float(second),
+                                                    0 if max_hits is None else int(max_hits)), self._ctx.handle)
+        w, h = (self.width, self.height) if roi is None else (r.x1 - r.x0, r.y1 - r.y0)
+        from .disparity import samplepoint_layout
+        _, _, nx, ny = samplepoint_layout(w, h)
+        self._sp_npts = nx * ny
+        self._sp_cap = self._sp_npts if max_hits is None or max_hits <= 0 else min(int(max_hits), self._sp_npts)
+
+    def disable_samplepoints(self):
+        self._live()
+        check(lib().mvsv_stream_disable_samplepoints(self._h), self._ctx.handle)
+        self._sp_npts = None
+
+    def front_samples(self):
+        """(values, count, hits) of the oldest pending frame, which stays pending
+        (pop it afterwards): the lattice values (float32), the number of hits
+        and the first min(count, max_hits) hit records as a structured array
+        (index, x, y, z) in index order."""
+        self._live()
+        from .disparity import SAMPLE_HIT_DTYPE
+        npts = getattr(self, "_sp_npts", None)
+        cap = self._sp_cap if npts is not None else 0
+        values = np.empty(npts or 0, np.float32)
+        hits = np.empty(cap, SAMPLE_HIT_DTYPE)
+        count = ctypes.c_int(0)
+        check(lib().mvsv_stream_front_samples(self._h, values.ctypes.data if values.size else None,
+                                              ctypes.byref(count), hits.ctypes.data if cap else None, cap),
+              self._ctx.handle)
+        return values, count.value, hits[:min(count.value, cap)]
 
     @staticmethod
     def _view_released(stream):

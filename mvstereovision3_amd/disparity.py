@@ -287,3 +287,72 @@ def mean_disparity_grid(dmap):
     check(lib().mvsv_mean_disparity_grid_device(ctx.handle, n, d.data_ptr(), d.stride(1),
                                                 d.stride(0), W, H, out.data_ptr()), ctx.handle)
     return out if batched else out[0]
+
+
+# mvsv_sample_hit (include/mvsv.h): a lattice point inside the range and its calcCoordinate
+SAMPLE_HIT_DTYPE = np.dtype([("index", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
+
+
+def samplepoint_layout(width, height):
+    """SamplepointDetection::init's lattice of a width x height map:
+    (step_x, step_y, nx, ny); point (c, r) is at ((c + 1) * step_x, (r + 1) * step_y)
+    and has index c * ny + r.  nx * ny == 0 for a map narrower or lower than 16."""
+    v = [ctypes.c_int() for _ in range(4)]
+    check(lib().mvsv_samplepoint_layout(int(width), int(height), *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def samplepoint_values(dmap, radius=2):
+    """SamplepointDetection::build on device: the value of every lattice point of
+    an int16 device map, (N, nx * ny) or (nx * ny,) float32 in the reference's
+    (column-major) point order."""
+    import torch
+    if not _is_torch(dmap) or not dmap.is_cuda or dmap.dtype != torch.int16:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "samplepoint_values: int16 device tensor expected")
+    batched = dmap.dim() == 3
+    d = dmap if batched else dmap.unsqueeze(0)
+    if d.stride(2) != 1:
+        d = d.contiguous()
+    n, H, W = d.shape
+    _, _, nx, ny = samplepoint_layout(W, H)
+    out = torch.empty((n, nx * ny), dtype=torch.float32, device=dmap.device)
+    ctx = context(dmap.device.index or 0)
+    check(lib().mvsv_set_stream(ctx.handle,
+                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
+          ctx.handle)
+    check(lib().mvsv_samplepoint_values_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
+                                               int(radius), out.data_ptr()), ctx.handle)
+    return out if batched else out[0]
+
+
+def samplepoint_detect(values, shape, Q, range_disparity, max_hits=None):
+    """SamplepointDetection::detectObstacles on device.  values: (N, nx * ny) or
+    (nx * ny,) float32 device tensor of a map of shape = (rows, cols);
+    range_disparity = (first, second): a hit has second < value < first.
+    Returns (counts, hits): int32 (N,) and uint8 (N, max_hits, 16) device tensors,
+    hits holding mvsv_sample_hit records (view the host copy as SAMPLE_HIT_DTYPE),
+    the first min(count, max_hits) of each frame in index order; max_hits=None:
+    room for every point.  Without the batch dimension: (count, hits[max_hits, 16])."""
+    import torch
+    if not _is_torch(values) or not values.is_cuda or values.dtype != torch.float32:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "samplepoint_detect: float32 device tensor expected")
+    batched = values.dim() == 2
+    v = (values if batched else values.unsqueeze(0)).contiguous()
+    H, W = int(shape[0]), int(shape[1])
+    _, _, nx, ny = samplepoint_layout(W, H)
+    if v.shape[1] != nx * ny:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "samplepoint_detect: values do not match the map's lattice")
+    n = v.shape[0]
+    cap = nx * ny if max_hits is None else int(max_hits)
+    counts = torch.zeros((n,), dtype=torch.int32, device=values.device)
+    hits = torch.zeros((n, cap, 16), dtype=torch.uint8, device=values.device)
+    q = np.ascontiguousarray(np.asarray(Q, np.float32).reshape(16))
+    ctx = context(values.device.index or 0)
+    check(lib().mvsv_set_stream(ctx.handle,
+                                ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)),
+          ctx.handle)
+    check(lib().mvsv_samplepoint_detect_device(ctx.handle, n, v.data_ptr(), W, H, q.ctypes.data,
+                                               float(range_disparity[0]), float(range_disparity[1]), cap,
+                                               counts.data_ptr(), hits.data_ptr() if cap else None),
+          ctx.handle)
+    return (counts, hits) if batched else (counts[0], hits[0])
