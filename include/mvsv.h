@@ -29,6 +29,12 @@
  *                                     Samplepoint inc/Samplepoint.h:17-40
  *   mvsv_stream_enable_samplepoints / both detectors on every frame of a stream
  *   _front_samples                    (trgt/demo.cpp:206-209,271-276)
+ *   mvsv_normalize_minmax(_device)    cv::normalize(dMap, dMapNorm, 0, 255, NORM_MINMAX, CV_8U)
+ *                                     trgt/liveDisparity.cpp:92, trgt/mean_test.cpp:307 and
+ *                                     the other loops' display step
+ *   mvsv_minmax_device                Utility::calcMinMaxDisparity src/utility.cpp:287-304
+ *   mvsv_stream_enable_display /      the display map with every frame of a stream
+ *   _front_display(_view)             (trgt/liveDisparity.cpp:88-95)
  *   mvsv_stream_*                     the disparity worker thread + main loop of
  *                                     trgt/mean_test.cpp:61-70,258-318 (condvar
  *                                     hand-off, Disparity::sgbm, build(MEAN_VALUE))
@@ -310,6 +316,41 @@ MVSV_API int mvsv_samplepoint_detect_device(mvsv_ctx* ctx, int n, const float* v
                                             float range_second, int max_hits, int* counts,
                                             mvsv_sample_hit* hits);
 
+/* ---- display maps: cv::normalize(NORM_MINMAX, CV_8U) of a disparity map ---------
+ * OpenCV 3.4's arithmetic (normalize -> Mat::convertTo, CV_16S -> CV_8U, no mask;
+ * its SSE2 / scalar form, where product and sum round separately):
+ *   smin, smax  the minimum / maximum over all values of the view (the invalid
+ *               marker (minDisparity - 1) * 16 included)
+ *   in double   dmin = min(alpha, beta), dmax = max(alpha, beta),
+ *               scale = (dmax - dmin) * (smax - smin > DBL_EPSILON ? 1 / (smax - smin) : 0),
+ *               shift = dmin - smin * scale, every operation rounded on its own
+ *   in float    out = saturate_u8(round_half_even((float)v * (float)scale + (float)shift)),
+ *               product and sum each rounded
+ * A constant map gives scale 0 and every pixel saturate(dmin).
+ *
+ * dmap: n int16 views (device pointers, strides in elements; any 2-byte-aligned
+ * view with stride >= width -- no byte outside [row, row + width) is touched).
+ * Row and frame strides that are multiples of 8 elements take packed 16-byte
+ * loads around narrow head / tail elements, other strides narrow loads; the
+ * results are the same.  All calls are asynchronous on the context's stream.
+ *
+ * minmax: [n][2] int16 (min, max) per frame.  positive_only != 0: over the
+ * values > 0 only (Utility::calcMinMaxDisparity's rule); a frame without one
+ * gives (32767, -32768). */
+MVSV_API int mvsv_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t stride, size_t frame_stride,
+                                int width, int height, int positive_only, int16_t* minmax);
+/* out: n uint8 maps (device pointer, strides in bytes, any alignment); minmax:
+ * device pointer, [n][2] (smin, smax) of every frame, or NULL.  Each frame is
+ * normalised with its own min / max. */
+MVSV_API int mvsv_normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t stride,
+                                          size_t frame_stride, int width, int height, double alpha, double beta,
+                                          uint8_t* out, size_t out_stride, size_t out_frame_stride,
+                                          int16_t* minmax);
+/* Same for one host map into a host image (synchronous); minmax: 2 int16 on the
+ * host, or NULL. */
+MVSV_API int mvsv_normalize_minmax(mvsv_ctx* ctx, const int16_t* dmap, size_t stride, int width, int height,
+                                   double alpha, double beta, uint8_t* out, size_t out_stride, int16_t* minmax);
+
 /* ---- frame stream ------------------------------------------
  * A camera loop pushes rectified pairs from host memory and pops int16 maps in
  * push order.  Up to `depth` frames are in flight: the upload of one frame, the
@@ -411,6 +452,27 @@ MVSV_API int mvsv_stream_disable_samplepoints(mvsv_stream* s);
  * pending either way. */
 MVSV_API int mvsv_stream_front_samples(mvsv_stream* s, float* values, int* count,
                                        mvsv_sample_hit* hits, int capacity);
+
+/* The display map in the stream (either kind): every frame's
+ * cv::normalize(dMap(roi), out, alpha, beta, NORM_MINMAX, CV_8U) is computed after
+ * its SGBM on the same device stream and comes back with the frame, next to the
+ * int16 map -- the last step of the reference's loops (trgt/liveDisparity.cpp:92;
+ * the detector loops normalise the work ROI, trgt/mean_test.cpp:307).  roi: NULL
+ * for the whole map; it must lie inside the stream's frame.  alpha, beta finite.
+ * Allowed only while no frame is pending (MVSV_E_INVALID_ARG otherwise); a second
+ * call replaces the first.  A stream that never enables it enqueues nothing extra. */
+MVSV_API int mvsv_stream_enable_display(mvsv_stream* s, const mvsv_rect* roi, double alpha, double beta);
+MVSV_API int mvsv_stream_disable_display(mvsv_stream* s);
+/* Waits for the oldest pending frame and copies its display map (roi height rows
+ * of roi width bytes, out_stride bytes apart) and minmax[2] = (smin, smax) out
+ * without popping it, so it composes with pop, pop_view, pop_pair and
+ * front_samples.  Either output may be NULL.  MVSV_E_INVALID_ARG when the display
+ * is not enabled or no frame is pending; the frame's own error when its launch
+ * failed (as pop reports it).  The frame stays pending either way. */
+MVSV_API int mvsv_stream_front_display(mvsv_stream* s, uint8_t* out, size_t out_stride, int16_t* minmax);
+/* Same without the copy: *map points at the frame's dense map (stride = roi
+ * width) in the stream's pinned slot, valid until the next push. */
+MVSV_API int mvsv_stream_front_display_view(mvsv_stream* s, const uint8_t** map, int16_t* minmax);
 
 /* ---- before the path: rectification ---------------------------
  * cv::remap(src, dst, map_x, map_y, INTER_LINEAR) with BORDER_CONSTANT 0 for CV_8UC1

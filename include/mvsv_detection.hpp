@@ -84,6 +84,19 @@ inline float calcMeanDisparity(const Mat& m)
     if (total == 0 || n == 0) return 0.0f;
     return (float)(total / (n < 0 ? -n : n));
 }
+// cv::normalize(dMap, out, alpha, beta, cv::NORM_MINMAX, CV_8U) on the device --
+// the display step of every loop of the reference (trgt/liveDisparity.cpp:92; the
+// detector loops pass the work ROI dMap(roi), trgt/mean_test.cpp:307).
+// minmax: where given, the (smin, smax) the map was normalised with.
+inline void normalize(const Mat& dMap, Mat& out, double alpha = 0, double beta = 255, int16_t* minmax = nullptr)
+{
+    if (dMap.type != MAT_16SC1 || dMap.empty()) throw Error(MVSV_E_INVALID_ARG, "normalize: CV_16S map expected");
+    out.create(dMap.rows, dMap.cols, MAT_8UC1);
+    mvsv_ctx* c = thread_context();
+    check(mvsv_normalize_minmax(c, reinterpret_cast<const int16_t*>(dMap.data), dMap.step / 2, dMap.cols, dMap.rows,
+                                alpha, beta, out.data, out.step, minmax),
+          c);
+}
 
 }  // namespace Utility
 
@@ -440,6 +453,25 @@ inline void stream_front_samples(mvsv_ctx* ctx, mvsv_stream* s, const SampleLayo
     out.hits.resize((size_t)std::max(0, std::min(out.count, l.cap)));  // only records that were written
 }
 
+// the display calls shared by DisparityStream and RawDisparityStream: the enabled
+// roi's size is what a stream class remembers
+struct DisplaySize {
+    int rows = 0, cols = 0;
+};
+inline DisplaySize stream_enable_display(mvsv_ctx* ctx, mvsv_stream* s, int width, int height, const Rect* roi,
+                                         double alpha, double beta)
+{
+    mvsv_rect r{0, 0, width, height};
+    if (roi) r = {roi->x, roi->y, roi->x + roi->width, roi->y + roi->height};
+    check(mvsv_stream_enable_display(s, &r, alpha, beta), ctx);
+    return {r.y1 - r.y0, r.x1 - r.x0};
+}
+inline void stream_front_display(mvsv_ctx* ctx, mvsv_stream* s, const DisplaySize& d, Mat& out, int16_t* minmax)
+{
+    if (d.rows > 0 && d.cols > 0) out.create(d.rows, d.cols, MAT_8UC1);
+    check(mvsv_stream_front_display(s, d.rows > 0 ? out.data : nullptr, out.step, minmax), ctx);
+}
+
 // Camera loop without the worker thread: push rectified pairs, pop maps (and the
 // 9x9 means of the work ROI) in order; up to `depth` frames in flight.
 class DisparityStream {
@@ -494,12 +526,33 @@ public:
     void disableSamplepoints() { check(mvsv_stream_disable_samplepoints(s_), ctx_); }
     // the oldest pending frame's lattice results; the frame stays pending (pop it next)
     void frontSamples(SampleFrame& out) { stream_front_samples(ctx_, s_, lattice_, out); }
+    // the 8-bit display map (Utility::normalize of dMap(roi)) with every frame pushed
+    // from now on (no frame may be pending); default roi: the whole map
+    void enableDisplay(const Rect* roi = nullptr, double alpha = 0, double beta = 255)
+    {
+        display_ = stream_enable_display(ctx_, s_, w_, h_, roi, alpha, beta);
+    }
+    void disableDisplay()
+    {
+        check(mvsv_stream_disable_display(s_), ctx_);
+        display_ = {};
+    }
+    // the oldest pending frame's display map and (smin, smax); the frame stays pending
+    void frontDisplay(Mat& out, int16_t* minmax = nullptr) { stream_front_display(ctx_, s_, display_, out, minmax); }
+    // the same map in the stream's pinned host slot (dense, no copy), valid until the next push
+    const uint8_t* frontDisplayView(int16_t* minmax = nullptr)
+    {
+        const uint8_t* map = nullptr;
+        check(mvsv_stream_front_display_view(s_, &map, minmax), ctx_);
+        return map;
+    }
 
 private:
     mvsv_ctx* ctx_;
     mvsv_stream* s_ = nullptr;
     int w_, h_;
     SampleLayout lattice_;
+    DisplaySize display_;
 };
 
 }  // namespace mvsv

@@ -372,12 +372,27 @@ public:
     }
     void disableSamplepoints() { check(mvsv_stream_disable_samplepoints(mStream), mCtx); }
     void frontSamples(SampleFrame& out) { stream_front_samples(mCtx, mStream, mLattice, out); }
+    // the 8-bit display map on every frame, as on DisparityStream
+    void enableDisplay(const Rect* roi = nullptr, double alpha = 0, double beta = 255)
+    {
+        mDisplay = stream_enable_display(mCtx, mStream, mW, mH, roi, alpha, beta);
+    }
+    void disableDisplay()
+    {
+        check(mvsv_stream_disable_display(mStream), mCtx);
+        mDisplay = {};
+    }
+    void frontDisplay(Mat& out, int16_t* minmax = nullptr)
+    {
+        stream_front_display(mCtx, mStream, mDisplay, out, minmax);
+    }
 
 private:
     mvsv_ctx* mCtx = nullptr;
     mvsv_stream* mStream = nullptr;
     int mRawW, mRawH, mW = 0, mH = 0;
     SampleLayout mLattice;
+    DisplaySize mDisplay;
     bool mKeep;
 };
 

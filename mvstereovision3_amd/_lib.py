@@ -161,6 +161,13 @@ def _declare(lib, strict=True):
         "mvsv_stream_enable_samplepoints": ([P, P, I, P, ctypes.c_float, ctypes.c_float, I], I),
         "mvsv_stream_disable_samplepoints": ([P], I),
         "mvsv_stream_front_samples": ([P, P, ctypes.POINTER(I), P, I], I),
+        "mvsv_minmax_device": ([P, I, P, Z, Z, I, I, I, P], I),
+        "mvsv_normalize_minmax_device": ([P, I, P, Z, Z, I, I, ctypes.c_double, ctypes.c_double, P, Z, Z, P], I),
+        "mvsv_normalize_minmax": ([P, P, Z, I, I, ctypes.c_double, ctypes.c_double, P, Z, P], I),
+        "mvsv_stream_enable_display": ([P, P, ctypes.c_double, ctypes.c_double], I),
+        "mvsv_stream_disable_display": ([P], I),
+        "mvsv_stream_front_display": ([P, P, Z, P], I),
+        "mvsv_stream_front_display_view": ([P, ctypes.POINTER(P), P], I),
         "mvsv_convert_maps": ([P, P, Z, I, I, P, Z, P, Z], I),
         "mvsv_remap_device": ([P, I, P, Z, Z, I, I, P, P, Z, P, Z, Z, I, I], I),
         "mvsv_rectify_pair": ([P, P, Z, P, Z, I, I, P, P, P, Z, P, Z], I),

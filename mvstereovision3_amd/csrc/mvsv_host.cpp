@@ -406,7 +406,7 @@ int mvsv_trim(mvsv_ctx* ctx)
                      &ctx->uf_tile, &ctx->tri_bnd, &ctx->bs_bnd, &ctx->status,
                      &ctx->dummy, &ctx->keys,
                      &ctx->bm_lf, &ctx->bm_rf, &ctx->bm_cost, &ctx->bm_sad, &ctx->h_left, &ctx->h_right,
-                     &ctx->h_out};
+                     &ctx->h_out, &ctx->mm_part};
     for (DevBuf* b : all) free_buf(*b);
     return MVSV_OK;
 }
@@ -757,6 +757,55 @@ int mvsv_samplepoint_detect_device(mvsv_ctx* ctx, int n, const float* values, in
     if (!values || !counts) return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point detection arguments");
     DeviceGuard dev_guard(ctx->device);
     return mark_last_use(ctx, sample_detect_device(ctx, n, values, W, H, Q, first, second, max_hits, counts, hits));
+}
+
+int mvsv_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
+                       int positive_only, int16_t* minmax)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0 || !dmap || !minmax || W <= 0 || H <= 0 || st < (size_t)W)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad min / max arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, minmax_device(ctx, n, dmap, st, fs, W, H, positive_only != 0, minmax));
+}
+
+int mvsv_normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
+                                 double alpha, double beta, uint8_t* out, size_t os, size_t ofs, int16_t* minmax)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0 || !dmap || !out || W <= 0 || H <= 0 || st < (size_t)W || os < (size_t)W || !std::isfinite(alpha) ||
+        !std::isfinite(beta))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad normalize arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, normalize_minmax_device(ctx, n, dmap, st, fs, W, H, alpha, beta, out, os, ofs, minmax));
+}
+
+int mvsv_normalize_minmax(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, double alpha, double beta,
+                          uint8_t* out, size_t os, int16_t* minmax)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (!dmap || !out || W <= 0 || H <= 0 || st < (size_t)W || os < (size_t)W || !std::isfinite(alpha) ||
+        !std::isfinite(beta))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad normalize arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, [&]() -> int {  // every exit after an enqueue
+    // staged rows are a multiple of 8 elements apart: the packed path for any width
+    const size_t ws = ((size_t)W + 7) & ~(size_t)7, px = ws * H;
+    int rc;
+    if ((rc = ensure(ctx, ctx->h_out, px * 3 + 4, "normalize staging"))) return rc;
+    int16_t* d = (int16_t*)ctx->h_out.ptr;
+    uint8_t* o = (uint8_t*)(d + px);
+    int16_t* mm = (int16_t*)(o + px);
+    hipStream_t s = ctx->stream;
+    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, ws * 2, dmap, st * 2, (size_t)W * 2, H, hipMemcpyHostToDevice, s),
+                        "H2D map")) ||
+        (rc = normalize_minmax_device(ctx, 1, d, ws, px, W, H, alpha, beta, o, ws, px, mm)) ||
+        (rc = check_hip(ctx, hipMemcpy2DAsync(out, os, o, ws, (size_t)W, H, hipMemcpyDeviceToHost, s),
+                        "D2H display map")) ||
+        (minmax && (rc = check_hip(ctx, hipMemcpyAsync(minmax, mm, 4, hipMemcpyDeviceToHost, s), "D2H min / max"))))
+        return rc;
+    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
+    }());
 }
 
 // Host-pointer path: stage through cached device buffers, run, copy back, sync.

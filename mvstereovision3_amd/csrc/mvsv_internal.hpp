@@ -159,6 +159,8 @@ struct mvsv_ctx {
     mvsv::DevBuf bm_lf, bm_rf, bm_cost, bm_sad;
     // host-pointer staging
     mvsv::DevBuf h_left, h_right, h_out;
+    // display maps: one (min, max) pair per block of minmax_kernel, [n][blocks][2] ints
+    mvsv::DevBuf mm_part;
     // stage profiling (HIP events on the context stream)
     int prof = 0;
     struct Mark {
@@ -275,5 +277,13 @@ int sample_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, siz
                        float* values);
 int sample_detect_device(mvsv_ctx* ctx, int n, const float* values, int W, int H, const float* Q, float first,
                          float second, int max_hits, int* counts, mvsv_sample_hit* hits);
+// Display maps (mvsv_post.hip).  minmax: [n][2] int16 (min, max) of every frame,
+// positive_only: over the values > 0 only, (32767, -32768) for none.
+// normalize_minmax_device: cv::normalize(NORM_MINMAX, CV_8U) of every frame with
+// its own min / max, which also go to minmax where it is not null.
+int minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H, bool positive_only,
+                  int16_t* minmax);
+int normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
+                            double alpha, double beta, uint8_t* out, size_t os, size_t ofs, int16_t* minmax);
 
 }  // namespace mvsv

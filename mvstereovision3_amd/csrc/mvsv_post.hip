@@ -10,6 +10,8 @@
 //     Utility::calcMeanDisparity src/utility.cpp:265-285)
 //   * SamplepointDetection lattice  (src/SamplePointDetection.cpp: values of the
 //     5x5 patches, range test + ordered compaction + calcCoordinate of the hits)
+//   * display maps                  (cv::normalize(dMap, out, 0, 255, NORM_MINMAX,
+//     CV_8U) of the reference's loops; min / max of Utility::calcMinMaxDisparity)
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -793,6 +795,177 @@ __global__ __launch_bounds__(1024) void sample_detect_kernel(const float* __rest
     if (threadIdx.x == 0) counts[f] = base;
 }
 
+// ---- display maps: cv::normalize(dMap, out, alpha, beta, NORM_MINMAX, CV_8U) ---------
+// (trgt/liveDisparity.cpp:92 and every other loop of the reference), and the
+// min / max of Utility::calcMinMaxDisparity (src/utility.cpp:287-304).
+//
+// A row of a view is walked as head | nvec packed 16-byte groups | tail: the
+// host picks `head` so that row + head is 16-byte aligned in every row of every
+// frame (display_split), or head = W (nvec = 0) where the strides do not allow
+// that.  Head and tail elements are 2-byte loads, so no access leaves
+// [row, row + W).  A wave takes a row, its lanes neighbouring elements / groups.
+constexpr int kMmBlocks = 64;  // partial pairs per frame at most: one wave folds them
+constexpr int kNormRows = 8;   // rows per block of normalize_u8_kernel (two per wave)
+
+__device__ __forceinline__ int wave_max_i32(int v)
+{
+    v = row_max_i32(v);
+    const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
+    const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
+    return max(max(a, b), max(c, d));
+}
+
+// Min and max of the part of a frame its block's waves walk: one (min, max)
+// pair per block, written unconditionally -- no atomics, no init pass, the same
+// partials on every run.  kPositive: only values > 0 count (calcMinMaxDisparity's
+// rule); a block that saw none leaves the identities (32767, -32768).
+template <bool kPositive>
+__global__ __launch_bounds__(256) void minmax_kernel(const int16_t* __restrict__ dmap, size_t st, size_t fs, int W,
+                                                     int H, int head, int nvec, int2* __restrict__ partials)
+{
+    __shared__ int s_lo[4], s_hi[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, f = blockIdx.y;
+    const int16_t* m = dmap + f * fs;
+    int lo = 32767, hi = -32768;
+    auto take = [&](int v) {
+        if (!kPositive || v > 0) {
+            lo = min(lo, v);
+            hi = max(hi, v);
+        }
+    };
+    const int tail0 = head + nvec * 8;
+    for (int y = blockIdx.x * 4 + w; y < H; y += gridDim.x * 4) {
+        const int16_t* r = m + (size_t)y * st;
+        for (int x = lane; x < head; x += 64) take(r[x]);
+        const uint4* rv = (const uint4*)(r + head);
+        for (int j = lane; j < nvec; j += 64) {
+            const uint4 q = rv[j];
+            take(lo16(q.x)); take(hi16(q.x)); take(lo16(q.y)); take(hi16(q.y));
+            take(lo16(q.z)); take(hi16(q.z)); take(lo16(q.w)); take(hi16(q.w));
+        }
+        for (int x = tail0 + lane; x < W; x += 64) take(r[x]);
+    }
+    lo = wave_min_i32(lo);
+    hi = wave_max_i32(hi);
+    if (lane == 0) {
+        s_lo[w] = lo;
+        s_hi[w] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partials[(size_t)f * gridDim.x + blockIdx.x] = make_int2(min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3])),
+                                                                 max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3])));
+}
+
+// a frame's nblk <= 64 partial pairs folded by one (whole) wave; wave-uniform result
+__device__ __forceinline__ void fold_partials(const int2* __restrict__ partials, int f, int nblk, int lane, int& lo,
+                                              int& hi)
+{
+    int2 p = make_int2(32767, -32768);
+    if (lane < nblk) p = partials[(size_t)f * nblk + lane];
+    lo = wave_min_i32(p.x);
+    hi = wave_max_i32(p.y);
+}
+
+__global__ __launch_bounds__(64) void minmax_final_kernel(const int2* __restrict__ partials, int nblk,
+                                                          int16_t* __restrict__ minmax)
+{
+    int lo, hi;
+    fold_partials(partials, blockIdx.x, nblk, threadIdx.x, lo, hi);
+    if (threadIdx.x == 0) {
+        minmax[2 * blockIdx.x] = (int16_t)lo;
+        minmax[2 * blockIdx.x + 1] = (int16_t)hi;
+    }
+}
+
+// OpenCV 3.4's arithmetic (normalize -> Mat::convertTo, CV_16S -> CV_8U, SSE2 /
+// scalar form): scale and shift in double, every operation rounded on its own;
+// then per pixel a float product and a float sum, each rounded, and a convert
+// with round-half-to-even and saturation.  The library is built with the
+// compiler's default contraction, which would fuse smin * scale into the
+// subtraction and the pixel's product into its sum (the rounding intrinsics
+// are plain operators once inlined): contraction is off in these two functions.
+__device__ __forceinline__ void display_scale(int smin, int smax, double dmin, double dmax, float& sf, float& hf)
+{
+#pragma clang fp contract(off)
+    const double range = (double)smax - (double)smin;
+    const double recip = range > DBL_EPSILON ? 1.0 / range : 0.0;
+    const double scale = (dmax - dmin) * recip;
+    const double prod = (double)smin * scale;
+    const double shift = dmin - prod;
+    sf = (float)scale;
+    hf = (float)shift;
+}
+
+__device__ __forceinline__ uint32_t display_u8(int v, float sf, float hf)
+{
+#pragma clang fp contract(off)
+    const float p = (float)v * sf;
+    const float t = p + hf;
+    return (uint32_t)clampi(__float2int_rn(t), 0, 255);
+}
+
+// Block (tile, frame): kNormRows rows of a frame to 8 bit.  Wave 0 folds the
+// frame's partials and lane 0 derives (sf, hf) once for the block.  A packed group
+// is 8 pixels = 8 output bytes, stored as one, two, four or eight stores by the
+// alignment of out + head (store_w, chosen by the host for the whole launch).
+__global__ __launch_bounds__(256) void normalize_u8_kernel(const int16_t* __restrict__ dmap, size_t st, size_t fs,
+                                                           int W, int H, int head, int nvec,
+                                                           const int2* __restrict__ partials, int nblk, double dmin,
+                                                           double dmax, uint8_t* __restrict__ out, size_t os,
+                                                           size_t ofs, int store_w, int16_t* __restrict__ minmax)
+{
+    __shared__ float s_sf, s_hf;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, f = blockIdx.y;
+    if (w == 0) {
+        int lo, hi;
+        fold_partials(partials, f, nblk, lane, lo, hi);
+        if (lane == 0) {
+            float sf, hf;
+            display_scale(lo, hi, dmin, dmax, sf, hf);
+            s_sf = sf;
+            s_hf = hf;
+            if (minmax && blockIdx.x == 0) {
+                minmax[2 * f] = (int16_t)lo;
+                minmax[2 * f + 1] = (int16_t)hi;
+            }
+        }
+    }
+    __syncthreads();
+    const float sf = s_sf, hf = s_hf;
+    const int tail0 = head + nvec * 8;
+    const int y1 = min(H, ((int)blockIdx.x + 1) * kNormRows);
+    for (int y = blockIdx.x * kNormRows + w; y < y1; y += 4) {
+        const int16_t* r = dmap + f * fs + (size_t)y * st;
+        uint8_t* o = out + f * ofs + (size_t)y * os;
+        for (int x = lane; x < head; x += 64) o[x] = (uint8_t)display_u8(r[x], sf, hf);
+        const uint4* rv = (const uint4*)(r + head);
+        for (int j = lane; j < nvec; j += 64) {
+            const uint4 q = rv[j];
+            const uint32_t b0 = display_u8(lo16(q.x), sf, hf), b1 = display_u8(hi16(q.x), sf, hf);
+            const uint32_t b2 = display_u8(lo16(q.y), sf, hf), b3 = display_u8(hi16(q.y), sf, hf);
+            const uint32_t b4 = display_u8(lo16(q.z), sf, hf), b5 = display_u8(hi16(q.z), sf, hf);
+            const uint32_t b6 = display_u8(lo16(q.w), sf, hf), b7 = display_u8(hi16(q.w), sf, hf);
+            uint8_t* p = o + head + (size_t)j * 8;
+            if (store_w == 8) {
+                *(uint2*)p = make_uint2(b0 | b1 << 8 | b2 << 16 | b3 << 24, b4 | b5 << 8 | b6 << 16 | b7 << 24);
+            } else if (store_w == 4) {
+                ((uint32_t*)p)[0] = b0 | b1 << 8 | b2 << 16 | b3 << 24;
+                ((uint32_t*)p)[1] = b4 | b5 << 8 | b6 << 16 | b7 << 24;
+            } else if (store_w == 2) {
+                ((uint16_t*)p)[0] = (uint16_t)(b0 | b1 << 8);
+                ((uint16_t*)p)[1] = (uint16_t)(b2 | b3 << 8);
+                ((uint16_t*)p)[2] = (uint16_t)(b4 | b5 << 8);
+                ((uint16_t*)p)[3] = (uint16_t)(b6 | b7 << 8);
+            } else {
+                p[0] = (uint8_t)b0; p[1] = (uint8_t)b1; p[2] = (uint8_t)b2; p[3] = (uint8_t)b3;
+                p[4] = (uint8_t)b4; p[5] = (uint8_t)b5; p[6] = (uint8_t)b6; p[7] = (uint8_t)b7;
+            }
+        }
+        for (int x = tail0 + lane; x < W; x += 64) o[x] = (uint8_t)display_u8(r[x], sf, hf);
+    }
+}
+
 }  // namespace
 
 int median3x3_device(mvsv_ctx* ctx, int n, const int16_t* src, size_t ss, size_t sfs, int16_t* dst,
@@ -916,6 +1089,62 @@ int sample_detect_device(mvsv_ctx* ctx, int n, const float* values, int W, int H
     hipLaunchKernelGGL(sample_detect_kernel, dim3(n), dim3(1024), 0, ctx->stream, values, nx * ny, ny, sx, sy, q,
                        first, second, max_hits, counts, hits);
     return check_hip(ctx, hipGetLastError(), "sample point detection");
+}
+
+// The packed path needs row + head 16-byte aligned in every row of every frame:
+// row and frame strides that are multiples of 8 elements (16 bytes), any
+// 2-byte-aligned base -- head = the 0..7 elements up to the next 16-byte
+// boundary.  Other strides take the narrow path (head = W: 2-byte loads only).
+static void display_split(const int16_t* dmap, size_t st, size_t fs, int n, int W, int* head, int* nvec)
+{
+    const bool packed = st % 8 == 0 && (n == 1 || fs % 8 == 0) && ((uintptr_t)dmap & 1) == 0;
+    *head = packed ? std::min(W, (int)(((16 - ((uintptr_t)dmap & 15)) & 15) / 2)) : W;
+    *nvec = (W - *head) / 8;
+}
+
+static int minmax_partials(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
+                           bool positive_only, int* nblk)
+{
+    int rc, head, nvec;
+    // room for 16 frames at least: the usual batches never grow (and so never synchronise) it
+    if ((rc = ensure(ctx, ctx->mm_part, (size_t)std::max(n, 16) * kMmBlocks * sizeof(int2), "min / max partials")))
+        return rc;
+    display_split(dmap, st, fs, n, W, &head, &nvec);
+    *nblk = std::min(kMmBlocks, (H + 3) / 4);
+    dim3 grid(*nblk, n);
+    if (positive_only)
+        hipLaunchKernelGGL(minmax_kernel<true>, grid, dim3(256), 0, ctx->stream, dmap, st, fs, W, H, head, nvec,
+                           (int2*)ctx->mm_part.ptr);
+    else
+        hipLaunchKernelGGL(minmax_kernel<false>, grid, dim3(256), 0, ctx->stream, dmap, st, fs, W, H, head, nvec,
+                           (int2*)ctx->mm_part.ptr);
+    return check_hip(ctx, hipGetLastError(), "min / max");
+}
+
+int minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H, bool positive_only,
+                  int16_t* minmax)
+{
+    int rc, nblk;
+    if ((rc = minmax_partials(ctx, n, dmap, st, fs, W, H, positive_only, &nblk))) return rc;
+    hipLaunchKernelGGL(minmax_final_kernel, dim3(n), dim3(64), 0, ctx->stream, (const int2*)ctx->mm_part.ptr, nblk,
+                       minmax);
+    return check_hip(ctx, hipGetLastError(), "min / max");
+}
+
+int normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
+                            double alpha, double beta, uint8_t* out, size_t os, size_t ofs, int16_t* minmax)
+{
+    int rc, nblk, head, nvec;
+    if ((rc = minmax_partials(ctx, n, dmap, st, fs, W, H, false, &nblk))) return rc;
+    display_split(dmap, st, fs, n, W, &head, &nvec);
+    // the widest store that is aligned at out + head of every row of every frame
+    const uintptr_t a = ((uintptr_t)out + head) | os | (n == 1 ? 0 : ofs);
+    const int store_w = a % 8 == 0 ? 8 : a % 4 == 0 ? 4 : a % 2 == 0 ? 2 : 1;
+    dim3 grid((H + kNormRows - 1) / kNormRows, n);
+    hipLaunchKernelGGL(normalize_u8_kernel, grid, dim3(256), 0, ctx->stream, dmap, st, fs, W, H, head, nvec,
+                       (const int2*)ctx->mm_part.ptr, nblk, std::min(alpha, beta), std::max(alpha, beta), out, os,
+                       ofs, store_w, minmax);
+    return check_hip(ctx, hipGetLastError(), "normalize");
 }
 
 int remap_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh,

@@ -11,6 +11,9 @@
 // With mvsv_stream_enable_samplepoints, SamplepointDetection's lattice values and
 // hits of every frame (trgt/demo.cpp:206-209,271-276 runs both detectors) are
 // computed next to the mean grid and come back with the frame (front_samples).
+// With mvsv_stream_enable_display, the 8-bit display map of every frame
+// (cv::normalize NORM_MINMAX, the last step of trgt/liveDisparity.cpp's loop) is
+// computed after them and comes back with the frame too (front_display).
 // With mvsv_stream_set_batch(b), pushed frames are computed b at a time: the
 // slots' device buffers are one contiguous [depth][frame] array, so a group of
 // consecutive slots is one frame-batch launch (sustained rate of the batch
@@ -28,6 +31,7 @@
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -194,7 +198,29 @@ struct mvsv_stream {
     float* sp_values(long i) const { return (float*)(hSp + (size_t)i * sp_slot_bytes); }
     int* sp_count(long i) const { return (int*)(sp_values(i) + sp_npts); }
     mvsv_sample_hit* sp_hits(long i) const { return (mvsv_sample_hit*)(sp_count(i) + 1); }
+    // the display map of disp_roi of every frame (mvsv_stream_enable_display): a
+    // dense u8 map and (smin, smax) per slot, on the device and in one pinned host block
+    bool disp = false;
+    mvsv_rect disp_roi{};
+    double disp_alpha = 0, disp_beta = 255;
+    uint8_t* dDisp = nullptr;    // [depth][rh][rw]
+    int16_t* dDispMM = nullptr;  // [depth][2]
+    uint8_t* hDisp = nullptr;    // pinned: [depth] x (map, min, max), disp_slot_bytes each
+    size_t disp_px = 0, disp_slot_bytes = 0;
+    uint8_t* disp_map(long i) const { return hDisp + (size_t)i * disp_slot_bytes; }
+    int16_t* disp_minmax(long i) const { return (int16_t*)(disp_map(i) + ((disp_px + 1) & ~(size_t)1)); }
 };
+
+static void display_free(mvsv_stream* st)
+{
+    if (st->dDisp) (void)hipFree(st->dDisp);
+    if (st->dDispMM) (void)hipFree(st->dDispMM);
+    if (st->hDisp) (void)hipHostFree(st->hDisp);
+    st->dDisp = nullptr;
+    st->dDispMM = nullptr;
+    st->hDisp = nullptr;
+    st->disp = false;
+}
 
 static void samplepoints_free(mvsv_stream* st)
 {
@@ -239,6 +265,7 @@ static void stream_free(mvsv_stream* st)
     if (st->dCropL) (void)hipFree(st->dCropL);
     if (st->dCropR) (void)hipFree(st->dCropR);
     samplepoints_free(st);
+    display_free(st);
     if (st->rep) (void)hipHostFree(st->rep);
     if (st->up) (void)hipStreamDestroy(st->up);
     if (st->down) (void)hipStreamDestroy(st->down);
@@ -466,6 +493,13 @@ static int stream_launch(mvsv_stream* st)
                 status = sample_detect_device(ctx, n, vals, rw, rh, st->sp_Q, st->sp_first, st->sp_second,
                                               st->sp_max, st->dSpCnt + i0, st->dSpHits + (size_t)i0 * st->sp_max);
         }
+        if (status == MVSV_OK && st->disp) {
+            const mvsv_rect& q = st->disp_roi;
+            const int rw = q.x1 - q.x0, rh = q.y1 - q.y0;
+            status = normalize_minmax_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, rw, rh,
+                                             st->disp_alpha, st->disp_beta, st->dDisp + (size_t)i0 * st->disp_px, rw,
+                                             st->disp_px, st->dDispMM + 2 * i0);
+        }
         if (status != MVSV_OK && ctx != st->ctx) st->ctx->err = ctx->err;  // reported by pop
         st->runs++;
         if ((rc = mark_last_use(ctx, MVSV_OK)) ||
@@ -501,6 +535,14 @@ static int stream_launch(mvsv_stream* st)
                                                       hipMemcpyDeviceToHost, st->down), "stream D2H")) ||
                     (rc = check_hip(c, hipMemcpyAsync(st->sp_hits(i), st->dSpHits + (size_t)i * st->sp_max,
                                                       (size_t)st->sp_max * sizeof(mvsv_sample_hit),
+                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")))
+                    return rc;
+            }
+            if (st->disp) {
+                const long i = i0 + k;
+                if ((rc = check_hip(c, hipMemcpyAsync(st->disp_map(i), st->dDisp + (size_t)i * st->disp_px, st->disp_px,
+                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")) ||
+                    (rc = check_hip(c, hipMemcpyAsync(st->disp_minmax(i), st->dDispMM + 2 * i, 2 * sizeof(int16_t),
                                                       hipMemcpyDeviceToHost, st->down), "stream D2H")))
                     return rc;
             }
@@ -819,6 +861,93 @@ int mvsv_stream_front_samples(mvsv_stream* st, float* values, int* count, mvsv_s
     if (hits)
         std::memcpy(hits, st->sp_hits(idx),
                     (size_t)std::min(std::min(total, st->sp_max), capacity) * sizeof(mvsv_sample_hit));
+    return MVSV_OK;
+}
+
+int mvsv_stream_disable_display(mvsv_stream* st)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (st->head != st->tail)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the display changes only while no frame is pending");
+    DeviceGuard dev_guard(st->ctx->device);
+    display_free(st);  // every frame was popped: nothing in flight uses the buffers
+    return MVSV_OK;
+}
+
+int mvsv_stream_enable_display(mvsv_stream* st, const mvsv_rect* roi, double alpha, double beta)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (!std::isfinite(alpha) || !std::isfinite(beta))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "display alpha / beta must be finite");
+    if (st->head != st->tail)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "the display changes only while no frame is pending");
+    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, st->W, st->H};
+    if (q.x0 < 0 || q.y0 < 0 || q.x1 > st->W || q.y1 > st->H || q.x1 <= q.x0 || q.y1 <= q.y0)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "display ROI empty or outside the image");
+    DeviceGuard dev_guard(ctx->device);
+    display_free(st);
+    st->disp_roi = q;
+    st->disp_alpha = alpha;
+    st->disp_beta = beta;
+    st->disp_px = (size_t)(q.x1 - q.x0) * (q.y1 - q.y0);
+    st->disp_slot_bytes = (((st->disp_px + 1) & ~(size_t)1) + 2 * sizeof(int16_t) + 15) & ~(size_t)15;
+    const size_t depth = st->slots.size();
+    const bool ok = hipMalloc((void**)&st->dDisp, depth * st->disp_px) == hipSuccess &&
+                    hipMalloc((void**)&st->dDispMM, depth * 2 * sizeof(int16_t)) == hipSuccess &&
+                    hipHostMalloc((void**)&st->hDisp, depth * st->disp_slot_bytes, hipHostMallocDefault) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        display_free(st);
+        return set_error(ctx, MVSV_E_OOM, "display buffer allocation failed");
+    }
+    st->disp = true;
+    return MVSV_OK;
+}
+
+// the oldest pending frame, complete: its slot index in *idx
+static int display_front(mvsv_stream* st, long* idx)
+{
+    mvsv_ctx* ctx = st->ctx;
+    if (!st->disp) return set_error(ctx, MVSV_E_INVALID_ARG, "the display is not enabled on this stream");
+    if (st->head == st->tail) return set_error(ctx, MVSV_E_INVALID_ARG, "stream empty");
+    *idx = st->tail % (long)st->slots.size();
+    auto& s = st->slots[*idx];
+    int rc;
+    if (st->tail >= st->launched && (rc = stream_launch(st))) return rc;  // partial group
+    if ((rc = check_hip(ctx, hipEventSynchronize(s.done), "stream sync"))) return rc;
+    if (s.status) return s.status;
+    // the report word is left for pop to read and clear
+    if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[*idx], __ATOMIC_ACQUIRE) != 0))
+        return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_display(mvsv_stream* st, uint8_t* out, size_t out_stride, int16_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    const int rw = st->disp_roi.x1 - st->disp_roi.x0, rh = st->disp_roi.y1 - st->disp_roi.y0;
+    if (st->disp && out && out_stride < (size_t)rw)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "display stride smaller than the ROI's width");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = display_front(st, &idx))) return rc;
+    if (out) copy_rows(out, out_stride, st->disp_map(idx), (size_t)rw, (size_t)rw, rh, 0, 1);
+    if (minmax) std::memcpy(minmax, st->disp_minmax(idx), 2 * sizeof(int16_t));
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_display_view(mvsv_stream* st, const uint8_t** map, int16_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (!map) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null map pointer");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = display_front(st, &idx))) return rc;
+    *map = st->disp_map(idx);
+    if (minmax) std::memcpy(minmax, st->disp_minmax(idx), 2 * sizeof(int16_t));
     return MVSV_OK;
 }
 

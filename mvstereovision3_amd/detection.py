@@ -632,6 +632,63 @@ class DisparityStream:
               self._ctx.handle)
         return values, count.value, hits[:min(count.value, cap)]
 
+    def enable_display(self, roi=None, alpha=0, beta=255):
+        """The 8-bit display map of every frame from now on:
+        cv::normalize(dMap(roi), out, alpha, beta, NORM_MINMAX, CV_8U), computed
+        after SGBM on the device (mvsv_stream_enable_display); only while no frame
+        is pending.  roi = (x0, y0, x1, y1), default the whole map."""
+        self._live()
+        self._display_views_gone("enable_display")
+        r = Rect(*(int(v) for v in roi)) if roi is not None else None
+        check(lib().mvsv_stream_enable_display(self._h, ctypes.byref(r) if r is not None else None,
+                                               float(alpha), float(beta)), self._ctx.handle)
+        self._disp_shape = (self.height, self.width) if r is None else (r.y1 - r.y0, r.x1 - r.x0)
+
+    def disable_display(self):
+        self._live()
+        self._display_views_gone("disable_display")
+        check(lib().mvsv_stream_disable_display(self._h), self._ctx.handle)
+        self._disp_shape = None
+
+    def _display_views_gone(self, what):
+        # the pinned display slots are reallocated: no view may point into them
+        with self._views_lock:
+            if getattr(self, "_disp_views", 0) > 0:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: a front_display view is still alive")
+
+    def front_display(self, copy=True):
+        """(map, (smin, smax)) of the oldest pending frame, which stays pending (pop
+        it afterwards): the uint8 display map of the enabled roi and the min / max
+        it was normalised with.  copy="view": a read-only view of the map in the
+        stream's pinned host slot, valid until the next push."""
+        self._live()
+        shape = getattr(self, "_disp_shape", None) or (0, 0)
+        mm = np.zeros(2, np.int16)
+        if copy == "view":
+            ptr = ctypes.c_void_p()
+            check(lib().mvsv_stream_front_display_view(self._h, ctypes.byref(ptr), mm.ctypes.data),
+                  self._ctx.handle)
+            buf = (ctypes.c_uint8 * (shape[0] * shape[1])).from_address(ptr.value)
+            buf._owner = self
+            with self._views_lock:
+                self._live_views += 1
+                self._disp_views = getattr(self, "_disp_views", 0) + 1
+            fin = weakref.finalize(buf, DisparityStream._display_view_released, self)
+            fin.atexit = False
+            view = np.ctypeslib.as_array(buf).reshape(shape)
+            view.flags.writeable = False
+            return view, (int(mm[0]), int(mm[1]))
+        out = np.empty(shape, np.uint8)
+        check(lib().mvsv_stream_front_display(self._h, out.ctypes.data if out.size else None, shape[1],
+                                              mm.ctypes.data), self._ctx.handle)
+        return out, (int(mm[0]), int(mm[1]))
+
+    @staticmethod
+    def _display_view_released(stream):
+        with stream._views_lock:
+            stream._disp_views -= 1
+        DisparityStream._view_released(stream)
+
     @staticmethod
     def _view_released(stream):
         with stream._views_lock:

@@ -89,7 +89,13 @@ class Utility:
 
     @staticmethod
     def calcMinMaxDisparity(matrix):
-        """src/utility.cpp:286-303: min / max of the positive values."""
+        """src/utility.cpp:286-303: min / max of the positive values.  An int16
+        device tensor is reduced on the GPU (mvsv_minmax_device)."""
+        if _is_device_map(matrix):
+            lo, hi = (int(x) for x in minmax(matrix, positive_only=True).cpu())
+            if lo > hi:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "calcMinMaxDisparity: no positive value")
+            return lo, hi
         m = np.asarray(matrix)
         v = m[m > 0]
         if v.size == 0:
@@ -120,6 +126,95 @@ def reproject(dmap, Q):
     check(lib().mvsv_reproject_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
                                       q.ctypes.data, out.data_ptr(), W, H * W), ctx.handle)
     return out if batched else out[0]
+
+
+def _is_device_map(d) -> bool:
+    if not type(d).__module__.startswith("torch"):
+        return False
+    import torch
+    return d.is_cuda and d.dtype == torch.int16 and d.dim() in (2, 3)
+
+
+def _device_frames(dmap, what):
+    """(frames view (N, H, W) with unit column stride, batched, context) of an int16 device map."""
+    import torch
+    if not _is_device_map(dmap):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: 2-D or 3-D int16 device tensor expected")
+    batched = dmap.dim() == 3
+    d = dmap if batched else dmap.unsqueeze(0)
+    if d.stride(2) != 1:
+        d = d.contiguous()
+    ctx = context(dmap.device.index or 0)
+    check(lib().mvsv_set_stream(ctx.handle,
+                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
+          ctx.handle)
+    return d, batched, ctx
+
+
+def minmax(dmap, positive_only=False):
+    """(min, max) of every frame of an int16 device map (any view with unit column
+    stride), on the GPU: int16 tensor (2,) or (N, 2).  positive_only: over the
+    values > 0 (Utility::calcMinMaxDisparity), (32767, -32768) where there is none."""
+    import torch
+    d, batched, ctx = _device_frames(dmap, "minmax")
+    n, H, W = d.shape
+    out = torch.empty((n, 2), dtype=torch.int16, device=dmap.device)
+    check(lib().mvsv_minmax_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
+                                   1 if positive_only else 0, out.data_ptr()), ctx.handle)
+    return out if batched else out[0]
+
+
+def normalize_minmax(dmap, alpha=0, beta=255, out=None, return_minmax=False):
+    """cv::normalize(dmap, out, alpha, beta, NORM_MINMAX, CV_8U) in OpenCV 3.4's
+    arithmetic, on the GPU: the display map of the reference's loops
+    (trgt/liveDisparity.cpp:92).
+
+    dmap: int16, (H, W) or a batch (N, H, W) whose frames are normalised each with
+    its own min / max.  A torch device tensor (any view with unit column stride)
+    gives a uint8 device tensor, asynchronously on the current stream; a numpy
+    array gives a numpy array.  out: a uint8 tensor / array of the same shape to
+    write into (device tensors: any view with unit column stride).
+    return_minmax: also return the (smin, smax) int16 pairs, (2,) or (N, 2)."""
+    if type(dmap).__module__.startswith("torch") and dmap.is_cuda:
+        import torch
+        d, batched, ctx = _device_frames(dmap, "normalize_minmax")
+        n, H, W = d.shape
+        if out is None:
+            out = torch.empty(tuple(dmap.shape), dtype=torch.uint8, device=dmap.device)
+        elif not (type(out).__module__.startswith("torch") and out.is_cuda and out.dtype == torch.uint8 and
+                  out.shape == dmap.shape and out.stride(-1) == 1):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG,
+                            "normalize_minmax: out must be a uint8 device tensor of dmap's shape, unit column stride")
+        o = out if batched else out.unsqueeze(0)
+        mm = torch.empty((n, 2), dtype=torch.int16, device=dmap.device) if return_minmax else None
+        check(lib().mvsv_normalize_minmax_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
+                                                 float(alpha), float(beta), o.data_ptr(), o.stride(1), o.stride(0),
+                                                 mm.data_ptr() if return_minmax else None), ctx.handle)
+        if return_minmax:
+            return out, (mm if batched else mm[0])
+        return out
+    d = np.asarray(dmap)
+    if d.ndim not in (2, 3) or d.dtype != np.int16:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "normalize_minmax: 2-D or 3-D int16 map expected")
+    if d.strides[-1] != 2:
+        d = np.ascontiguousarray(d)
+    if out is None:
+        out = np.empty(d.shape, np.uint8)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.shape == d.shape and out.strides[-1] == 1):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG,
+                        "normalize_minmax: out must be a uint8 array of dmap's shape, unit column stride")
+    frames = d if d.ndim == 3 else d[None]
+    outs = out if d.ndim == 3 else out[None]
+    mm = np.empty((len(frames), 2), np.int16)
+    ctx = context(0)
+    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    for f, o, m in zip(frames, outs, mm):
+        check(lib().mvsv_normalize_minmax(ctx.handle, f.ctypes.data, f.strides[0] // 2, f.shape[1], f.shape[0],
+                                          float(alpha), float(beta), o.ctypes.data, o.strides[0], m.ctypes.data),
+              ctx.handle)
+    if return_minmax:
+        return out, (mm if d.ndim == 3 else mm[0])
+    return out
 
 
 class ply:  # noqa: N801 - reference name (inc/ply.h)
