@@ -56,6 +56,11 @@
  *   mvsv_write_ply                    ply::write src/ply.cpp:37-133 (MODE PLAIN,
  *                                     WITH_COLOR, WITH_COLOR_SHADING)
  *   mvsv_dmap2pcl                     Utility::dmap2pcl src/utility.cpp:242-262
+ *   mvsv_point_cloud(_device)         the loop of Utility::dmap2pcl src/utility.cpp:248-259
+ *                                     (pixels with v > 0 in raster order) with the grey
+ *                                     of ply::write src/ply.cpp:90, compacted on the device
+ *   mvsv_stream_enable_cloud /        the point cloud with every frame of a stream (the
+ *   _front_cloud(_device)             dmap2pcl call of trgt/demo.cpp:394 and the other loops)
  *
  * Conventions
  *   - Plain C types only; no exceptions cross this boundary.
@@ -316,6 +321,39 @@ MVSV_API int mvsv_samplepoint_detect_device(mvsv_ctx* ctx, int n, const float* v
                                             float range_second, int max_hits, int* counts,
                                             mvsv_sample_hit* hits);
 
+/* ---- point clouds: the valid pixels of a disparity map, compacted in raster order ----
+ * Utility::dmap2pcl's loop (src/utility.cpp:248-259) keeps the pixels with v > 0,
+ * row by row, and ply::write greys them (src/ply.cpp:90).  A record is that point:
+ *   x, y, z   mvsv_calc_coordinate(col, row, v) bit for bit, col / row relative to
+ *             the view
+ *   grey      int((z - (float)mn) / (float)(mx - mn) * 255.0) with mn / mx the frame's
+ *             min / max over v > 0: float difference and quotient, double product,
+ *             truncation -- what mvsv_write_ply prints in MVSV_PLY_WITH_COLOR mode.
+ *             Not clamped to 0..255 (z is in millimetres; the reference does not
+ *             clamp either).  INT32_MIN where the double is NaN or outside int32,
+ *             notably for every point of a frame with mx == mn.
+ * Record k of frame f is its k-th valid pixel in raster order, at
+ * records[f * capacity + k]; positions come from a prefix sum, so two runs give the
+ * same bytes.  At most capacity records per frame are written and nothing behind
+ * them; counts[f] is the number of valid pixels even where it exceeds capacity;
+ * minmax[2 f] = (mn, mx), or (32767, -32768) for a frame without a positive value
+ * (count 0, nothing written).
+ *
+ * dmap as for mvsv_normalize_minmax_device (any 2-byte-aligned view, packed loads
+ * where the strides allow); records 16-byte aligned; width * height < 2^31; all
+ * device pointers, asynchronous on the context's stream; minmax may be NULL. */
+typedef struct {
+    float x, y, z;
+    int32_t grey;
+} mvsv_cloud_point;
+MVSV_API int mvsv_point_cloud_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t stride, size_t frame_stride,
+                                     int width, int height, const float* Q, mvsv_cloud_point* records, int capacity,
+                                     int* counts, int32_t* minmax);
+/* Same for one host map into host records (synchronous): *count and minmax[2] (may
+ * be NULL) are read back first, then only min(*count, capacity) records. */
+MVSV_API int mvsv_point_cloud(mvsv_ctx* ctx, const int16_t* dmap, size_t stride, int width, int height,
+                              const float* Q, mvsv_cloud_point* records, int capacity, int* count, int32_t* minmax);
+
 /* ---- display maps: cv::normalize(NORM_MINMAX, CV_8U) of a disparity map ---------
  * OpenCV 3.4's arithmetic (normalize -> Mat::convertTo, CV_16S -> CV_8U, no mask;
  * its SSE2 / scalar form, where product and sum round separately):
@@ -474,6 +512,32 @@ MVSV_API int mvsv_stream_front_display(mvsv_stream* s, uint8_t* out, size_t out_
  * width) in the stream's pinned slot, valid until the next push. */
 MVSV_API int mvsv_stream_front_display_view(mvsv_stream* s, const uint8_t** map, int16_t* minmax);
 
+/* The point cloud in the stream (either kind): every frame's
+ * mvsv_point_cloud_device of dMap(roi) is computed after its SGBM on the same
+ * device stream -- what Utility::dmap2pcl("pointcloud.ply", dMapRaw, Q_32F) makes of
+ * a frame (trgt/demo.cpp:394).  roi: NULL for the whole map; it must lie inside the
+ * stream's frame, and x / y count from its corner, as for dMapRaw(roi).
+ * max_points <= 0: room for every pixel of the roi.  The records stay on the device,
+ * in a ring of depth x max_points; only (count, min, max) come back with the frame.
+ * Allowed only while no frame is pending (MVSV_E_INVALID_ARG otherwise); a second
+ * call replaces the first.  A stream that never enables it enqueues and allocates
+ * nothing extra. */
+MVSV_API int mvsv_stream_enable_cloud(mvsv_stream* s, const mvsv_rect* roi, const float* Q, int max_points);
+MVSV_API int mvsv_stream_disable_cloud(mvsv_stream* s);
+/* Waits for the oldest pending frame and copies the first min(count, max_points,
+ * capacity) records from the device, *count = the number of pixels with v > 0 (it
+ * may exceed both), minmax[2] = (min, max) over them, without popping the frame, so
+ * it composes with pop, pop_view, pop_pair, front_samples and front_display.  Every
+ * output may be NULL.  MVSV_E_INVALID_ARG when the cloud is not enabled or no frame
+ * is pending; the frame's own error when its launch failed (as pop reports it). */
+MVSV_API int mvsv_stream_front_cloud(mvsv_stream* s, mvsv_cloud_point* records, int capacity, int* count,
+                                     int32_t* minmax);
+/* Same without the copy: *records_dev is the device pointer of the frame's slot
+ * (max_points records, the first min(count, max_points) written), valid until the
+ * frame is popped -- for consumers that stay on the GPU. */
+MVSV_API int mvsv_stream_front_cloud_device(mvsv_stream* s, const mvsv_cloud_point** records_dev, int* count,
+                                            int32_t* minmax);
+
 /* ---- before the path: rectification ---------------------------
  * cv::remap(src, dst, map_x, map_y, INTER_LINEAR) with BORDER_CONSTANT 0 for CV_8UC1
  * images and CV_32FC1 maps, in OpenCV 3.4's fixed-point arithmetic (INTER_BITS 5,
@@ -618,8 +682,9 @@ MVSV_API int mvsv_write_ply(const char* path, const char* author, const char* ob
                             const int16_t* dmap, size_t dmap_stride, int width, int height);
 
 /* Utility::dmap2pcl: every pixel of the host int16 map with v > 0 reprojected
- * (on the device of ctx) and written as "Hagen Hiller" / "disparity pointcloud"
- * PLY in MODE WITH_COLOR, raster order. */
+ * (on the device of ctx, mvsv_point_cloud_device: only the valid points come back)
+ * and written as "Hagen Hiller" / "disparity pointcloud" PLY in MODE WITH_COLOR,
+ * raster order. */
 MVSV_API int mvsv_dmap2pcl(mvsv_ctx* ctx, const char* path, const int16_t* dmap, size_t stride,
                            int width, int height, const float* Q);
 

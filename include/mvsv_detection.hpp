@@ -97,6 +97,25 @@ inline void normalize(const Mat& dMap, Mat& out, double alpha = 0, double beta =
                                 alpha, beta, out.data, out.step, minmax),
           c);
 }
+// the loop of dmap2pcl without the file: the pixels with v > 0 of dMap in raster
+// order as (x, y, z, grey) records, compacted on the device (mvsv_point_cloud).
+// max_points <= 0: every valid pixel.  Returns the number of valid pixels, which may
+// exceed max_points; out holds the first min(count, max_points).  minmax: where
+// given, the (min, max) over the valid values.
+inline int pointCloud(const Mat& dMap, const QMatrix& Q, std::vector<mvsv_cloud_point>& out, int max_points = 0,
+                      int32_t* minmax = nullptr)
+{
+    if (dMap.type != MAT_16SC1 || dMap.empty()) throw Error(MVSV_E_INVALID_ARG, "pointCloud: CV_16S map expected");
+    const size_t px = (size_t)dMap.rows * dMap.cols;
+    out.resize(max_points <= 0 ? px : std::min((size_t)max_points, px));
+    int count = 0;
+    mvsv_ctx* c = thread_context();
+    check(mvsv_point_cloud(c, reinterpret_cast<const int16_t*>(dMap.data), dMap.step / 2, dMap.cols, dMap.rows,
+                           Q.data(), out.data(), (int)out.size(), &count, minmax),
+          c);
+    out.resize(std::min((size_t)std::max(count, 0), out.size()));
+    return count;
+}
 
 }  // namespace Utility
 
@@ -472,6 +491,28 @@ inline void stream_front_display(mvsv_ctx* ctx, mvsv_stream* s, const DisplaySiz
     check(mvsv_stream_front_display(s, d.rows > 0 ? out.data : nullptr, out.step, minmax), ctx);
 }
 
+// the point cloud calls shared by DisparityStream and RawDisparityStream: the
+// records kept per frame are what a stream class remembers
+inline int stream_enable_cloud(mvsv_ctx* ctx, mvsv_stream* s, int width, int height, const QMatrix& Q, const Rect* roi,
+                               int max_points)
+{
+    mvsv_rect r{0, 0, width, height};
+    if (roi) r = {roi->x, roi->y, roi->x + roi->width, roi->y + roi->height};
+    check(mvsv_stream_enable_cloud(s, &r, Q.data(), max_points), ctx);
+    const long px = (long)(r.x1 - r.x0) * (r.y1 - r.y0);
+    return (int)(max_points <= 0 ? px : std::min((long)max_points, px));
+}
+// the header first (the frame is waited for there), then the records that exist
+inline int stream_front_cloud(mvsv_ctx* ctx, mvsv_stream* s, int cap, std::vector<mvsv_cloud_point>& out,
+                              int32_t* minmax)
+{
+    int count = 0;
+    check(mvsv_stream_front_cloud(s, nullptr, 0, &count, minmax), ctx);
+    out.resize((size_t)std::max(0, std::min(count, cap)));
+    if (!out.empty()) check(mvsv_stream_front_cloud(s, out.data(), (int)out.size(), nullptr, nullptr), ctx);
+    return count;
+}
+
 // Camera loop without the worker thread: push rectified pairs, pop maps (and the
 // 9x9 means of the work ROI) in order; up to `depth` frames in flight.
 class DisparityStream {
@@ -546,6 +587,31 @@ public:
         check(mvsv_stream_front_display_view(s_, &map, minmax), ctx_);
         return map;
     }
+    // the point cloud (Utility::pointCloud of dMap(roi)) with every frame pushed from
+    // now on (no frame may be pending); default roi: the whole map, max_points <= 0:
+    // room for every pixel of the roi.  The records stay on the device until asked for.
+    void enableCloud(const QMatrix& Q, const Rect* roi = nullptr, int max_points = 0)
+    {
+        cloud_ = stream_enable_cloud(ctx_, s_, w_, h_, Q, roi, max_points);
+    }
+    void disableCloud()
+    {
+        check(mvsv_stream_disable_cloud(s_), ctx_);
+        cloud_ = 0;
+    }
+    // the oldest pending frame's records (the first min(count, max_points)); returns
+    // the count of valid pixels; the frame stays pending
+    int frontCloud(std::vector<mvsv_cloud_point>& out, int32_t* minmax = nullptr)
+    {
+        return stream_front_cloud(ctx_, s_, cloud_, out, minmax);
+    }
+    // the same records on the device (the frame's slot of the ring), valid until the frame is popped
+    const mvsv_cloud_point* frontCloudDevice(int* count, int32_t* minmax = nullptr)
+    {
+        const mvsv_cloud_point* p = nullptr;
+        check(mvsv_stream_front_cloud_device(s_, &p, count, minmax), ctx_);
+        return p;
+    }
 
 private:
     mvsv_ctx* ctx_;
@@ -553,6 +619,7 @@ private:
     int w_, h_;
     SampleLayout lattice_;
     DisplaySize display_;
+    int cloud_ = 0;
 };
 
 }  // namespace mvsv

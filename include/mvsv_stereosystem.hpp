@@ -386,6 +386,20 @@ public:
     {
         stream_front_display(mCtx, mStream, mDisplay, out, minmax);
     }
+    // the point cloud on every frame, as on DisparityStream
+    void enableCloud(const QMatrix& Q, const Rect* roi = nullptr, int max_points = 0)
+    {
+        mCloud = stream_enable_cloud(mCtx, mStream, mW, mH, Q, roi, max_points);
+    }
+    void disableCloud()
+    {
+        check(mvsv_stream_disable_cloud(mStream), mCtx);
+        mCloud = 0;
+    }
+    int frontCloud(std::vector<mvsv_cloud_point>& out, int32_t* minmax = nullptr)
+    {
+        return stream_front_cloud(mCtx, mStream, mCloud, out, minmax);
+    }
 
 private:
     mvsv_ctx* mCtx = nullptr;
@@ -393,6 +407,7 @@ private:
     int mRawW, mRawH, mW = 0, mH = 0;
     SampleLayout mLattice;
     DisplaySize mDisplay;
+    int mCloud = 0;
     bool mKeep;
 };
 

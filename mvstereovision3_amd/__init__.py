@@ -16,7 +16,7 @@ from .detection import (DisparityStream, MeanDisparityDetection, Samplepoint, Sa
                         create_dmap_rois)
 from .calibration import Stereosystem, read_matrix, stereo_rectify, write_matrices
 from .rectify import convert_maps, init_undistort_rectify_map, rectify_pair, remap
-from .utility import Utility, dMapValues, minmax, normalize_minmax, ply, reproject
+from .utility import CLOUD_DTYPE, Utility, dMapValues, minmax, normalize_minmax, ply, point_cloud, reproject
 
 __all__ = [
     "Disparity", "StereoBM", "StereoSGBM", "Stereopair", "sgbmParameters", "MvsvError",
@@ -28,6 +28,6 @@ __all__ = [
     "stereo_rectify", "convert_maps", "MVSV_E_TIMEOUT", "OPT_STRIP_SPIN_LIMIT", "OPT_STRIP_WAVES", "OPT_BM_TILE_ROWS",
     "OPT_PATH_SCHEDULE", "OPT_BITSLICE", "Samplepoint", "SamplepointDetection", "samplepoint_layout",
     "samplepoint_values", "samplepoint_detect", "SAMPLE_HIT_DTYPE",
-    "normalize_minmax", "minmax",
+    "normalize_minmax", "minmax", "point_cloud", "CLOUD_DTYPE",
 ]
 __version__ = "1.0.0"

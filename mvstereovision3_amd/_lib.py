@@ -168,6 +168,12 @@ def _declare(lib, strict=True):
         "mvsv_stream_disable_display": ([P], I),
         "mvsv_stream_front_display": ([P, P, Z, P], I),
         "mvsv_stream_front_display_view": ([P, ctypes.POINTER(P), P], I),
+        "mvsv_point_cloud_device": ([P, I, P, Z, Z, I, I, P, P, I, P, P], I),
+        "mvsv_point_cloud": ([P, P, Z, I, I, P, P, I, ctypes.POINTER(I), P], I),
+        "mvsv_stream_enable_cloud": ([P, P, P, I], I),
+        "mvsv_stream_disable_cloud": ([P], I),
+        "mvsv_stream_front_cloud": ([P, P, I, ctypes.POINTER(I), P], I),
+        "mvsv_stream_front_cloud_device": ([P, ctypes.POINTER(P), ctypes.POINTER(I), P], I),
         "mvsv_convert_maps": ([P, P, Z, I, I, P, Z, P, Z], I),
         "mvsv_remap_device": ([P, I, P, Z, Z, I, I, P, P, Z, P, Z, Z, I, I], I),
         "mvsv_rectify_pair": ([P, P, Z, P, Z, I, I, P, P, P, Z, P, Z], I),

@@ -406,7 +406,7 @@ int mvsv_trim(mvsv_ctx* ctx)
                      &ctx->uf_tile, &ctx->tri_bnd, &ctx->bs_bnd, &ctx->status,
                      &ctx->dummy, &ctx->keys,
                      &ctx->bm_lf, &ctx->bm_rf, &ctx->bm_cost, &ctx->bm_sad, &ctx->h_left, &ctx->h_right,
-                     &ctx->h_out, &ctx->mm_part};
+                     &ctx->h_out, &ctx->mm_part, &ctx->cl_rows};
     for (DevBuf* b : all) free_buf(*b);
     return MVSV_OK;
 }
@@ -877,39 +877,88 @@ int mvsv_reproject_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, 
     return mark_last_use(ctx, reproject_device(ctx, n, dmap, st, fs, W, H, Q, xyzw, xs, xfs));
 }
 
+int mvsv_point_cloud_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
+                            const float* Q, mvsv_cloud_point* records, int capacity, int* counts, int32_t* minmax)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0 || !dmap || !Q || !records || !counts || W <= 0 || H <= 0 || st < (size_t)W || capacity < 1 ||
+        (size_t)W * H > (size_t)INT32_MAX || ((uintptr_t)records & 15) != 0)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad point cloud arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, point_cloud_device(ctx, n, dmap, st, fs, W, H, Q, records, capacity, counts, 1, minmax, 2));
+}
+
+// One host map through the device: the map staged with rows a multiple of 8
+// elements apart (the packed path for any width), a (count, min, max) header behind
+// it; the header comes back first, then the records that exist.  *dev_records: the
+// staged records (up to capacity of them), *hdr: the header on the host.
+static int host_cloud(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, const float* Q, int capacity,
+                      int hdr[3], const mvsv_cloud_point** dev_records)
+{
+    const size_t ws = ((size_t)W + 7) & ~(size_t)7, px = ws * H;
+    const int cap = (int)std::min((size_t)capacity, (size_t)W * H);
+    int rc;
+    if ((rc = ensure(ctx, ctx->h_out, px * 2 + 3 * sizeof(int), "dmap staging"))) return rc;
+    if ((rc = ensure(ctx, ctx->h_left, (size_t)cap * sizeof(mvsv_cloud_point), "point staging"))) return rc;
+    int16_t* d = (int16_t*)ctx->h_out.ptr;
+    int* dh = (int*)(d + px);  // px * 2 is a multiple of 16
+    hipStream_t s = ctx->stream;
+    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, ws * 2, dmap, st * 2, (size_t)W * 2, H, hipMemcpyHostToDevice, s),
+                        "H2D dmap")) ||
+        (rc = point_cloud_device(ctx, 1, d, ws, px, W, H, Q, (mvsv_cloud_point*)ctx->h_left.ptr, cap, dh, 3, dh + 1,
+                                 3)) ||
+        (rc = check_hip(ctx, hipMemcpyAsync(hdr, dh, 3 * sizeof(int), hipMemcpyDeviceToHost, s), "D2H cloud header")) ||
+        (rc = check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize")))
+        return rc;
+    *dev_records = (const mvsv_cloud_point*)ctx->h_left.ptr;
+    return MVSV_OK;
+}
+
+int mvsv_point_cloud(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, const float* Q,
+                     mvsv_cloud_point* records, int capacity, int* count, int32_t* minmax)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (!dmap || !Q || !records || !count || W <= 0 || H <= 0 || st < (size_t)W || capacity < 1 ||
+        (size_t)W * H > (size_t)INT32_MAX)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad point cloud arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, [&]() -> int {  // every exit after an enqueue
+    int rc, hdr[3];
+    const mvsv_cloud_point* dev = nullptr;
+    if ((rc = host_cloud(ctx, dmap, st, W, H, Q, capacity, hdr, &dev))) return rc;
+    *count = hdr[0];
+    if (minmax) {
+        minmax[0] = hdr[1];
+        minmax[1] = hdr[2];
+    }
+    const size_t k = (size_t)std::min(hdr[0], capacity);
+    if (k == 0) return MVSV_OK;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(records, dev, k * sizeof(mvsv_cloud_point), hipMemcpyDeviceToHost,
+                                            ctx->stream), "D2H points")))
+        return rc;
+    return check_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }());
+}
+
 // [Utility::dmap2pcl] src/utility.cpp:242-262
 int mvsv_dmap2pcl(mvsv_ctx* ctx, const char* path, const int16_t* dmap, size_t st, int W, int H,
                   const float* Q)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
-    if (!path || !dmap || !Q || W <= 0 || H <= 0 || st < (size_t)W)
+    if (!path || !dmap || !Q || W <= 0 || H <= 0 || st < (size_t)W || (size_t)W * H > (size_t)INT32_MAX)
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad dmap2pcl arguments");
     DeviceGuard dev_guard(ctx->device);
     return mark_last_use(ctx, [&]() -> int {
-    const size_t px = (size_t)W * H;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_out, px * 2, "dmap staging"))) return rc;
-    if ((rc = ensure(ctx, ctx->h_left, px * 16, "point staging"))) return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_out.ptr, (size_t)W * 2, dmap, st * 2,
-                                              (size_t)W * 2, H, hipMemcpyHostToDevice, s),
-                        "H2D dmap")))
+    int rc, hdr[3];
+    const mvsv_cloud_point* dev = nullptr;
+    if ((rc = host_cloud(ctx, dmap, st, W, H, Q, INT32_MAX, hdr, &dev))) return rc;
+    // the records are (x, y, z, grey): vertices 4 floats apart; the writer prints its own grey
+    const size_t k = (size_t)hdr[0];
+    std::vector<float> pts(k * 4);
+    if (k && ((rc = check_hip(ctx, hipMemcpyAsync(pts.data(), dev, k * sizeof(mvsv_cloud_point),
+                                                  hipMemcpyDeviceToHost, ctx->stream), "D2H points")) ||
+              (rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))))
         return rc;
-    if ((rc = reproject_device(ctx, 1, (const int16_t*)ctx->h_out.ptr, W, px, W, H, Q,
-                               (float*)ctx->h_left.ptr, W, px)))
-        return rc;
-    std::vector<float> pts(px * 4);
-    if ((rc = check_hip(ctx, hipMemcpyAsync(pts.data(), ctx->h_left.ptr, px * 16,
-                                            hipMemcpyDeviceToHost, s),
-                        "D2H points")) ||
-        (rc = check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize")))
-        return rc;
-    size_t k = 0;
-    for (size_t i = 0; i < px; i++)  // raster order, v > 0 (flag in the 4th float)
-        if (pts[4 * i + 3] != 0.0f) {
-            for (int j = 0; j < 4; j++) pts[4 * k + j] = pts[4 * i + j];
-            k++;
-        }
     rc = mvsv_write_ply(path, "Hagen Hiller", "disparity pointcloud", pts.data(), k, 4,
                         MVSV_PLY_WITH_COLOR, dmap, st, W, H);
     if (rc == MVSV_E_IO) return set_error(ctx, rc, std::string("cannot write ") + path);

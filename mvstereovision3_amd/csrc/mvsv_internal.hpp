@@ -161,6 +161,8 @@ struct mvsv_ctx {
     mvsv::DevBuf h_left, h_right, h_out;
     // display maps: one (min, max) pair per block of minmax_kernel, [n][blocks][2] ints
     mvsv::DevBuf mm_part;
+    // point clouds: (min, max) per frame, then (first record, min | max) per row, int pairs
+    mvsv::DevBuf cl_rows;
     // stage profiling (HIP events on the context stream)
     int prof = 0;
     struct Mark {
@@ -285,5 +287,11 @@ int minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t f
                   int16_t* minmax);
 int normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
                             double alpha, double beta, uint8_t* out, size_t os, size_t ofs, int16_t* minmax);
+// Point clouds (mvsv_post.hip): the records of the pixels with v > 0 of every frame
+// in raster order, frame f into records[f * capacity ..]; counts[f * cs] = the
+// number of such pixels, minmax[f * ms], [f * ms + 1] = their (min, max) where
+// minmax is not null.
+int point_cloud_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H, const float* Q,
+                       mvsv_cloud_point* records, int capacity, int* counts, size_t cs, int* minmax, size_t ms);
 
 }  // namespace mvsv

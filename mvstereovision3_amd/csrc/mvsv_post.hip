@@ -12,6 +12,9 @@
 //     5x5 patches, range test + ordered compaction + calcCoordinate of the hits)
 //   * display maps                  (cv::normalize(dMap, out, 0, 255, NORM_MINMAX,
 //     CV_8U) of the reference's loops; min / max of Utility::calcMinMaxDisparity)
+//   * point clouds                  (the loop of Utility::dmap2pcl, src/utility.cpp:248-259,
+//     as an ordered compaction: the pixels with v > 0 in raster order, with
+//     ply::write's grey)
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -966,6 +969,182 @@ __global__ __launch_bounds__(256) void normalize_u8_kernel(const int16_t* __rest
     }
 }
 
+// ---- point clouds: Utility::dmap2pcl's loop (src/utility.cpp:248-259) as an ordered compaction ----
+// The records of a frame are its pixels with v > 0 in raster order: (x, y, z) of
+// calc_coordinate_dev and the grey ply::write prints in WITH_COLOR mode
+// (src/ply.cpp:90).  Three launches, no block waits on another and no atomics, so
+// a record's position never depends on timing:
+//   cloud_rows_kernel     a wave per row: (count, min, max over v > 0) of the row,
+//                         written unconditionally
+//   cloud_scan_kernel     a block per frame: the counts become the rows' first
+//                         record positions (exclusive scan, in chunks of the block's
+//                         width), min / max are folded, the frame's count is written
+//   cloud_scatter_kernel  a wave per row again: a pixel's position is its row's
+//                         first + the valid pixels of earlier steps of the walk +
+//                         those of lower lanes / elements of this step (ballots)
+// Rows are walked head | packed 16-byte groups | tail as in minmax_kernel; every
+// loop bound is wave-uniform, so every ballot sees the whole wave.
+constexpr int kCloudScan = 256;                      // rows per step of cloud_scan_kernel
+constexpr int kCloudNone = (int)0x80007fffu;         // packed (min, max) identities (32767, -32768)
+
+__device__ __forceinline__ int lanes_below(unsigned long long m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
+
+__global__ __launch_bounds__(256) void cloud_rows_kernel(const int16_t* __restrict__ dmap, size_t st, size_t fs, int W,
+                                                         int H, int head, int nvec, int2* __restrict__ rows)
+{
+    const int lane = threadIdx.x & 63, f = blockIdx.y;
+    const int y = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (y >= H) return;  // whole waves
+    const int16_t* r = dmap + f * fs + (size_t)y * st;
+    int cnt = 0, lo = 32767, hi = -32768;
+    auto take = [&](int v) {
+        const bool ok = v > 0;
+        cnt += __popcll(__ballot(ok));
+        if (ok) {
+            lo = min(lo, v);
+            hi = max(hi, v);
+        }
+    };
+    for (int x0 = 0; x0 < head; x0 += 64) take(x0 + lane < head ? r[x0 + lane] : 0);
+    const uint4* rv = (const uint4*)(r + head);
+    for (int j0 = 0; j0 < nvec; j0 += 64) {
+        const uint4 q = j0 + lane < nvec ? rv[j0 + lane] : make_uint4(0u, 0u, 0u, 0u);
+        take(lo16(q.x)); take(hi16(q.x)); take(lo16(q.y)); take(hi16(q.y));
+        take(lo16(q.z)); take(hi16(q.z)); take(lo16(q.w)); take(hi16(q.w));
+    }
+    for (int x0 = head + nvec * 8; x0 < W; x0 += 64) take(x0 + lane < W ? r[x0 + lane] : 0);
+    lo = wave_min_i32(lo);
+    hi = wave_max_i32(hi);
+    if (lane == 0) rows[(size_t)f * H + y] = make_int2(cnt, (int)((uint32_t)(lo & 0xffff) | (uint32_t)hi << 16));
+}
+
+// frames[f] = (min, max); counts / minmax are the caller's (element strides cs, ms; minmax may be null)
+__global__ __launch_bounds__(kCloudScan) void cloud_scan_kernel(int2* __restrict__ rows, int H, int2* __restrict__ frames,
+                                                                int* __restrict__ counts, size_t cs,
+                                                                int* __restrict__ minmax, size_t ms)
+{
+    constexpr int kWaves = kCloudScan / 64;
+    __shared__ int s_cnt[kWaves], s_lo[kWaves], s_hi[kWaves];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, f = blockIdx.x;
+    int2* r = rows + (size_t)f * H;
+    int base = 0, lo = 32767, hi = -32768;
+    for (int i0 = 0; i0 < H; i0 += kCloudScan) {
+        const int i = i0 + threadIdx.x;
+        const int2 t = i < H ? r[i] : make_int2(0, kCloudNone);
+        lo = min(lo, lo16((uint32_t)t.y));
+        hi = max(hi, hi16((uint32_t)t.y));
+        int inc = t.x;  // inclusive scan over the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int u = __shfl_up(inc, o);
+            if (lane >= o) inc += u;
+        }
+        if (lane == 63) s_cnt[w] = inc;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < kWaves; k++) {
+            const int c = s_cnt[k];
+            before += k < w ? c : 0;
+            total += c;
+        }
+        if (i < H) r[i].x = base + before + inc - t.x;
+        base += total;
+        __syncthreads();  // s_cnt is rewritten by the next chunk
+    }
+    lo = wave_min_i32(lo);
+    hi = wave_max_i32(hi);
+    if (lane == 0) {
+        s_lo[w] = lo;
+        s_hi[w] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 1; k < kWaves; k++) {
+            lo = min(lo, s_lo[k]);
+            hi = max(hi, s_hi[k]);
+        }
+        frames[f] = make_int2(lo, hi);
+        counts[(size_t)f * cs] = base;
+        if (minmax) {
+            minmax[(size_t)f * ms] = lo;
+            minmax[(size_t)f * ms + 1] = hi;
+        }
+    }
+}
+
+// int((z - mn) / (mx - mn) * 255.0) as the host writer computes it: a float
+// difference and a correctly rounded float quotient, a double product, truncation;
+// INT32_MIN where the double is NaN or outside int32 (what the x86-64 conversion
+// yields; mx == mn divides by zero).  No contraction: nothing here may fuse.
+__device__ __forceinline__ int cloud_grey(float z, float mn, float range)
+{
+#pragma clang fp contract(off)
+    const float num = z - mn;
+    const float q = __fdiv_rn(num, range);
+    const double d = (double)q * 255.0;
+    return (d > -2147483649.0 && d < 2147483648.0) ? (int)d : (int)0x80000000u;
+}
+
+__global__ __launch_bounds__(256) void cloud_scatter_kernel(const int16_t* __restrict__ dmap, size_t st, size_t fs,
+                                                            int W, int H, int head, int nvec, QMat Q,
+                                                            const int2* __restrict__ rows,
+                                                            const int2* __restrict__ frames,
+                                                            float4* __restrict__ records, int capacity)
+{
+    const int lane = threadIdx.x & 63, f = blockIdx.y;
+    const int y = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (y >= H) return;  // whole waves
+    int base = rows[(size_t)f * H + y].x;  // wave-uniform: the records of earlier rows
+    if (base >= capacity) return;
+    const int2 mm = frames[f];
+    const float mn = (float)mm.x, range = (float)(mm.y - mm.x);
+    const int16_t* r = dmap + f * fs + (size_t)y * st;
+    float4* out = records + (size_t)f * capacity;
+    auto emit = [&](int x, int v, int pos) {
+        if (v > 0 && pos < capacity) {
+            float X, Y, Z;
+            calc_coordinate_dev(Q, (float)x, (float)y, (float)v, X, Y, Z);
+            out[pos] = make_float4(X, Y, Z, __int_as_float(cloud_grey(Z, mn, range)));
+        }
+    };
+    auto narrow = [&](int x0, int x1) {
+        for (; x0 < x1; x0 += 64) {
+            const int x = x0 + lane;
+            const int v = x < x1 ? r[x] : 0;
+            const unsigned long long m = __ballot(v > 0);
+            emit(x, v, base + lanes_below(m, lane));
+            base += __popcll(m);
+        }
+    };
+    narrow(0, head);
+    const uint4* rv = (const uint4*)(r + head);
+    for (int j0 = 0; j0 < nvec; j0 += 64) {
+        const int j = j0 + lane;
+        const uint4 q = j < nvec ? rv[j] : make_uint4(0u, 0u, 0u, 0u);
+        // a lane holds 8 neighbouring pixels: the records of lower lanes come first
+        int below = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const uint32_t d = k < 2 ? q.x : k < 4 ? q.y : k < 6 ? q.z : q.w;
+            const unsigned long long m = __ballot(((k & 1) ? hi16(d) : lo16(d)) > 0);
+            below += lanes_below(m, lane);
+            total += __popcll(m);
+        }
+        int pos = base + below;
+#pragma unroll 1
+        for (int k = 0; k < 8; k++) {
+            const uint32_t d = k < 2 ? q.x : k < 4 ? q.y : k < 6 ? q.z : q.w;
+            const int v = (k & 1) ? hi16(d) : lo16(d);
+            emit(head + j * 8 + k, v, pos);
+            pos += v > 0 ? 1 : 0;
+        }
+        base += total;
+    }
+    narrow(head + nvec * 8, W);
+}
+
 }  // namespace
 
 int median3x3_device(mvsv_ctx* ctx, int n, const int16_t* src, size_t ss, size_t sfs, int16_t* dst,
@@ -1216,6 +1395,30 @@ int reproject_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_
     hipLaunchKernelGGL(reproject_kernel, grid, dim3(256), 0, ctx->stream, dmap, st, fs, W, H, q,
                        (float4*)out, os, ofs);
     return check_hip(ctx, hipGetLastError(), "reprojection");
+}
+
+int point_cloud_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H, const float* Q,
+                       mvsv_cloud_point* records, int capacity, int* counts, size_t cs, int* minmax, size_t ms)
+{
+    int rc, head, nvec;
+    // (min, max) per frame, then (first record, min | max) per row; room for 16
+    // frames of 1024 rows at least, so the usual streams never grow (and so never
+    // synchronise) it
+    const size_t need = (size_t)n * ((size_t)H + 1);
+    if ((rc = ensure(ctx, ctx->cl_rows, std::max(need, (size_t)16 * 1025) * sizeof(int2), "point cloud row counts")))
+        return rc;
+    int2* frames = (int2*)ctx->cl_rows.ptr;
+    int2* rows = frames + n;
+    QMat q;
+    for (int i = 0; i < 16; i++) q.q[i] = Q[i];
+    display_split(dmap, st, fs, n, W, &head, &nvec);
+    dim3 grid((H + 3) / 4, n);
+    hipLaunchKernelGGL(cloud_rows_kernel, grid, dim3(256), 0, ctx->stream, dmap, st, fs, W, H, head, nvec, rows);
+    hipLaunchKernelGGL(cloud_scan_kernel, dim3(n), dim3(kCloudScan), 0, ctx->stream, rows, H, frames, counts, cs,
+                       minmax, ms);
+    hipLaunchKernelGGL(cloud_scatter_kernel, grid, dim3(256), 0, ctx->stream, dmap, st, fs, W, H, head, nvec, q,
+                       (const int2*)rows, (const int2*)frames, (float4*)records, capacity);
+    return check_hip(ctx, hipGetLastError(), "point cloud");
 }
 
 }  // namespace mvsv

@@ -14,6 +14,10 @@
 // With mvsv_stream_enable_display, the 8-bit display map of every frame
 // (cv::normalize NORM_MINMAX, the last step of trgt/liveDisparity.cpp's loop) is
 // computed after them and comes back with the frame too (front_display).
+// With mvsv_stream_enable_cloud, the point cloud of every frame (the dmap2pcl call
+// that ends the detector loops' key handler, trgt/demo.cpp:394) is compacted after
+// them into a device ring; only its (count, min, max) come back with the frame and
+// front_cloud copies the records that exist on demand.
 // With mvsv_stream_set_batch(b), pushed frames are computed b at a time: the
 // slots' device buffers are one contiguous [depth][frame] array, so a group of
 // consecutive slots is one frame-batch launch (sustained rate of the batch
@@ -209,7 +213,30 @@ struct mvsv_stream {
     size_t disp_px = 0, disp_slot_bytes = 0;
     uint8_t* disp_map(long i) const { return hDisp + (size_t)i * disp_slot_bytes; }
     int16_t* disp_minmax(long i) const { return (int16_t*)(disp_map(i) + ((disp_px + 1) & ~(size_t)1)); }
+    // the point cloud of cloud_roi of every frame (mvsv_stream_enable_cloud): the
+    // records stay in a device ring, (count, min, max) per slot come to the host
+    bool cloud = false;
+    mvsv_rect cloud_roi{};
+    float cloud_Q[16] = {};
+    int cloud_max = 0;
+    mvsv_cloud_point* dCloud = nullptr;  // [depth][cloud_max]
+    int* dCloudHdr = nullptr;            // [depth][3] (count, min, max)
+    int* hCloudHdr = nullptr;            // pinned, [depth][3]
+    hipStream_t cloud_copy = nullptr;    // front_cloud's copies: not behind the later frames' downloads
 };
+
+static void cloud_free(mvsv_stream* st)
+{
+    if (st->dCloud) (void)hipFree(st->dCloud);
+    if (st->dCloudHdr) (void)hipFree(st->dCloudHdr);
+    if (st->hCloudHdr) (void)hipHostFree(st->hCloudHdr);
+    if (st->cloud_copy) (void)hipStreamDestroy(st->cloud_copy);
+    st->cloud_copy = nullptr;
+    st->dCloud = nullptr;
+    st->dCloudHdr = nullptr;
+    st->hCloudHdr = nullptr;
+    st->cloud = false;
+}
 
 static void display_free(mvsv_stream* st)
 {
@@ -266,6 +293,7 @@ static void stream_free(mvsv_stream* st)
     if (st->dCropR) (void)hipFree(st->dCropR);
     samplepoints_free(st);
     display_free(st);
+    cloud_free(st);
     if (st->rep) (void)hipHostFree(st->rep);
     if (st->up) (void)hipStreamDestroy(st->up);
     if (st->down) (void)hipStreamDestroy(st->down);
@@ -500,6 +528,12 @@ static int stream_launch(mvsv_stream* st)
                                              st->disp_alpha, st->disp_beta, st->dDisp + (size_t)i0 * st->disp_px, rw,
                                              st->disp_px, st->dDispMM + 2 * i0);
         }
+        if (status == MVSV_OK && st->cloud) {
+            const mvsv_rect& q = st->cloud_roi;
+            status = point_cloud_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, q.x1 - q.x0, q.y1 - q.y0,
+                                        st->cloud_Q, st->dCloud + (size_t)i0 * st->cloud_max, st->cloud_max,
+                                        st->dCloudHdr + 3 * i0, 3, st->dCloudHdr + 3 * i0 + 1, 3);
+        }
         if (status != MVSV_OK && ctx != st->ctx) st->ctx->err = ctx->err;  // reported by pop
         st->runs++;
         if ((rc = mark_last_use(ctx, MVSV_OK)) ||
@@ -546,6 +580,10 @@ static int stream_launch(mvsv_stream* st)
                                                       hipMemcpyDeviceToHost, st->down), "stream D2H")))
                     return rc;
             }
+            if (st->cloud &&  // the header only: the records wait on the device for front_cloud
+                (rc = check_hip(c, hipMemcpyAsync(st->hCloudHdr + 3 * (i0 + k), st->dCloudHdr + 3 * (i0 + k),
+                                                  3 * sizeof(int), hipMemcpyDeviceToHost, st->down), "stream D2H")))
+                return rc;
             if ((rc = check_hip(c, hipEventRecord(s.done, st->down), "stream event"))) return rc;
         }
         st->launched += n;
@@ -948,6 +986,102 @@ int mvsv_stream_front_display_view(mvsv_stream* st, const uint8_t** map, int16_t
     if ((rc = display_front(st, &idx))) return rc;
     *map = st->disp_map(idx);
     if (minmax) std::memcpy(minmax, st->disp_minmax(idx), 2 * sizeof(int16_t));
+    return MVSV_OK;
+}
+
+int mvsv_stream_disable_cloud(mvsv_stream* st)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (st->head != st->tail)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the point cloud changes only while no frame is pending");
+    DeviceGuard dev_guard(st->ctx->device);
+    cloud_free(st);  // every frame was popped: nothing in flight uses the buffers
+    return MVSV_OK;
+}
+
+int mvsv_stream_enable_cloud(mvsv_stream* st, const mvsv_rect* roi, const float* Q, int max_points)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (!Q) return set_error(ctx, MVSV_E_INVALID_ARG, "null Q matrix");
+    if (st->head != st->tail)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "the point cloud changes only while no frame is pending");
+    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, st->W, st->H};
+    if (q.x0 < 0 || q.y0 < 0 || q.x1 > st->W || q.y1 > st->H || q.x1 <= q.x0 || q.y1 <= q.y0)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "point cloud ROI empty or outside the image");
+    const size_t roi_px = (size_t)(q.x1 - q.x0) * (q.y1 - q.y0);
+    if (roi_px > (size_t)INT32_MAX) return set_error(ctx, MVSV_E_INVALID_ARG, "point cloud ROI too large");
+    DeviceGuard dev_guard(ctx->device);
+    cloud_free(st);
+    st->cloud_roi = q;
+    std::memcpy(st->cloud_Q, Q, sizeof(st->cloud_Q));
+    st->cloud_max = (int)(max_points <= 0 ? roi_px : std::min((size_t)max_points, roi_px));
+    const size_t depth = st->slots.size();
+    const bool ok =
+        hipMalloc((void**)&st->dCloud, depth * (size_t)st->cloud_max * sizeof(mvsv_cloud_point)) == hipSuccess &&
+        hipMalloc((void**)&st->dCloudHdr, depth * 3 * sizeof(int)) == hipSuccess &&
+        hipHostMalloc((void**)&st->hCloudHdr, depth * 3 * sizeof(int), hipHostMallocDefault) == hipSuccess &&
+        hipStreamCreateWithFlags(&st->cloud_copy, hipStreamNonBlocking) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        cloud_free(st);
+        return set_error(ctx, MVSV_E_OOM, "point cloud buffer allocation failed");
+    }
+    st->cloud = true;
+    return MVSV_OK;
+}
+
+// the oldest pending frame, complete: its slot index in *idx
+static int cloud_front(mvsv_stream* st, long* idx, int* count, int32_t* minmax)
+{
+    mvsv_ctx* ctx = st->ctx;
+    if (!st->cloud) return set_error(ctx, MVSV_E_INVALID_ARG, "the point cloud is not enabled on this stream");
+    if (st->head == st->tail) return set_error(ctx, MVSV_E_INVALID_ARG, "stream empty");
+    *idx = st->tail % (long)st->slots.size();
+    auto& s = st->slots[*idx];
+    int rc;
+    if (st->tail >= st->launched && (rc = stream_launch(st))) return rc;  // partial group
+    if ((rc = check_hip(ctx, hipEventSynchronize(s.done), "stream sync"))) return rc;
+    if (s.status) return s.status;
+    // the report word is left for pop to read and clear
+    if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[*idx], __ATOMIC_ACQUIRE) != 0))
+        return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
+    const int* h = st->hCloudHdr + 3 * *idx;
+    if (count) *count = h[0];
+    if (minmax) {
+        minmax[0] = h[1];
+        minmax[1] = h[2];
+    }
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_cloud(mvsv_stream* st, mvsv_cloud_point* records, int capacity, int* count, int32_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (records && capacity < 0) return set_error(st->ctx, MVSV_E_INVALID_ARG, "negative point cloud capacity");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = cloud_front(st, &idx, count, minmax))) return rc;
+    const size_t k = records ? (size_t)std::min(std::min(st->hCloudHdr[3 * idx], st->cloud_max), capacity) : 0;
+    if (k == 0) return MVSV_OK;
+    // the frame is complete; a stream of its own, so the copy does not queue behind the later frames' downloads
+    if ((rc = check_hip(st->ctx, hipMemcpyAsync(records, st->dCloud + (size_t)idx * st->cloud_max,
+                                                k * sizeof(mvsv_cloud_point), hipMemcpyDeviceToHost, st->cloud_copy),
+                        "stream D2H")))
+        return rc;
+    return check_hip(st->ctx, hipStreamSynchronize(st->cloud_copy), "stream sync");
+}
+
+int mvsv_stream_front_cloud_device(mvsv_stream* st, const mvsv_cloud_point** records_dev, int* count, int32_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (!records_dev) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null records pointer");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = cloud_front(st, &idx, count, minmax))) return rc;
+    *records_dev = st->dCloud + (size_t)idx * st->cloud_max;
     return MVSV_OK;
 }
 

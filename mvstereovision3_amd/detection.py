@@ -388,6 +388,15 @@ class SamplepointDetection:
             self.mObstacleCounter += 1
 
 
+class _DeviceSpan:
+    """float32 device memory owned by someone else, for torch.as_tensor (no copy)."""
+
+    def __init__(self, ptr, shape, owner):
+        self._owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
 class DisparityStream:
     """Double-buffered camera-loop pipeline over mvsv_stream (include/mvsv.h).
 
@@ -682,6 +691,62 @@ class DisparityStream:
         check(lib().mvsv_stream_front_display(self._h, out.ctypes.data if out.size else None, shape[1],
                                               mm.ctypes.data), self._ctx.handle)
         return out, (int(mm[0]), int(mm[1]))
+
+    def enable_cloud(self, Q, roi=None, max_points=None):
+        """The point cloud of every frame from now on: the pixels with v > 0 of
+        dMap(roi) in raster order, as Utility::dmap2pcl writes them
+        (mvsv_stream_enable_cloud), compacted after SGBM into a device ring; only
+        while no frame is pending.  roi = (x0, y0, x1, y1), default the whole map;
+        x / y count from its corner.  max_points: the records kept per frame,
+        default every pixel of the roi."""
+        self._live()
+        q = np.ascontiguousarray(np.asarray(Q, np.float32).reshape(16))
+        r = Rect(*(int(v) for v in roi)) if roi is not None else None
+        check(lib().mvsv_stream_enable_cloud(self._h, ctypes.byref(r) if r is not None else None, q.ctypes.data,
+                                             0 if max_points is None else int(max_points)), self._ctx.handle)
+        px = self.width * self.height if r is None else (r.x1 - r.x0) * (r.y1 - r.y0)
+        self._cloud_max = px if max_points is None or max_points <= 0 else min(int(max_points), px)
+
+    def disable_cloud(self):
+        self._live()
+        check(lib().mvsv_stream_disable_cloud(self._h), self._ctx.handle)
+        self._cloud_max = None
+
+    def front_cloud(self, copy=True, return_minmax=False):
+        """(records, count) of the oldest pending frame, which stays pending (pop it
+        afterwards).  count: the frame's number of valid pixels; records: the first
+        min(count, max_points) of them as a structured array of CLOUD_DTYPE, copied
+        from the device now that the count is known.  copy=False: no copy -- a
+        float32 device tensor (min(count, max_points), 4) viewing the frame's slot
+        of the ring ((x, y, z, grey bits), as point_cloud returns), valid until the
+        frame is popped.  return_minmax: also (min, max) over the valid values."""
+        self._live()
+        from .utility import CLOUD_DTYPE
+        cap = getattr(self, "_cloud_max", None) or 0
+        count = ctypes.c_int(0)
+        mm = np.zeros(2, np.int32)
+        if copy:
+            # the header first (the frame is waited for here), then the records that exist
+            check(lib().mvsv_stream_front_cloud(self._h, None, 0, ctypes.byref(count), mm.ctypes.data),
+                  self._ctx.handle)
+            rec = np.empty(min(count.value, cap), CLOUD_DTYPE)
+            if rec.size:
+                check(lib().mvsv_stream_front_cloud(self._h, rec.ctypes.data, rec.size, None, None),
+                      self._ctx.handle)
+        else:
+            import torch
+            ptr = ctypes.c_void_p()
+            check(lib().mvsv_stream_front_cloud_device(self._h, ctypes.byref(ptr), ctypes.byref(count),
+                                                       mm.ctypes.data), self._ctx.handle)
+            k = min(count.value, cap)
+            dev = torch.device("cuda", self._ctx.device)
+            if k == 0:
+                rec = torch.empty((0, 4), dtype=torch.float32, device=dev)
+            else:
+                rec = torch.as_tensor(_DeviceSpan(ptr.value, (k, 4), self), device=dev)
+        if return_minmax:
+            return rec, count.value, (int(mm[0]), int(mm[1]))
+        return rec, count.value
 
     @staticmethod
     def _display_view_released(stream):

@@ -20,6 +20,9 @@ PLY_PLAIN = 0
 PLY_WITH_COLOR = 1
 PLY_WITH_COLOR_SHADING = 2
 
+# one record of a point cloud (mvsv_cloud_point)
+CLOUD_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"), ("grey", "i4")])
+
 
 def _q16(Q) -> np.ndarray:
     q = np.ascontiguousarray(np.asarray(Q, dtype=np.float32).reshape(16))
@@ -64,7 +67,22 @@ class Utility:
 
     @staticmethod
     def dmap2pcl(filename: str, dMap, Q) -> None:
-        """src/utility.cpp:242-262: PLY of every pixel with disparity > 0 (WITH_COLOR)."""
+        """src/utility.cpp:242-262: PLY of every pixel with disparity > 0 (WITH_COLOR).
+        An int16 device tensor (H, W) is compacted on the GPU (point_cloud): the map
+        stays there and only the count and the valid points come to the host."""
+        if _is_device_map(dMap):
+            if dMap.dim() != 2:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "dmap2pcl: 2-D int16 map expected")
+            pts, count, mm = point_cloud(dMap, Q, return_minmax=True)
+            k = int(count)
+            if k == 0:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "dmap2pcl: map has no positive disparity")
+            xyzg = pts[:k].cpu().numpy()
+            # the writer takes min / max from its map: a two-pixel map holding them gives the same
+            w = ply("Hagen Hiller", "disparity pointcloud", mm.cpu().numpy().astype(np.int16).reshape(1, 2))
+            if not w.write(filename, xyzg[:, :3], ply.WITH_COLOR):
+                raise MvsvError(_lib.MVSV_E_IO, f"cannot write {filename}")
+            return
         d = np.asarray(dMap)
         if d.ndim != 2 or d.dtype != np.int16:
             raise MvsvError(_lib.MVSV_E_INVALID_ARG, "dmap2pcl: 2-D int16 map expected")
@@ -215,6 +233,72 @@ def normalize_minmax(dmap, alpha=0, beta=255, out=None, return_minmax=False):
     if return_minmax:
         return out, (mm if d.ndim == 3 else mm[0])
     return out
+
+
+def point_cloud(dmap, Q, max_points=None, return_minmax=False, out=None):
+    """The valid pixels (v > 0) of an int16 map as a point cloud, compacted on the
+    GPU in raster order -- what Utility::dmap2pcl makes of a map (src/utility.cpp:
+    248-259), with the grey ply::write prints (mvsv_point_cloud_device).
+
+    A torch device tensor (H, W) or (N, H, W) (any view with unit column stride)
+    gives (records, counts), asynchronously on the current stream: records float32
+    (cap, 4) / (N, cap, 4) = (x, y, z, grey bits) -- read the int32 grey as
+    records.view(torch.int32)[..., 3] -- and counts int32, scalar / (N,).  cap =
+    max_points, default H * W.  Frame f's first min(counts[f], cap) records are
+    written and nothing else; counts holds the number of valid pixels even beyond
+    cap.  out: a contiguous float32 device tensor (cap, 4) / (N, cap, 4) to write into.
+
+    A numpy map (H, W) gives the records as a structured array of CLOUD_DTYPE,
+    trimmed to min(count, max_points).
+
+    return_minmax: also the int32 (min, max) over the valid values, (2,) / (N, 2);
+    (32767, -32768) where there is none."""
+    q = _q16(Q)
+    if type(dmap).__module__.startswith("torch") and dmap.is_cuda:
+        import torch
+        d, batched, ctx = _device_frames(dmap, "point_cloud")
+        n, H, W = d.shape
+        if out is None:
+            cap = H * W if max_points is None else int(max_points)
+            if cap < 1:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "point_cloud: max_points must be at least 1")
+            out = torch.empty((n, cap, 4) if batched else (cap, 4), dtype=torch.float32, device=dmap.device)
+        elif not (type(out).__module__.startswith("torch") and out.is_cuda and out.dtype == torch.float32 and
+                  out.is_contiguous() and out.dim() == (3 if batched else 2) and out.shape[-1] == 4 and
+                  out.shape[-2] >= 1 and (not batched or out.shape[0] == n)):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG,
+                            "point_cloud: out must be a contiguous float32 device tensor (cap, 4) or (N, cap, 4)")
+        cap = out.shape[-2]
+        counts = torch.empty((n,), dtype=torch.int32, device=dmap.device)
+        mm = torch.empty((n, 2), dtype=torch.int32, device=dmap.device) if return_minmax else None
+        check(lib().mvsv_point_cloud_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
+                                            q.ctypes.data, out.data_ptr(), cap, counts.data_ptr(),
+                                            mm.data_ptr() if return_minmax else None), ctx.handle)
+        c = counts if batched else counts[0]
+        if return_minmax:
+            return out, c, (mm if batched else mm[0])
+        return out, c
+    d = np.asarray(dmap)
+    if d.ndim != 2 or d.dtype != np.int16:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "point_cloud: 2-D int16 map expected")
+    if d.strides[1] != 2:
+        d = np.ascontiguousarray(d)
+    cap = d.size if max_points is None else int(max_points)
+    if cap < 1:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "point_cloud: max_points must be at least 1")
+    cap = min(cap, d.size)
+    rec = np.empty(cap, CLOUD_DTYPE)
+    count = ctypes.c_int(0)
+    mm = np.zeros(2, np.int32)
+    ctx = context(0)
+    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    check(lib().mvsv_point_cloud(ctx.handle, d.ctypes.data, d.strides[0] // 2, d.shape[1], d.shape[0],
+                                 q.ctypes.data, rec.ctypes.data, cap, ctypes.byref(count), mm.ctypes.data),
+          ctx.handle)
+    rec = rec[:min(count.value, cap)]
+    if return_minmax:
+        return rec, mm
+    return rec
 
 
 class ply:  # noqa: N801 - reference name (inc/ply.h)
