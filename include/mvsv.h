@@ -61,6 +61,14 @@
  *                                     of ply::write src/ply.cpp:90, compacted on the device
  *   mvsv_stream_enable_cloud /        the point cloud with every frame of a stream (the
  *   _front_cloud(_device)             dmap2pcl call of trgt/demo.cpp:394 and the other loops)
+ *   mvsv_sharpness(_device)           Utility::checkSharpness src/utility.cpp:163-174, the
+ *                                     focusing loop of trgt/liveView.cpp:94-117
+ *   mvsv_stream_enable_sharpness /    the focus measure of the pushed pair with every frame
+ *   _front_sharpness                  of a stream
+ *   mvsv_undistort_maps /             cv::undistort's CV_16SC2 stripe maps, cv::remap on such
+ *   mvsv_remap_fixed_device /         maps, and Stereosystem::getUndistortedImagepair
+ *   mvsv_undistort_pair               src/Stereosystem.cpp:179-191 (trgt/liveUndistortion.cpp:58,
+ *                                     example/images.cpp:95)
  *
  * Conventions
  *   - Plain C types only; no exceptions cross this boundary.
@@ -537,6 +545,89 @@ MVSV_API int mvsv_stream_front_cloud(mvsv_stream* s, mvsv_cloud_point* records, 
  * frame is popped -- for consumers that stay on the GPU. */
 MVSV_API int mvsv_stream_front_cloud_device(mvsv_stream* s, const mvsv_cloud_point** records_dev, int* count,
                                             int32_t* minmax);
+
+/* ---- camera set-up: the focus measure (Utility::checkSharpness, src/utility.cpp:163-174) ----
+ * OpenCV 3.4: Lx = sepFilter2D(src, CV_64F, kernelX = M, kernelY = G), Ly =
+ * sepFilter2D(src, CV_64F, kernelX = G, kernelY = M) with M = (-1, 2, -1) and
+ * G = getGaussianKernel(3, -1) = (0.25, 0.5, 0.25); the result is cv::mean(|Lx| + |Ly|).
+ *   border   BORDER_REFLECT_101 (index i of n: 0 for n == 1, else -i below 0 and
+ *            2n - 2 - i from n on)
+ *   ROI      the filter engine does not isolate a view: the 1-pixel halo of a roi
+ *            comes from the parent image and is reflected only at the parent's border
+ *   mean     sum * (1.0 / N): a reciprocal and a product, each rounded
+ * Every intermediate is a multiple of 0.25 far below 2^53, so the doubles are exact
+ * and
+ *   S4 = sum over the roi of |KX (*) s| + |KY (*) s|,  KX = (1,2,1)^T (-1,2,-1) = 4 Lx,
+ *                                                      KY = (-1,2,-1)^T (1,2,1) = 4 Ly
+ * on the reflect-extended parent s is an exact integer (at most 4080 a pixel).  The
+ * device delivers S4; sharpness = (S4 / 4.0) * (1.0 / N) in host double, N the roi's
+ * pixels.  No atomics: two runs give the same bytes.
+ *
+ * n u8 images (device), strides in bytes, any alignment (row and frame strides that
+ * are multiples of 4 take packed loads, others narrow ones; no byte outside
+ * [row, row + width) is read); roi NULL = whole image, else non-empty and inside it;
+ * width * height < 2^31; sums: device, n int64.  Asynchronous on the context's stream. */
+MVSV_API int mvsv_sharpness_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t stride, size_t frame_stride,
+                                   int width, int height, const mvsv_rect* roi, int64_t* sums);
+/* one host image, synchronous; value and sum4 may each be NULL */
+MVSV_API int mvsv_sharpness(mvsv_ctx* ctx, const uint8_t* img, size_t stride, int width, int height,
+                            const mvsv_rect* roi, double* value, int64_t* sum4);
+
+/* The focus measure in the stream (either kind): mvsv_sharpness_device of the pushed
+ * left and right image, each over its own roi (NULL: the whole image), on the frame's
+ * device stream beside the other post-passes -- the value liveView prints, with every
+ * frame.  The pushed images are measured: on a raw stream the raw camera pair before
+ * rectification (what getImagepair returned), and the rois are validated against that
+ * size.  16 bytes more come back with a frame.  Allowed only while no frame is pending
+ * (MVSV_E_INVALID_ARG otherwise); a second call replaces the first.  A stream that
+ * never enables it enqueues and allocates nothing extra. */
+MVSV_API int mvsv_stream_enable_sharpness(mvsv_stream* s, const mvsv_rect* roi_left, const mvsv_rect* roi_right);
+MVSV_API int mvsv_stream_disable_sharpness(mvsv_stream* s);
+/* Waits for the oldest pending frame and hands out (left, right) values and / or S4
+ * sums without popping it, so it composes with pop, pop_view, pop_pair, front_samples,
+ * front_display and front_cloud.  Either output may be NULL.  MVSV_E_INVALID_ARG when
+ * the measure is not enabled or no frame is pending; the frame's own error when its
+ * launch failed (as pop reports it). */
+MVSV_API int mvsv_stream_front_sharpness(mvsv_stream* s, double value[2], int64_t sum4[2]);
+
+/* ---- camera set-up: undistorted pairs (Stereosystem::getUndistortedImagepair) -------
+ * cv::undistort(src, dst, K, dist) of OpenCV 3.4 (no new camera matrix: Ar = K) works
+ * in stripes of min(max(1, 4096 / W), H) rows; for the stripe starting at row y0 it
+ * calls initUndistortRectifyMap(K, dist, I, Ar with Ar(1,2) = cy - y0, CV_16SC2) and
+ * remap(INTER_LINEAR, BORDER_CONSTANT 0).  CV_16SC2 maps come straight from the doubles
+ * u, v: iu = cvRound(u * 32), iv = cvRound(v * 32) (half to even), xy = ((short)(iu >> 5),
+ * (short)(iv >> 5)) -- plain casts, not saturated as in mvsv_convert_maps --,
+ * frac = (iv & 31) * 32 + (iu & 31).
+ *
+ * mvsv_undistort_maps: those maps for a whole width x height image (host only).  K
+ * 3x3, dist as for mvsv_init_undistort_rectify_map (ndist 0: all zeros, dist may be
+ * NULL), new_K 3x3 or NULL for K; xy_stride in int16 pairs, frac_stride in elements.
+ * The double arithmetic is mvsv_init_undistort_rectify_map's (shared code, the
+ * incremental walk along a row included), and so is its caveat: Ar is inverted by its
+ * adjugate where OpenCV uses LU, so u, v may differ in the last bit and a map entry by
+ * one 1/32 step where u * 32 or v * 32 lies that close to a rounding tie. */
+MVSV_API int mvsv_undistort_maps(const double* K, const double* dist, int ndist, const double* new_K, int width,
+                                 int height, int16_t* xy, size_t xy_stride, uint16_t* frac, size_t frac_stride);
+/* cv::remap(src, dst, xy, frac, INTER_LINEAR, BORDER_CONSTANT 0) for CV_8UC1 images and
+ * CV_16SC2 + CV_16UC1 maps on the device: pure integer (mvsv_remap_device's arithmetic
+ * behind its rounding step), bit-exact for given maps.  n frames share one map pair of
+ * the destination's size; image strides in bytes, xy_stride in int16 pairs, frac_stride
+ * in elements; maps 2-byte aligned. */
+MVSV_API int mvsv_remap_fixed_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t src_stride,
+                                     size_t src_frame_stride, int src_width, int src_height, const int16_t* xy,
+                                     size_t xy_stride, const uint16_t* frac, size_t frac_stride, uint8_t* dst,
+                                     size_t dst_stride, size_t dst_frame_stride, int dst_width, int dst_height);
+/* Stereosystem::getUndistortedImagepair on host buffers (synchronous): cv::undistort of
+ * the left image with (K_left, dist_left) and of the right one with (K_right,
+ * dist_right).  out_left / out_right may be left / right (the reference copies the
+ * result back into the pair).  The context keeps the device maps of the last
+ * calibration it was called with (size, K and dist of both sides): a camera loop builds
+ * and uploads them once; mvsv_trim releases them. */
+MVSV_API int mvsv_undistort_pair(mvsv_ctx* ctx, const uint8_t* left, size_t left_stride, const uint8_t* right,
+                                 size_t right_stride, int width, int height, const double* K_left,
+                                 const double* dist_left, int ndist_left, const double* K_right,
+                                 const double* dist_right, int ndist_right, uint8_t* out_left,
+                                 size_t out_left_stride, uint8_t* out_right, size_t out_right_stride);
 
 /* ---- before the path: rectification ---------------------------
  * cv::remap(src, dst, map_x, map_y, INTER_LINEAR) with BORDER_CONSTANT 0 for CV_8UC1

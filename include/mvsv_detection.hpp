@@ -97,6 +97,22 @@ inline void normalize(const Mat& dMap, Mat& out, double alpha = 0, double beta =
                                 alpha, beta, out.data, out.step, minmax),
           c);
 }
+// src/utility.cpp:163-174: cv::mean(|Lx| + |Ly|) of the two cv::sepFilter2D responses,
+// on the device (mvsv_sharpness).  The reference passes a view, checkSharpness(
+// s.mLeft(viewArea)) (trgt/liveView.cpp:107-108), and OpenCV's filter engine takes
+// the view's 1-pixel halo from the parent image; an mvsv::Mat view does not know its
+// parent, so the parent and the view area are passed here.  sum4: where given, the
+// exact integer sum S4 (include/mvsv.h) behind the value.
+inline double checkSharpness(const Mat& image, const Rect& viewArea, int64_t* sum4 = nullptr)
+{
+    if (image.type != MAT_8UC1 || image.empty()) throw Error(MVSV_E_INVALID_ARG, "checkSharpness: CV_8U image expected");
+    const mvsv_rect r{viewArea.x, viewArea.y, viewArea.x + viewArea.width, viewArea.y + viewArea.height};
+    double value = 0;
+    mvsv_ctx* c = thread_context();
+    check(mvsv_sharpness(c, image.data, image.step, image.cols, image.rows, &r, &value, sum4), c);
+    return value;
+}
+inline double checkSharpness(const Mat& image) { return checkSharpness(image, Rect{0, 0, image.cols, image.rows}); }
 // the loop of dmap2pcl without the file: the pixels with v > 0 of dMap in raster
 // order as (x, y, z, grey) records, compacted on the device (mvsv_point_cloud).
 // max_points <= 0: every valid pixel.  Returns the number of valid pixels, which may
@@ -513,6 +529,26 @@ inline int stream_front_cloud(mvsv_ctx* ctx, mvsv_stream* s, int cap, std::vecto
     return count;
 }
 
+// the focus measure calls shared by DisparityStream and RawDisparityStream
+struct Sharpness {
+    double left = 0, right = 0;      // Utility::checkSharpness of the pushed images
+    int64_t sum4_left = 0, sum4_right = 0;
+};
+inline void stream_enable_sharpness(mvsv_ctx* ctx, mvsv_stream* s, const Rect* roi_left, const Rect* roi_right)
+{
+    mvsv_rect l{}, r{};
+    if (roi_left) l = {roi_left->x, roi_left->y, roi_left->x + roi_left->width, roi_left->y + roi_left->height};
+    if (roi_right) r = {roi_right->x, roi_right->y, roi_right->x + roi_right->width, roi_right->y + roi_right->height};
+    check(mvsv_stream_enable_sharpness(s, roi_left ? &l : nullptr, roi_right ? &r : nullptr), ctx);
+}
+inline Sharpness stream_front_sharpness(mvsv_ctx* ctx, mvsv_stream* s)
+{
+    double v[2] = {0, 0};
+    int64_t s4[2] = {0, 0};
+    check(mvsv_stream_front_sharpness(s, v, s4), ctx);
+    return {v[0], v[1], s4[0], s4[1]};
+}
+
 // Camera loop without the worker thread: push rectified pairs, pop maps (and the
 // 9x9 means of the work ROI) in order; up to `depth` frames in flight.
 class DisparityStream {
@@ -605,6 +641,15 @@ public:
     {
         return stream_front_cloud(ctx_, s_, cloud_, out, minmax);
     }
+    // Utility::checkSharpness of every pair pushed from now on (no frame may be pending),
+    // each side over its own view area (default: the whole image)
+    void enableSharpness(const Rect* roi_left = nullptr, const Rect* roi_right = nullptr)
+    {
+        stream_enable_sharpness(ctx_, s_, roi_left, roi_right);
+    }
+    void disableSharpness() { check(mvsv_stream_disable_sharpness(s_), ctx_); }
+    // the oldest pending frame's focus values; the frame stays pending
+    Sharpness frontSharpness() { return stream_front_sharpness(ctx_, s_); }
     // the same records on the device (the frame's slot of the ring), valid until the frame is popped
     const mvsv_cloud_point* frontCloudDevice(int* count, int32_t* minmax = nullptr)
     {

@@ -5,6 +5,7 @@
 // Reference surface kept (names, argument meaning, return values, quirks):
 //   getFundamentalMatrix / getTranslationMatrix / getBaseline / getRotationMatrix /
 //   getQMatrix / getNewKMats                         src/Stereosystem.cpp:47-80
+//   getUndistortedImagepair(Stereopair&)             src/Stereosystem.cpp:179-191
 //   initRectification                                src/Stereosystem.cpp:193-241
 //   getRectifiedImagepair(Stereopair&)               src/Stereosystem.cpp:243-277
 //   getRectifiedImagepair(Stereopair&, float)        src/Stereosystem.cpp:279-315
@@ -17,11 +18,11 @@
 // mode, the raw pair of getImagepair) is given here at construction / passed
 // in: getRectifiedImagepair rectifies the raw pair the Stereopair holds, in
 // place, like the reference does after Stereosystem::getImagepair filled it.
-// Calibration (cv::stereoCalibrate) and getUndistortedImagepair stay out of
-// scope.  Compute: the remap and resize run in HIP kernels
-// (mvsv_rectify_pair, mvsv_resize, include/mvsv.h); stereoRectify and the
+// Calibration (cv::stereoCalibrate) stays out of scope.
+// Compute: the remaps and the resize run in HIP kernels (mvsv_rectify_pair,
+// mvsv_undistort_pair, mvsv_resize, include/mvsv.h); stereoRectify and the
 // undistort maps are host restatements (mvsv_stereo_rectify,
-// mvsv_init_undistort_rectify_map).  LOG(INFO) / LOG(ERROR) lines of the
+// mvsv_init_undistort_rectify_map, mvsv_undistort_maps).  LOG(INFO) / LOG(ERROR) lines of the
 // reference go to stderr with the same mTag prefix.
 #ifndef MVSV_STEREOSYSTEM_HPP
 #define MVSV_STEREOSYSTEM_HPP
@@ -92,6 +93,30 @@ public:
     Matd getRotationMatrix() const { return mR; }
     Matd getQMatrix() const { return mQ; }
     std::vector<Matd> getNewKMats() const { return {mP0, mP1}; }
+
+    // cv::undistort of the raw pair in sip (mWidth x mHeight CV_8UC1) with each
+    // camera's matrix and distortion coefficients, written back into sip
+    // (src/Stereosystem.cpp:179-191).  The fixed-point maps are built once and stay
+    // on the device, in the calling thread's context, as long as the calibration
+    // this instance passes does not change (mvsv_undistort_pair): loadIntrinsic with
+    // other values replaces them.  An empty distCoeffs matrix means no distortion.
+    bool getUndistortedImagepair(Stereopair& sip)
+    {
+        Mat& L = sip.mLeft;
+        Mat& R = sip.mRight;
+        if (mIntrinsicLeft.rows != 3 || mIntrinsicRight.rows != 3 || L.empty() || R.empty() ||
+            L.type != MAT_8UC1 || R.type != MAT_8UC1 || L.cols != mWidth || L.rows != mHeight ||
+            R.cols != mWidth || R.rows != mHeight)
+            return false;
+        mvsv_ctx* c = thread_context();
+        check(mvsv_undistort_pair(c, L.data, L.step, R.data, R.step, mWidth, mHeight, mIntrinsicLeft.data(),
+                                  mDistCoeffsLeft.empty() ? nullptr : mDistCoeffsLeft.data(),
+                                  (int)mDistCoeffsLeft.v.size(), mIntrinsicRight.data(),
+                                  mDistCoeffsRight.empty() ? nullptr : mDistCoeffsRight.data(),
+                                  (int)mDistCoeffsRight.v.size(), L.data, L.step, R.data, R.step),
+              c);
+        return true;
+    }
 
     // --- rectification (src/Stereosystem.cpp:193-320) --------------------------
     bool initRectification()
@@ -386,6 +411,14 @@ public:
     {
         stream_front_display(mCtx, mStream, mDisplay, out, minmax);
     }
+    // the focus measure of every pushed raw pair (what trgt/liveView.cpp prints),
+    // as on DisparityStream; the view areas lie in the raw frame
+    void enableSharpness(const Rect* roi_left = nullptr, const Rect* roi_right = nullptr)
+    {
+        stream_enable_sharpness(mCtx, mStream, roi_left, roi_right);
+    }
+    void disableSharpness() { check(mvsv_stream_disable_sharpness(mStream), mCtx); }
+    Sharpness frontSharpness() { return stream_front_sharpness(mCtx, mStream); }
     // the point cloud on every frame, as on DisparityStream
     void enableCloud(const QMatrix& Q, const Rect* roi = nullptr, int max_points = 0)
     {

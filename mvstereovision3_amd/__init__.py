@@ -15,8 +15,9 @@ from .disparity import (SAMPLE_HIT_DTYPE, Disparity, StereoBM, StereoSGBM, Stere
 from .detection import (DisparityStream, MeanDisparityDetection, Samplepoint, SamplepointDetection, Subimage,
                         create_dmap_rois)
 from .calibration import Stereosystem, read_matrix, stereo_rectify, write_matrices
-from .rectify import convert_maps, init_undistort_rectify_map, rectify_pair, remap
-from .utility import CLOUD_DTYPE, Utility, dMapValues, minmax, normalize_minmax, ply, point_cloud, reproject
+from .rectify import (convert_maps, init_undistort_rectify_map, rectify_pair, remap, remap_fixed, undistort_maps,
+                      undistort_pair)
+from .utility import CLOUD_DTYPE, Utility, dMapValues, minmax, normalize_minmax, ply, point_cloud, reproject, sharpness
 
 __all__ = [
     "Disparity", "StereoBM", "StereoSGBM", "Stereopair", "sgbmParameters", "MvsvError",
@@ -29,5 +30,6 @@ __all__ = [
     "OPT_PATH_SCHEDULE", "OPT_BITSLICE", "Samplepoint", "SamplepointDetection", "samplepoint_layout",
     "samplepoint_values", "samplepoint_detect", "SAMPLE_HIT_DTYPE",
     "normalize_minmax", "minmax", "point_cloud", "CLOUD_DTYPE",
+    "sharpness", "undistort_maps", "remap_fixed", "undistort_pair",
 ]
 __version__ = "1.0.0"

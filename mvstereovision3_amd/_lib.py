@@ -174,6 +174,14 @@ def _declare(lib, strict=True):
         "mvsv_stream_disable_cloud": ([P], I),
         "mvsv_stream_front_cloud": ([P, P, I, ctypes.POINTER(I), P], I),
         "mvsv_stream_front_cloud_device": ([P, ctypes.POINTER(P), ctypes.POINTER(I), P], I),
+        "mvsv_sharpness_device": ([P, I, P, Z, Z, I, I, P, P], I),
+        "mvsv_sharpness": ([P, P, Z, I, I, P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)], I),
+        "mvsv_stream_enable_sharpness": ([P, P, P], I),
+        "mvsv_stream_disable_sharpness": ([P], I),
+        "mvsv_stream_front_sharpness": ([P, P, P], I),
+        "mvsv_undistort_maps": ([P, P, I, P, I, I, P, Z, P, Z], I),
+        "mvsv_remap_fixed_device": ([P, I, P, Z, Z, I, I, P, Z, P, Z, P, Z, Z, I, I], I),
+        "mvsv_undistort_pair": ([P, P, Z, P, Z, I, I, P, P, I, P, P, I, P, Z, P, Z], I),
         "mvsv_convert_maps": ([P, P, Z, I, I, P, Z, P, Z], I),
         "mvsv_remap_device": ([P, I, P, Z, Z, I, I, P, P, Z, P, Z, Z, I, I], I),
         "mvsv_rectify_pair": ([P, P, Z, P, Z, I, I, P, P, P, Z, P, Z], I),

@@ -150,9 +150,11 @@ class Stereosystem:
         self.mValidROI = [None, None]
         self.mDisplayROI = None
         self.mIsInit = False
+        self._undistort_maps = None  # device maps of getUndistortedImagepair, per instance
 
     # --- load / save (src/Stereosystem.cpp:326-446) ---------------------------
     def loadIntrinsic(self, file) -> bool:
+        self._undistort_maps = None
         v = Intrinsics()
         rc = _declare().mvsv_load_intrinsic(str(file).encode(), ctypes.byref(v))
         if rc == _lib.MVSV_E_PARSE:
@@ -245,6 +247,39 @@ class Stereosystem:
 
     def resetRectification(self):
         self.mIsInit = False
+        self._undistort_maps = None
+
+    def getUndistortedImagepair(self, sip) -> bool:
+        """src/Stereosystem.cpp:179-191: cv::undistort of sip.mLeft with
+        (mIntrinsicLeft, mDistCoeffsLeft) and of sip.mRight with the right camera's,
+        written back into sip.  The fixed-point maps of both sides are built once
+        per instance and stay on the device (loadIntrinsic and resetRectification
+        drop them); the remap runs in a HIP kernel (mvsv_remap_fixed_device).
+        Images: numpy arrays (uploaded, results come back as arrays) or uint8
+        device tensors (results stay on the device).  An empty distCoeffs matrix
+        -- loadIntrinsic never checks the left one -- means no distortion."""
+        import torch
+        from .rectify import remap_fixed, undistort_maps
+        if self.mIntrinsicLeft is None or self.mIntrinsicRight is None:
+            log.error("%sUnable to undistort: no intrinsics", self.mTag)
+            return False
+        if self._undistort_maps is None:
+            size = (self.width, self.height)
+            maps = []
+            for K, D in ((self.mIntrinsicLeft, self.mDistCoeffsLeft), (self.mIntrinsicRight, self.mDistCoeffsRight)):
+                xy, frac = undistort_maps(K, D, size)
+                maps.append((torch.from_numpy(xy).cuda(), torch.from_numpy(frac.view(np.int16)).cuda()))
+            self._undistort_maps = maps
+        out = []
+        for img, (xy, frac) in zip((sip.mLeft, sip.mRight), self._undistort_maps):
+            on_device = type(img).__module__.startswith("torch")
+            t = img if on_device else torch.from_numpy(np.ascontiguousarray(img, np.uint8)).to(xy.device)
+            if tuple(t.shape) != (self.height, self.width):
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "getUndistortedImagepair: pair of the system's size expected")
+            r = remap_fixed(t, xy, frac)
+            out.append(r if on_device else r.cpu().numpy())
+        sip.mLeft, sip.mRight = out
+        return True
 
     def getRectifiedImagepair(self, sip, factor=None) -> bool:
         """Remap sip.mLeft / sip.mRight (the raw pair) on the GPU and crop to the

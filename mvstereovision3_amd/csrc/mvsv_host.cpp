@@ -406,8 +406,9 @@ int mvsv_trim(mvsv_ctx* ctx)
                      &ctx->uf_tile, &ctx->tri_bnd, &ctx->bs_bnd, &ctx->status,
                      &ctx->dummy, &ctx->keys,
                      &ctx->bm_lf, &ctx->bm_rf, &ctx->bm_cost, &ctx->bm_sad, &ctx->h_left, &ctx->h_right,
-                     &ctx->h_out, &ctx->mm_part, &ctx->cl_rows};
+                     &ctx->h_out, &ctx->mm_part, &ctx->cl_rows, &ctx->sh_part, &ctx->ud_maps};
     for (DevBuf* b : all) free_buf(*b);
+    ctx->ud_key.clear();
     return MVSV_OK;
 }
 
@@ -1077,3 +1078,134 @@ int mvsv_rectify_pair(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t*
     }());
 }
 
+
+// ---- camera set-up: focus measure and undistorted pairs ---------------------------
+
+static bool rect_inside(const mvsv_rect& q, int W, int H)
+{
+    return q.x0 >= 0 && q.y0 >= 0 && q.x1 <= W && q.y1 <= H && q.x1 > q.x0 && q.y1 > q.y0;
+}
+
+// [Utility::checkSharpness] src/utility.cpp:163-174: the integer sum S4
+int mvsv_sharpness_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t st, size_t fs, int W, int H,
+                          const mvsv_rect* roi, int64_t* sums)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, W, H};
+    if (n <= 0 || !img || !sums || W <= 0 || H <= 0 || st < (size_t)W || !rect_inside(q, W, H) ||
+        (size_t)W * H > (size_t)INT32_MAX)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad sharpness arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, sharpness_device(ctx, n, img, st, fs, W, H, q, sums, 1));
+}
+
+int mvsv_sharpness(mvsv_ctx* ctx, const uint8_t* img, size_t st, int W, int H, const mvsv_rect* roi, double* value,
+                   int64_t* sum4)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, W, H};
+    if (!img || W <= 0 || H <= 0 || st < (size_t)W || !rect_inside(q, W, H) || (size_t)W * H > (size_t)INT32_MAX)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad sharpness arguments");
+    DeviceGuard dev_guard(ctx->device);
+    int64_t s4 = 0;
+    const int rc = mark_last_use(ctx, [&]() -> int {
+    // staged rows are a multiple of 4 bytes apart: packed loads for any width; the sum sits behind them
+    const size_t ws = ((size_t)W + 3) & ~(size_t)3, sum_at = (ws * H + 7) & ~(size_t)7;
+    int rc;
+    if ((rc = ensure(ctx, ctx->h_left, sum_at + sizeof(int64_t), "sharpness staging"))) return rc;
+    uint8_t* d = (uint8_t*)ctx->h_left.ptr;
+    int64_t* ds = (int64_t*)(d + sum_at);
+    hipStream_t s = ctx->stream;
+    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, ws, img, st, (size_t)W, H, hipMemcpyHostToDevice, s), "H2D image")) ||
+        (rc = sharpness_device(ctx, 1, d, ws, ws * H, W, H, q, ds, 1)) ||
+        (rc = check_hip(ctx, hipMemcpyAsync(&s4, ds, sizeof s4, hipMemcpyDeviceToHost, s), "D2H sharpness")))
+        return rc;
+    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
+    }());
+    if (rc) return rc;
+    if (sum4) *sum4 = s4;
+    // cv::mean: sum * (1.0 / N), a reciprocal and a product, each rounded
+    if (value) *value = ((double)s4 / 4.0) * (1.0 / ((double)(q.x1 - q.x0) * (double)(q.y1 - q.y0)));
+    return MVSV_OK;
+}
+
+// [cv::remap, CV_16SC2 + CV_16UC1 maps]
+int mvsv_remap_fixed_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh,
+                            const int16_t* xy, size_t xs, const uint16_t* frac, size_t fs, uint8_t* dst, size_t ds,
+                            size_t dfs, int dw, int dh)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0 || !src || !xy || !frac || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || ss < (size_t)sw ||
+        xs < (size_t)dw || fs < (size_t)dw || ds < (size_t)dw || ((uintptr_t)xy & 1) || ((uintptr_t)frac & 1))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad fixed-point remap arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, remap_fixed_device(ctx, n, src, ss, sfs, sw, sh, xy, xs, frac, fs, dst, ds, dfs, dw, dh));
+}
+
+// [Stereosystem::getUndistortedImagepair] src/Stereosystem.cpp:179-191: two cv::undistort
+int mvsv_undistort_pair(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs, int W, int H,
+                        const double* KL, const double* DL, int nL, const double* KR, const double* DR, int nR,
+                        uint8_t* oL, size_t ols, uint8_t* oR, size_t ors)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    auto dist_ok = [](const double* d, int nd) { return (nd == 0 || nd == 4 || nd == 5 || nd == 8) && (nd == 0 || d); };
+    if (!L || !R || !oL || !oR || !KL || !KR || W <= 0 || H <= 0 || ls < (size_t)W || rs < (size_t)W ||
+        ols < (size_t)W || ors < (size_t)W || !dist_ok(DL, nL) || !dist_ok(DR, nR) ||
+        (size_t)W * H > (size_t)INT32_MAX)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad undistortion arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, [&]() -> int {
+    const size_t px = (size_t)W * H;
+    int rc;
+    if ((rc = ensure(ctx, ctx->h_left, 2 * px, "undistort staging")) ||
+        (rc = ensure(ctx, ctx->h_right, 2 * px, "undistort staging")))
+        return rc;
+    hipStream_t s = ctx->stream;
+    // the maps of a calibration are built and uploaded once: the key is all they depend on
+    std::vector<double> key = {(double)W, (double)H, (double)nL, (double)nR};
+    key.insert(key.end(), KL, KL + 9);
+    key.insert(key.end(), KR, KR + 9);
+    key.insert(key.end(), DL, DL + nL);
+    key.insert(key.end(), DR, DR + nR);
+    const bool cached = ctx->ud_maps.ptr && key.size() == ctx->ud_key.size() &&
+                        std::memcmp(key.data(), ctx->ud_key.data(), key.size() * sizeof(double)) == 0;
+    if (!cached) {
+        ctx->ud_key.clear();
+        if ((rc = ensure(ctx, ctx->ud_maps, 2 * px * 6, "undistort maps"))) return rc;
+        std::vector<int16_t> xy(2 * px * 2);
+        std::vector<uint16_t> fr(2 * px);
+        if (mvsv_undistort_maps(KL, DL, nL, nullptr, W, H, xy.data(), W, fr.data(), W) ||
+            mvsv_undistort_maps(KR, DR, nR, nullptr, W, H, xy.data() + 2 * px, W, fr.data() + px, W))
+            return set_error(ctx, MVSV_E_INVALID_ARG, "singular camera matrix");
+        // synchronous copies: the host vectors end with this scope
+        if ((rc = check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize")) ||
+            (rc = check_hip(ctx, hipMemcpy(ctx->ud_maps.ptr, xy.data(), 4 * px * sizeof(int16_t),
+                                           hipMemcpyHostToDevice), "H2D map")) ||
+            (rc = check_hip(ctx, hipMemcpy((uint8_t*)ctx->ud_maps.ptr + 8 * px, fr.data(), 2 * px * sizeof(uint16_t),
+                                           hipMemcpyHostToDevice), "H2D map")))
+            return rc;
+        ctx->ud_key = key;
+    }
+    const int16_t* dxy = (const int16_t*)ctx->ud_maps.ptr;
+    const uint16_t* dfr = (const uint16_t*)((const uint8_t*)ctx->ud_maps.ptr + 8 * px);
+    uint8_t* dsrc = (uint8_t*)ctx->h_left.ptr;   // [2][H][W] inputs
+    uint8_t* ddst = (uint8_t*)ctx->h_right.ptr;  // [2][H][W] outputs: in-place calls are safe
+    const uint8_t* ins[2] = {L, R};
+    const size_t istr[2] = {ls, rs};
+    uint8_t* outs[2] = {oL, oR};
+    const size_t ostr[2] = {ols, ors};
+    for (int i = 0; i < 2; i++)
+        if ((rc = check_hip(ctx, hipMemcpy2DAsync(dsrc + i * px, W, ins[i], istr[i], W, H, hipMemcpyHostToDevice, s),
+                            "H2D image")))
+            return rc;
+    for (int i = 0; i < 2; i++)
+        if ((rc = remap_fixed_device(ctx, 1, dsrc + i * px, W, px, W, H, dxy + i * 2 * px, W, dfr + i * px, W,
+                                     ddst + i * px, W, px, W, H)))
+            return rc;
+    for (int i = 0; i < 2; i++)
+        if ((rc = check_hip(ctx, hipMemcpy2DAsync(outs[i], ostr[i], ddst + i * px, W, W, H, hipMemcpyDeviceToHost, s),
+                            "D2H image")))
+            return rc;
+    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
+    }());
+}

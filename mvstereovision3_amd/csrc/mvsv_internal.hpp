@@ -163,6 +163,12 @@ struct mvsv_ctx {
     mvsv::DevBuf mm_part;
     // point clouds: (min, max) per frame, then (first record, min | max) per row, int pairs
     mvsv::DevBuf cl_rows;
+    // focus measure: one 64-bit partial sum per block of sharpness_kernel, [n][blocks]
+    mvsv::DevBuf sh_part;
+    // mvsv_undistort_pair: both cameras' fixed-point maps ([2][H][W] int16 pairs, then
+    // [2][H][W] u16) for the calibration in ud_key (K, dist, size of both sides)
+    mvsv::DevBuf ud_maps;
+    std::vector<double> ud_key;
     // stage profiling (HIP events on the context stream)
     int prof = 0;
     struct Mark {
@@ -287,6 +293,14 @@ int minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t f
                   int16_t* minmax);
 int normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
                             double alpha, double beta, uint8_t* out, size_t os, size_t ofs, int16_t* minmax);
+// Focus measure (mvsv_post.hip): S4 (include/mvsv.h) of roi q of every u8 frame
+// into sums[f * ss]; q non-empty and inside the W x H image, strides in bytes.
+int sharpness_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t st, size_t fs, int W, int H, const mvsv_rect& q,
+                     int64_t* sums, size_t ss);
+// cv::remap with fixed-point maps (mvsv_post.hip): xs in int16 pairs, fs in elements
+int remap_fixed_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh,
+                       const int16_t* xy, size_t xs, const uint16_t* frac, size_t fs, uint8_t* dst, size_t ds,
+                       size_t dfs, int dw, int dh);
 // Point clouds (mvsv_post.hip): the records of the pixels with v > 0 of every frame
 // in raster order, frame f into records[f * capacity ..]; counts[f * cs] = the
 // number of such pixels, minmax[f * ms], [f * ms + 1] = their (min, max) where

@@ -347,14 +347,18 @@ int mvsv_convert_maps(const float* mx, const float* my, size_t ms, int W, int H,
     return MVSV_OK;
 }
 
-// [cv::initUndistortRectifyMap] (OpenCV 3.4 undistort.cpp), CV_32FC1 output
-int mvsv_init_undistort_rectify_map(const double* K, const double* dist, int ndist,
-                                    const double* Rm, const double* P, int W, int H, float* mx,
-                                    float* my, size_t ms)
+}  // extern "C"
+
+namespace {
+
+// [cv::initUndistortRectifyMap] (OpenCV 3.4 undistort.cpp): the double (u, v) of
+// every pixel of a W x H map in row order, emit(i, j, u, v) -- the arithmetic
+// shared by the CV_32FC1 maps and cv::undistort's CV_16SC2 stripes.  A = P * R
+// is inverted by its adjugate (OpenCV: LU), so a value may differ in its last bit.
+template <class Emit>
+int undistort_walk(const double* K, const double* dist, int ndist, const double* Rm, const double* P, int W, int H,
+                   Emit emit)
 {
-    if (!K || !P || !mx || !my || W <= 0 || H <= 0 || ms < (size_t)W ||
-        !(ndist == 0 || ndist == 4 || ndist == 5 || ndist == 8) || (ndist && !dist))
-        return MVSV_E_INVALID_ARG;
     const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     const double* R = Rm ? Rm : I3;
     // A = P[:, :3] * R; iR = A^-1
@@ -378,8 +382,6 @@ int mvsv_init_undistort_rectify_map(const double* K, const double* dist, int ndi
     const double k1 = k[0], k2 = k[1], p1 = k[2], p2 = k[3], k3 = k[4], k4 = k[5], k5 = k[6], k6 = k[7];
     const double u0 = K[2], v0 = K[5], fx = K[0], fy = K[4];
     for (int i = 0; i < H; i++) {
-        float* m1 = mx + (size_t)i * ms;
-        float* m2 = my + (size_t)i * ms;
         double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
         for (int j = 0; j < W; j++, _x += ir[0], _y += ir[3], _w += ir[6]) {
             const double w = 1. / _w, x = _x * w, y = _y * w;
@@ -388,9 +390,59 @@ int mvsv_init_undistort_rectify_map(const double* K, const double* dist, int ndi
             const double kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
             const double u = fx * (x * kr + p1 * _2xy + p2 * (r2 + 2 * x2)) + u0;
             const double v = fy * (y * kr + p1 * (r2 + 2 * y2) + p2 * _2xy) + v0;
-            m1[j] = (float)u;
-            m2[j] = (float)v;
+            emit(i, j, u, v);
         }
+    }
+    return MVSV_OK;
+}
+
+bool dist_ok(const double* dist, int ndist)
+{
+    return (ndist == 0 || ndist == 4 || ndist == 5 || ndist == 8) && (ndist == 0 || dist);
+}
+
+}  // namespace
+
+extern "C" {
+
+// CV_32FC1 output
+int mvsv_init_undistort_rectify_map(const double* K, const double* dist, int ndist,
+                                    const double* Rm, const double* P, int W, int H, float* mx,
+                                    float* my, size_t ms)
+{
+    if (!K || !P || !mx || !my || W <= 0 || H <= 0 || ms < (size_t)W || !dist_ok(dist, ndist))
+        return MVSV_E_INVALID_ARG;
+    return undistort_walk(K, dist, ndist, Rm, P, W, H, [&](int i, int j, double u, double v) {
+        mx[(size_t)i * ms + j] = (float)u;
+        my[(size_t)i * ms + j] = (float)v;
+    });
+}
+
+// [cv::undistort] (OpenCV 3.4 undistort.cpp): the maps of its stripes of
+// min(max(1, 4096 / W), H) rows -- initUndistortRectifyMap(K, dist, I, Ar with
+// Ar(1,2) = cy - y0, CV_16SC2) for the stripe starting at row y0 --, which come
+// straight from the doubles: iu = cvRound(u * 32) (half to even), xy = the plain
+// short casts of iu >> 5, iv >> 5 (not saturated), frac = (iv & 31) * 32 + (iu & 31).
+int mvsv_undistort_maps(const double* K, const double* dist, int ndist, const double* new_K, int W, int H,
+                        int16_t* xy, size_t xs, uint16_t* frac, size_t fs)
+{
+    if (!K || !xy || !frac || W <= 0 || H <= 0 || xs < (size_t)W || fs < (size_t)W || !dist_ok(dist, ndist))
+        return MVSV_E_INVALID_ARG;
+    const int stripe0 = std::min(std::max(1, (1 << 12) / W), H);
+    double Ar[9];
+    std::memcpy(Ar, new_K ? new_K : K, sizeof Ar);
+    const double cy = Ar[5];
+    for (int y0 = 0; y0 < H; y0 += stripe0) {
+        Ar[5] = cy - y0;
+        const int rc = undistort_walk(K, dist, ndist, nullptr, Ar, W, std::min(stripe0, H - y0),
+                                      [&](int i, int j, double u, double v) {
+                                          const int iu = (int)std::lrint(u * 32), iv = (int)std::lrint(v * 32);
+                                          int16_t* o = xy + 2 * ((size_t)(y0 + i) * xs + j);
+                                          o[0] = (int16_t)(iu >> 5);
+                                          o[1] = (int16_t)(iv >> 5);
+                                          frac[(size_t)(y0 + i) * fs + j] = (uint16_t)((iv & 31) * 32 + (iu & 31));
+                                      });
+        if (rc) return rc;
     }
     return MVSV_OK;
 }

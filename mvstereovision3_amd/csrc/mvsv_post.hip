@@ -537,16 +537,34 @@ __global__ __launch_bounds__(256) void remap_linear_kernel(
 // load, the 2x2 taps as bounds-checked gathers, one dword store where the
 // destination is 4-byte aligned (the row stride may be odd) and byte stores
 // otherwise and in the row's tail.
-__device__ __forceinline__ int rectify_px(const uint8_t* s, int sw, int sh, int sxy, int fr)
+__device__ __forceinline__ int rectify_px(const uint8_t* s, size_t ss, int sw, int sh, int sxy, int fr)
 {
     const int sx = (int)(short)(sxy & 0xffff), sy = sxy >> 16;
     const int ax = fr & 31, ay = fr >> 5;
     if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) return 0;
     const int w00 = (32 - ay) * (32 - ax) * 32, w01 = (32 - ay) * ax * 32;
     const int w10 = ay * (32 - ax) * 32, w11 = ay * ax * 32;
-    const int acc = remap_tap(s, sw, sw, sh, sx, sy) * w00 + remap_tap(s, sw, sw, sh, sx + 1, sy) * w01 +
-                    remap_tap(s, sw, sw, sh, sx, sy + 1) * w10 + remap_tap(s, sw, sw, sh, sx + 1, sy + 1) * w11;
+    const int acc = remap_tap(s, ss, sw, sh, sx, sy) * w00 + remap_tap(s, ss, sw, sh, sx + 1, sy) * w01 +
+                    remap_tap(s, ss, sw, sh, sx, sy + 1) * w10 + remap_tap(s, ss, sw, sh, sx + 1, sy + 1) * w11;
     return clampi((acc + (1 << 14)) >> 15, 0, 255);
+}
+
+// cv::remap with CV_16SC2 + CV_16UC1 maps (mvsv_remap_fixed_device): rectify_px on
+// strided views, one pixel per thread; xs in int16 pairs, fs in elements, any
+// 2-byte-aligned maps.  frac's bits above the 10 used ones are ignored, as
+// cv::remap masks them (INTER_TAB_SIZE2 - 1).
+__global__ __launch_bounds__(256) void remap_fixed_kernel(
+    const uint8_t* __restrict__ src, size_t ss, size_t sfs, int sw, int sh, const int16_t* __restrict__ xy, size_t xs,
+    const uint16_t* __restrict__ frac, size_t fs, uint8_t* __restrict__ dst, size_t ds, size_t dfs, int dw, int dh)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int f = blockIdx.z;
+    if (x >= dw || y >= dh) return;
+    const int16_t* p = xy + 2 * ((size_t)y * xs + x);
+    const int sxy = (int)(uint16_t)p[0] | (int)p[1] << 16;
+    dst[f * dfs + (size_t)y * ds + x] =
+        (uint8_t)rectify_px(src + f * sfs, ss, sw, sh, sxy, (int)(frac[(size_t)y * fs + x] & 1023u));
 }
 
 __global__ __launch_bounds__(256) void rectify_pair_kernel(
@@ -563,10 +581,10 @@ __global__ __launch_bounds__(256) void rectify_pair_kernel(
     const size_t m = ((size_t)side * dh + y) * ms + x;
     const int4 q = *reinterpret_cast<const int4*>(xy + 2 * m);
     const uint2 a = *reinterpret_cast<const uint2*>(frac + m);
-    const int v0 = rectify_px(s, sw, sh, q.x, (int)(a.x & 0xffffu));
-    const int v1 = rectify_px(s, sw, sh, q.y, (int)(a.x >> 16));
-    const int v2 = rectify_px(s, sw, sh, q.z, (int)(a.y & 0xffffu));
-    const int v3 = rectify_px(s, sw, sh, q.w, (int)(a.y >> 16));
+    const int v0 = rectify_px(s, sw, sw, sh, q.x, (int)(a.x & 0xffffu));
+    const int v1 = rectify_px(s, sw, sw, sh, q.y, (int)(a.x >> 16));
+    const int v2 = rectify_px(s, sw, sw, sh, q.z, (int)(a.y & 0xffffu));
+    const int v3 = rectify_px(s, sw, sw, sh, q.w, (int)(a.y >> 16));
     uint8_t* d = (side ? dR : dL) + f * dfs + (size_t)y * ds + x;
     if (x + 3 < dw && ((uintptr_t)d & 3) == 0) {
         *reinterpret_cast<uint32_t*>(d) = (uint32_t)v0 | (uint32_t)v1 << 8 | (uint32_t)v2 << 16 | (uint32_t)v3 << 24;
@@ -879,6 +897,135 @@ __global__ __launch_bounds__(64) void minmax_final_kernel(const int2* __restrict
         minmax[2 * blockIdx.x] = (int16_t)lo;
         minmax[2 * blockIdx.x + 1] = (int16_t)hi;
     }
+}
+
+// ---- focus measure: Utility::checkSharpness (src/utility.cpp:163-174) -----------------
+// S4 = sum over the ROI of |KX (*) s| + |KY (*) s| on the BORDER_REFLECT_101
+// extension s of the parent image, KX = (1,2,1)^T (-1,2,-1) = 4 Lx and
+// KY = (-1,2,-1)^T (1,2,1) = 4 Ly of the two cv::sepFilter2D calls: an exact
+// integer, at most 4080 a pixel (include/mvsv.h).
+//
+// A wave takes a work item: a strip of 256 columns (4 adjacent ones per lane) by
+// a band of kShBand ROI rows; it requests all kShBand + 2 rows at once and then
+// walks them with a three-row register window of the horizontal passes
+// m = (-1,2,-1) and g = (1,2,1).  Strips start
+// at xs <= roi x0 with row + xs 4-byte aligned in every row of every frame where
+// the strides allow (packed: one dword load per lane and row); lanes that cross
+// the image's border, and every lane otherwise, assemble their columns from byte
+// loads at reflected indices.  The two halo columns come from the neighbouring
+// lanes, for lanes 0 / 63 from one more byte load.  Only columns roi x0 - 1 ..
+// x1 and rows y0 - 1 .. y1 (reflected into the parent) are needed; nothing
+// outside [row, row + W) of a parent row is read.
+constexpr int kShBand = 8;       // ROI rows per work item (2 halo rows on top: 1/4 more row reads, mostly L2 hits)
+constexpr int kShBlocks = 1024;  // partial sums per frame at most
+
+__device__ __forceinline__ int reflect101(int i, int n) { return n == 1 ? 0 : i < 0 ? -i : i >= n ? 2 * n - 2 - i : i; }
+
+struct ShRaw {  // a lane's part of one parent row: 4 columns packed, the halo columns beside them
+    uint32_t w;
+    int left, right;
+};
+
+__device__ __forceinline__ ShRaw sharp_load(const uint8_t* __restrict__ r, int W, int c0, int lo, int hi, bool packed,
+                                            int lane)
+{
+    ShRaw q;
+    if (packed && c0 >= 0 && c0 + 3 < W) {
+        q.w = *reinterpret_cast<const uint32_t*>(r + c0);
+    } else {
+        q.w = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int c = c0 + k;
+            if (c >= lo && c <= hi) q.w |= (uint32_t)r[reflect101(c, W)] << (8 * k);
+        }
+    }
+    q.left = q.right = 0;
+    if (lane == 0 && c0 - 1 >= lo && c0 - 1 <= hi) q.left = r[reflect101(c0 - 1, W)];
+    if (lane == 63 && c0 + 4 >= lo && c0 + 4 <= hi) q.right = r[reflect101(c0 + 4, W)];
+    return q;
+}
+
+// the horizontal passes of a lane's 4 columns: m = 2 p - l - r, g = 2 p + l + r
+__device__ __forceinline__ void sharp_hpass(const ShRaw& q, int lane, int* m, int* g)
+{
+    const int up = __shfl_up((int)(q.w >> 24), 1), dn = __shfl_down((int)(q.w & 0xffu), 1);
+    int p[6];
+    p[0] = lane == 0 ? q.left : up;
+    p[1] = (int)(q.w & 0xffu);
+    p[2] = (int)((q.w >> 8) & 0xffu);
+    p[3] = (int)((q.w >> 16) & 0xffu);
+    p[4] = (int)(q.w >> 24);
+    p[5] = lane == 63 ? q.right : dn;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        m[k] = 2 * p[k + 1] - p[k] - p[k + 2];
+        g[k] = 2 * p[k + 1] + p[k] + p[k + 2];
+    }
+}
+
+// One 64-bit partial per block, written unconditionally: no atomics, no init
+// pass, the same partials on every run (integer sums do not depend on order).
+__global__ __launch_bounds__(256) void sharpness_kernel(const uint8_t* __restrict__ img, size_t st, size_t fs, int W,
+                                                        int H, int x0, int y0, int x1, int y1, int xs, int packed,
+                                                        int nstrips, int nbands,
+                                                        unsigned long long* __restrict__ partials)
+{
+    __shared__ unsigned long long s_sum[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, f = blockIdx.y;
+    const uint8_t* im = img + f * fs;
+    const int lo = x0 - 1, hi = x1;
+    unsigned long long total = 0;
+    for (int it = blockIdx.x * 4 + w; it < nstrips * nbands; it += gridDim.x * 4) {
+        const int strip = it % nstrips, band = it / nstrips;
+        const int c0 = xs + strip * 256 + lane * 4;
+        const int yb = y0 + band * kShBand, ye = min(yb + kShBand, y1);
+        bool own[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) own[k] = c0 + k >= x0 && c0 + k < x1;
+        // every row of the band is requested before the first is summed; rows past a short
+        // band's end repeat its last halo row and are not summed
+        ShRaw raw[kShBand + 2];
+#pragma unroll
+        for (int i = 0; i < kShBand + 2; i++)
+            raw[i] = sharp_load(im + (size_t)reflect101(min(yb - 1 + i, ye), H) * st, W, c0, lo, hi, packed, lane);
+        int am[4], ag[4], bm[4], bg[4], cm[4], cg[4];
+        sharp_hpass(raw[0], lane, am, ag);
+        sharp_hpass(raw[1], lane, bm, bg);
+        uint32_t acc = 0;  // at most 4 * kShBand * 4080
+#pragma unroll
+        for (int i = 0; i < kShBand; i++) {
+            sharp_hpass(raw[i + 2], lane, cm, cg);
+            const bool row = yb + i < ye;  // wave-uniform
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int v = abs(am[k] + 2 * bm[k] + cm[k]) + abs(2 * bg[k] - ag[k] - cg[k]);
+                acc += row && own[k] ? (uint32_t)v : 0u;
+                am[k] = bm[k];
+                ag[k] = bg[k];
+                bm[k] = cm[k];
+                bg[k] = cg[k];
+            }
+        }
+        total += acc;
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) total += __shfl_down(total, o);
+    if (lane == 0) s_sum[w] = total;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partials[(size_t)f * gridDim.x + blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+}
+
+// a frame's nblk partials folded by one wave into sums[f * ss]
+__global__ __launch_bounds__(64) void sharpness_fold_kernel(const unsigned long long* __restrict__ partials, int nblk,
+                                                            int64_t* __restrict__ sums, size_t ss)
+{
+    unsigned long long t = 0;
+    for (int i = threadIdx.x; i < nblk; i += 64) t += partials[(size_t)blockIdx.x * nblk + i];
+#pragma unroll
+    for (int o = 32; o; o >>= 1) t += __shfl_down(t, o);
+    if (threadIdx.x == 0) sums[(size_t)blockIdx.x * ss] = (int64_t)t;
 }
 
 // OpenCV 3.4's arithmetic (normalize -> Mat::convertTo, CV_16S -> CV_8U, SSE2 /
@@ -1324,6 +1471,37 @@ int normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st
                        (const int2*)ctx->mm_part.ptr, nblk, std::min(alpha, beta), std::max(alpha, beta), out, os,
                        ofs, store_w, minmax);
     return check_hip(ctx, hipGetLastError(), "normalize");
+}
+
+int sharpness_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t st, size_t fs, int W, int H, const mvsv_rect& q,
+                     int64_t* sums, size_t ss)
+{
+    // strips start where a row is 4-byte aligned: row strides and frame stride multiples of 4
+    const bool packed = st % 4 == 0 && (n == 1 || fs % 4 == 0);
+    const int xs = packed ? q.x0 - (int)(((uintptr_t)img + q.x0) & 3) : q.x0;
+    const int nstrips = (q.x1 - xs + 255) / 256, nbands = (q.y1 - q.y0 + kShBand - 1) / kShBand;
+    const int nblk = (int)std::min<long>(kShBlocks, ((long)nstrips * nbands + 3) / 4);
+    int rc;
+    // room for 16 frames at least: the usual batches never grow (and so never synchronise) it
+    if ((rc = ensure(ctx, ctx->sh_part, (size_t)std::max(n, 16) * kShBlocks * sizeof(unsigned long long),
+                     "sharpness partials")))
+        return rc;
+    unsigned long long* part = (unsigned long long*)ctx->sh_part.ptr;
+    hipLaunchKernelGGL(sharpness_kernel, dim3(nblk, n), dim3(256), 0, ctx->stream, img, st, fs, W, H, q.x0, q.y0, q.x1,
+                       q.y1, xs, packed ? 1 : 0, nstrips, nbands, part);
+    hipLaunchKernelGGL(sharpness_fold_kernel, dim3(n), dim3(64), 0, ctx->stream, (const unsigned long long*)part, nblk,
+                       sums, ss);
+    return check_hip(ctx, hipGetLastError(), "sharpness");
+}
+
+int remap_fixed_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh,
+                       const int16_t* xy, size_t xs, const uint16_t* frac, size_t fs, uint8_t* dst, size_t ds,
+                       size_t dfs, int dw, int dh)
+{
+    dim3 grid((dw + 63) / 64, (dh + 3) / 4, n);
+    hipLaunchKernelGGL(remap_fixed_kernel, grid, dim3(256), 0, ctx->stream, src, ss, sfs, sw, sh, xy, xs, frac, fs,
+                       dst, ds, dfs, dw, dh);
+    return check_hip(ctx, hipGetLastError(), "remap fixed");
 }
 
 int remap_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh,

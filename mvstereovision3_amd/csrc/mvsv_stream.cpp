@@ -18,6 +18,10 @@
 // that ends the detector loops' key handler, trgt/demo.cpp:394) is compacted after
 // them into a device ring; only its (count, min, max) come back with the frame and
 // front_cloud copies the records that exist on demand.
+// With mvsv_stream_enable_sharpness, the focus measure of the pushed pair
+// (Utility::checkSharpness, what trgt/liveView.cpp prints; on a raw stream the raw
+// camera pair) is summed on the same device stream and its two int64 sums come back
+// with the frame (front_sharpness).
 // With mvsv_stream_set_batch(b), pushed frames are computed b at a time: the
 // slots' device buffers are one contiguous [depth][frame] array, so a group of
 // consecutive slots is one frame-batch launch (sustained rate of the batch
@@ -223,7 +227,22 @@ struct mvsv_stream {
     int* dCloudHdr = nullptr;            // [depth][3] (count, min, max)
     int* hCloudHdr = nullptr;            // pinned, [depth][3]
     hipStream_t cloud_copy = nullptr;    // front_cloud's copies: not behind the later frames' downloads
+    // the focus measure of every pushed pair (mvsv_stream_enable_sharpness): S4 of
+    // sharp_roi[0] of the left and sharp_roi[1] of the right pushed image per slot
+    bool sharp = false;
+    mvsv_rect sharp_roi[2] = {};
+    int64_t* dSharp = nullptr;  // [depth][2]
+    int64_t* hSharp = nullptr;  // pinned, [depth][2]
 };
+
+static void sharpness_free(mvsv_stream* st)
+{
+    if (st->dSharp) (void)hipFree(st->dSharp);
+    if (st->hSharp) (void)hipHostFree(st->hSharp);
+    st->dSharp = nullptr;
+    st->hSharp = nullptr;
+    st->sharp = false;
+}
 
 static void cloud_free(mvsv_stream* st)
 {
@@ -294,6 +313,7 @@ static void stream_free(mvsv_stream* st)
     samplepoints_free(st);
     display_free(st);
     cloud_free(st);
+    sharpness_free(st);
     if (st->rep) (void)hipHostFree(st->rep);
     if (st->up) (void)hipStreamDestroy(st->up);
     if (st->down) (void)hipStreamDestroy(st->down);
@@ -534,6 +554,17 @@ static int stream_launch(mvsv_stream* st)
                                         st->cloud_Q, st->dCloud + (size_t)i0 * st->cloud_max, st->cloud_max,
                                         st->dCloudHdr + 3 * i0, 3, st->dCloudHdr + 3 * i0 + 1, 3);
         }
+        if (status == MVSV_OK && st->sharp) {
+            // the pushed pair: a raw slot holds it as [2][rawH][rawW]
+            const int iw = st->raw ? st->rawW : W, ih = st->raw ? st->rawH : H;
+            const size_t ipx = (size_t)iw * ih;
+            const uint8_t* pl = st->raw ? first.dRaw : first.dL;
+            const uint8_t* pr = st->raw ? first.dRaw + ipx : first.dR;
+            const size_t ifs = st->raw ? 2 * ipx : ipx;
+            status = sharpness_device(ctx, n, pl, iw, ifs, iw, ih, st->sharp_roi[0], st->dSharp + 2 * i0, 2);
+            if (status == MVSV_OK)
+                status = sharpness_device(ctx, n, pr, iw, ifs, iw, ih, st->sharp_roi[1], st->dSharp + 2 * i0 + 1, 2);
+        }
         if (status != MVSV_OK && ctx != st->ctx) st->ctx->err = ctx->err;  // reported by pop
         st->runs++;
         if ((rc = mark_last_use(ctx, MVSV_OK)) ||
@@ -583,6 +614,10 @@ static int stream_launch(mvsv_stream* st)
             if (st->cloud &&  // the header only: the records wait on the device for front_cloud
                 (rc = check_hip(c, hipMemcpyAsync(st->hCloudHdr + 3 * (i0 + k), st->dCloudHdr + 3 * (i0 + k),
                                                   3 * sizeof(int), hipMemcpyDeviceToHost, st->down), "stream D2H")))
+                return rc;
+            if (st->sharp &&
+                (rc = check_hip(c, hipMemcpyAsync(st->hSharp + 2 * (i0 + k), st->dSharp + 2 * (i0 + k),
+                                                  2 * sizeof(int64_t), hipMemcpyDeviceToHost, st->down), "stream D2H")))
                 return rc;
             if ((rc = check_hip(c, hipEventRecord(s.done, st->down), "stream event"))) return rc;
         }
@@ -986,6 +1021,73 @@ int mvsv_stream_front_display_view(mvsv_stream* st, const uint8_t** map, int16_t
     if ((rc = display_front(st, &idx))) return rc;
     *map = st->disp_map(idx);
     if (minmax) std::memcpy(minmax, st->disp_minmax(idx), 2 * sizeof(int16_t));
+    return MVSV_OK;
+}
+
+int mvsv_stream_disable_sharpness(mvsv_stream* st)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (st->head != st->tail)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the sharpness changes only while no frame is pending");
+    DeviceGuard dev_guard(st->ctx->device);
+    sharpness_free(st);  // every frame was popped: nothing in flight uses the buffers
+    return MVSV_OK;
+}
+
+int mvsv_stream_enable_sharpness(mvsv_stream* st, const mvsv_rect* roi_left, const mvsv_rect* roi_right)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (st->head != st->tail)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "the sharpness changes only while no frame is pending");
+    // the pushed images' size
+    const int iw = st->raw ? st->rawW : st->W, ih = st->raw ? st->rawH : st->H;
+    const mvsv_rect* rois[2] = {roi_left, roi_right};
+    mvsv_rect q[2];
+    for (int i = 0; i < 2; i++) {
+        q[i] = rois[i] ? *rois[i] : mvsv_rect{0, 0, iw, ih};
+        if (q[i].x0 < 0 || q[i].y0 < 0 || q[i].x1 > iw || q[i].y1 > ih || q[i].x1 <= q[i].x0 || q[i].y1 <= q[i].y0)
+            return set_error(ctx, MVSV_E_INVALID_ARG, "sharpness ROI empty or outside the pushed image");
+    }
+    DeviceGuard dev_guard(ctx->device);
+    sharpness_free(st);
+    st->sharp_roi[0] = q[0];
+    st->sharp_roi[1] = q[1];
+    const size_t bytes = st->slots.size() * 2 * sizeof(int64_t);
+    const bool ok = hipMalloc((void**)&st->dSharp, bytes) == hipSuccess &&
+                    hipHostMalloc((void**)&st->hSharp, bytes, hipHostMallocDefault) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        sharpness_free(st);
+        return set_error(ctx, MVSV_E_OOM, "sharpness buffer allocation failed");
+    }
+    st->sharp = true;
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_sharpness(mvsv_stream* st, double value[2], int64_t sum4[2])
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (!st->sharp) return set_error(ctx, MVSV_E_INVALID_ARG, "the sharpness is not enabled on this stream");
+    if (st->head == st->tail) return set_error(ctx, MVSV_E_INVALID_ARG, "stream empty");
+    DeviceGuard dev_guard(ctx->device);
+    const long idx = st->tail % (long)st->slots.size();
+    auto& s = st->slots[idx];
+    int rc;
+    if (st->tail >= st->launched && (rc = stream_launch(st))) return rc;  // partial group
+    if ((rc = check_hip(ctx, hipEventSynchronize(s.done), "stream sync"))) return rc;
+    if (s.status) return s.status;
+    // the report word is left for pop to read and clear
+    if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[idx], __ATOMIC_ACQUIRE) != 0))
+        return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
+    for (int i = 0; i < 2; i++) {
+        const mvsv_rect& q = st->sharp_roi[i];
+        const int64_t s4 = st->hSharp[2 * idx + i];
+        if (sum4) sum4[i] = s4;
+        // cv::mean: sum * (1.0 / N), a reciprocal and a product, each rounded
+        if (value) value[i] = ((double)s4 / 4.0) * (1.0 / ((double)(q.x1 - q.x0) * (double)(q.y1 - q.y0)));
+    }
     return MVSV_OK;
 }
 

@@ -748,6 +748,32 @@ class DisparityStream:
             return rec, count.value, (int(mm[0]), int(mm[1]))
         return rec, count.value
 
+    def enable_sharpness(self, roi_left=None, roi_right=None):
+        """Utility::checkSharpness of every pushed pair from now on, each side over
+        its own roi = (x0, y0, x1, y1) (default: the whole image), on the device
+        beside the frame's other passes (mvsv_stream_enable_sharpness); only while
+        no frame is pending.  The pushed images are measured: on a raw stream the
+        raw camera pair, as trgt/liveView.cpp measures what getImagepair returned."""
+        self._live()
+        rl = Rect(*(int(v) for v in roi_left)) if roi_left is not None else None
+        rr = Rect(*(int(v) for v in roi_right)) if roi_right is not None else None
+        check(lib().mvsv_stream_enable_sharpness(self._h, ctypes.byref(rl) if rl is not None else None,
+                                                 ctypes.byref(rr) if rr is not None else None), self._ctx.handle)
+
+    def disable_sharpness(self):
+        self._live()
+        check(lib().mvsv_stream_disable_sharpness(self._h), self._ctx.handle)
+
+    def front_sharpness(self, return_sums=False):
+        """(left, right) focus values of the oldest pending frame, which stays
+        pending (pop it afterwards); return_sums: also the exact integer sums S4."""
+        self._live()
+        values = np.zeros(2, np.float64)
+        sums = np.zeros(2, np.int64)
+        check(lib().mvsv_stream_front_sharpness(self._h, values.ctypes.data, sums.ctypes.data), self._ctx.handle)
+        v = (float(values[0]), float(values[1]))
+        return (v, (int(sums[0]), int(sums[1]))) if return_sums else v
+
     @staticmethod
     def _display_view_released(stream):
         with stream._views_lock:

@@ -160,3 +160,85 @@ def resize(src, fx, fy=None):
     check(lib().mvsv_resize(ctx.handle, a.ctypes.data, sw, sw, sh, float(fx), float(fy),
                             out.ctypes.data, dw), ctx.handle)
     return out
+
+
+def undistort_maps(K, dist, size, new_K=None):
+    """The CV_16SC2 + CV_16UC1 maps cv::undistort(src, dst, K, dist[, new_K]) builds
+    stripe by stripe (mvsv_undistort_maps, host only): (xy int16 (H, W, 2),
+    frac uint16 (H, W)) for size = (w, h); dist None or empty: no distortion."""
+    w, h = (int(v) for v in size)
+    K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))
+    d = np.ascontiguousarray(np.asarray(dist if dist is not None else [], np.float64).reshape(-1))
+    nk = None if new_K is None else np.ascontiguousarray(np.asarray(new_K, np.float64).reshape(3, 3))
+    if w <= 0 or h <= 0:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "undistort_maps: empty size")
+    xy = np.empty((h, w, 2), np.int16)
+    frac = np.empty((h, w), np.uint16)
+    check(lib().mvsv_undistort_maps(K.ctypes.data, d.ctypes.data if d.size else None, int(d.size),
+                                    nk.ctypes.data if nk is not None else None, w, h, xy.ctypes.data, w,
+                                    frac.ctypes.data, w))
+    return xy, frac
+
+
+def remap_fixed(src, xy, frac):
+    """cv::remap(src, dst, xy, frac, INTER_LINEAR) with CV_16SC2 + CV_16UC1 maps for
+    uint8 device tensors (mvsv_remap_fixed_device): pure integer, bit-exact.
+
+    src: (H, W) or (N, H, W) uint8 device tensor, any view with unit column stride;
+    xy: int16 device tensor (h, w, 2), frac: uint16 / int16 device tensor (h, w) (rows
+    may be strided).  Returns uint8 (..., h, w)."""
+    import torch
+    if not (type(src).__module__.startswith("torch") and src.is_cuda and src.dtype == torch.uint8 and
+            src.dim() in (2, 3)):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "remap_fixed: uint8 device tensor expected")
+    if not (xy.is_cuda and xy.dtype == torch.int16 and xy.dim() == 3 and xy.shape[2] == 2 and
+            frac.is_cuda and frac.element_size() == 2 and frac.dim() == 2 and frac.shape == xy.shape[:2]):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "remap_fixed: int16 (h, w, 2) and 16-bit (h, w) device maps expected")
+    if xy.stride(2) != 1 or xy.stride(1) != 2 or xy.stride(0) % 2:
+        xy = xy.contiguous()
+    if frac.stride(1) != 1:
+        frac = frac.contiguous()
+    batched = src.dim() == 3
+    s = src if batched else src.unsqueeze(0)
+    if s.stride(2) != 1:
+        s = s.contiguous()
+    n, sh, sw = s.shape
+    dh, dw = frac.shape
+    out = torch.empty((n, dh, dw), dtype=torch.uint8, device=src.device)
+    ctx = context(src.device.index or 0)
+    check(lib().mvsv_set_stream(ctx.handle,
+                                ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)),
+          ctx.handle)
+    check(lib().mvsv_remap_fixed_device(ctx.handle, n, s.data_ptr(), s.stride(1), s.stride(0), sw, sh,
+                                        xy.data_ptr(), xy.stride(0) // 2, frac.data_ptr(), frac.stride(0),
+                                        out.data_ptr(), dw, dh * dw, dw, dh), ctx.handle)
+    return out if batched else out[0]
+
+
+def undistort_pair(left, right, K_left, dist_left, K_right, dist_right, out=None):
+    """Stereosystem::getUndistortedImagepair on host images (mvsv_undistort_pair):
+    cv::undistort of each side with its camera matrix and distortion coefficients.
+    out = (left, right) arrays to write into -- the inputs themselves are allowed."""
+    L, R = np.asarray(left), np.asarray(right)
+    if L.ndim != 2 or L.shape != R.shape or L.dtype != np.uint8 or R.dtype != np.uint8 or L.size == 0:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "undistort_pair: two uint8 images of one size expected")
+    if L.strides[1] != 1:
+        L = np.ascontiguousarray(L)
+    if R.strides[1] != 1:
+        R = np.ascontiguousarray(R)
+    H, W = L.shape
+    oL, oR = (np.empty((H, W), np.uint8), np.empty((H, W), np.uint8)) if out is None else out
+    for o in (oL, oR):
+        if not (isinstance(o, np.ndarray) and o.dtype == np.uint8 and o.shape == (H, W) and o.strides[1] == 1):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "undistort_pair: out must be uint8 arrays of the images' shape")
+    KL = np.ascontiguousarray(np.asarray(K_left, np.float64).reshape(3, 3))
+    KR = np.ascontiguousarray(np.asarray(K_right, np.float64).reshape(3, 3))
+    dl = np.ascontiguousarray(np.asarray(dist_left if dist_left is not None else [], np.float64).reshape(-1))
+    dr = np.ascontiguousarray(np.asarray(dist_right if dist_right is not None else [], np.float64).reshape(-1))
+    ctx = context(0)
+    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    check(lib().mvsv_undistort_pair(ctx.handle, L.ctypes.data, L.strides[0], R.ctypes.data, R.strides[0], W, H,
+                                    KL.ctypes.data, dl.ctypes.data if dl.size else None, int(dl.size),
+                                    KR.ctypes.data, dr.ctypes.data if dr.size else None, int(dr.size),
+                                    oL.ctypes.data, oL.strides[0], oR.ctypes.data, oR.strides[0]), ctx.handle)
+    return oL, oR

@@ -120,6 +120,78 @@ class Utility:
             raise MvsvError(_lib.MVSV_E_INVALID_ARG, "calcMinMaxDisparity: no positive value")
         return int(v.min()), int(v.max())
 
+    @staticmethod
+    def checkSharpness(src, roi=None) -> float:
+        """src/utility.cpp:163-174: cv::mean(|Lx| + |Ly|) of the two cv::sepFilter2D
+        responses, computed on the GPU (mvsv_sharpness).  src: a uint8 image, a numpy
+        array or a device tensor (H, W).  roi = (x0, y0, x1, y1) stands for the
+        reference's view src(viewArea): its 1-pixel halo comes from src, as OpenCV's
+        filter engine takes it from a view's parent image."""
+        if (src.dim() if type(src).__module__.startswith("torch") else np.asarray(src).ndim) != 2:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "checkSharpness: a 2-D uint8 image expected")
+        return float(sharpness(src, roi))
+
+
+def _rect(roi):
+    return _lib.Rect(*(int(v) for v in roi)) if roi is not None else None
+
+
+def sharpness_value(sum4, n_pixels) -> float:
+    """The double cv::mean returns for the integer sum S4 over n_pixels pixels:
+    (S4 / 4.0) * (1.0 / N), a reciprocal and a product, each rounded."""
+    return (float(int(sum4)) / 4.0) * (1.0 / float(int(n_pixels)))
+
+
+def sharpness(frames, roi=None, return_sums=False):
+    """Utility::checkSharpness of one uint8 image (H, W) or a batch (N, H, W), all
+    over the same roi = (x0, y0, x1, y1) (default: the whole image), on the GPU.
+
+    A torch device tensor (any view with unit column stride) is measured where it
+    is, asynchronously up to the read-back of the N sums; a numpy array goes
+    through mvsv_sharpness frame by frame.  Returns a float, or a float64 array
+    (N,) for a batch; return_sums: also the exact integer sums S4 (int, or int64
+    array), with value = (S4 / 4.0) * (1.0 / roi pixels)."""
+    r = _rect(roi)
+    if type(frames).__module__.startswith("torch"):
+        import torch
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (2, 3)):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "sharpness: 2-D or 3-D uint8 device tensor expected")
+        batched = frames.dim() == 3
+        d = frames if batched else frames.unsqueeze(0)
+        if d.stride(2) != 1:
+            d = d.contiguous()
+        n, H, W = d.shape
+        ctx = context(frames.device.index or 0)
+        check(lib().mvsv_set_stream(ctx.handle,
+                                    ctypes.c_void_p(torch.cuda.current_stream(frames.device).cuda_stream)),
+              ctx.handle)
+        out = torch.empty((n,), dtype=torch.int64, device=frames.device)
+        check(lib().mvsv_sharpness_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
+                                          ctypes.byref(r) if r is not None else None, out.data_ptr()), ctx.handle)
+        sums = out.cpu().numpy()
+    else:
+        a = np.asarray(frames)
+        if a.ndim not in (2, 3) or a.dtype != np.uint8:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "sharpness: 2-D or 3-D uint8 image expected")
+        if a.strides[-1] != 1:
+            a = np.ascontiguousarray(a)
+        batched = a.ndim == 3
+        H, W = a.shape[-2:]
+        ctx = context(0)
+        check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+        sums = np.empty(len(a) if batched else 1, np.int64)
+        for i, f in enumerate(a if batched else a[None]):
+            s4 = ctypes.c_int64(0)
+            check(lib().mvsv_sharpness(ctx.handle, f.ctypes.data, f.strides[0], W, H,
+                                       ctypes.byref(r) if r is not None else None, None, ctypes.byref(s4)),
+                  ctx.handle)
+            sums[i] = s4.value
+    npx = W * H if r is None else (r.x1 - r.x0) * (r.y1 - r.y0)
+    values = np.array([sharpness_value(s, npx) for s in sums], np.float64)
+    if not batched:
+        return (float(values[0]), int(sums[0])) if return_sums else float(values[0])
+    return (values, sums) if return_sums else values
+
 
 def reproject(dmap, Q):
     """Utility::calcCoordinate for every pixel of an int16 device map, on the GPU.
