@@ -35,6 +35,11 @@
  *   mvsv_minmax_device                Utility::calcMinMaxDisparity src/utility.cpp:287-304
  *   mvsv_stream_enable_display /      the display map with every frame of a stream
  *   _front_display(_view)             (trgt/liveDisparity.cpp:88-95)
+ *   mvsv_view(_device) / _view_draw   the annotated frame of the detection programs: normalize,
+ *                                     cvtColor(GRAY2BGR), View::drawSubimageGrid / drawObstacleGrid
+ *                                     (src/view.cpp), drawFoundObstacles (trgt/demo.cpp:116-128,280-298)
+ *   mvsv_stream_enable_view /         that frame with every frame of a stream
+ *   _front_view(_view)
  *   mvsv_stream_*                     the disparity worker thread + main loop of
  *                                     trgt/mean_test.cpp:61-70,258-318 (condvar
  *                                     hand-off, Disparity::sgbm, build(MEAN_VALUE))
@@ -397,6 +402,74 @@ MVSV_API int mvsv_normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* d
 MVSV_API int mvsv_normalize_minmax(mvsv_ctx* ctx, const int16_t* dmap, size_t stride, int width, int height,
                                    double alpha, double beta, uint8_t* out, size_t out_stride, int16_t* minmax);
 
+/* ---- detection view: the annotated BGR frame of the detection programs ------------
+ * What trgt/demo.cpp:280-298 (and mean_test, sample_test, obstacle, ...) show per
+ * frame: cv::normalize(NORM_MINMAX, CV_8U), cv::cvtColor(GRAY2BGR), View's grids
+ * (src/view.cpp) and drawFoundObstacles, in one device pass.  The view of a
+ * width x height map (both >= 9) is uint8 [height][width][3] in B, G, R order.
+ * Every pixel starts as its display byte in all three channels (exactly what
+ * mvsv_normalize_minmax_device writes for alpha, beta); then the layers of
+ * `layers` are drawn in this order, each over everything before it, all
+ * relative to the view and clipped to it (a restatement of OpenCV 3.4's
+ * cv::line, filled cv::rectangle and filled cv::circle, thickness 1, no
+ * antialiasing):
+ *   SUBIMAGE_GRID  View::drawSubimageGrid: colour (100, 0, 0), whole columns
+ *                  (width / 9) * k and whole rows (height / 9) * k, k in {1, 2, 4, 5, 7, 8}
+ *   OBSTACLE_GRID  View::drawObstacleGrid: colour (0, 0, 255), columns width / 3
+ *                  and 2 * (width / 3), rows height / 3 and 2 * (height / 3)
+ *   FOUND_TILES    drawFoundObstacles(Subimage): tile (c, r), index r * 9 + c, is
+ *                  found when means[i] < tile_first && means[i] > tile_second
+ *                  (float compares, MeanDisparityDetection::detectObstacles) and
+ *                  paints (0, 0, 255) on c * dx <= x <= c * dx + dx,
+ *                  r * dy <= y <= r * dy + dy with dx = width / 9, dy = height / 9:
+ *                  both corners included, as a filled cv::rectangle does
+ *   FOUND_POINTS   drawFoundObstacles(Samplepoint): a lattice point of
+ *                  mvsv_samplepoint_layout(width, height) is found when
+ *                  values[i] < point_first && values[i] > point_second and paints
+ *                  cv::circle(centre, point_radius, (0, 0, 255), -1); the
+ *                  reference's radius is 3, accepted are 0..3 (lattice steps are
+ *                  >= 8, so circles neither overlap nor leave the view).  A map
+ *                  without lattice points has no circles.
+ * A NaN or infinite range bound is valid: the compares decide. */
+enum {
+    MVSV_VIEW_SUBIMAGE_GRID = 1,
+    MVSV_VIEW_OBSTACLE_GRID = 2,
+    MVSV_VIEW_FOUND_TILES = 4,
+    MVSV_VIEW_FOUND_POINTS = 8
+};
+typedef struct {
+    int layers;                      /* MVSV_VIEW_* bits */
+    double alpha, beta;              /* as mvsv_normalize_minmax; finite */
+    const float* means;              /* [n][81], needed by FOUND_TILES */
+    float tile_first, tile_second;
+    const float* values;             /* [n][nx * ny], needed by FOUND_POINTS */
+    float point_first, point_second;
+    int point_radius;                /* 0..3 */
+} mvsv_view_spec;
+/* dmap as for mvsv_normalize_minmax_device (any 2-byte-aligned view, packed
+ * 16-byte loads where the strides allow); out: n images (device pointer, strides
+ * in bytes, any alignment, out_stride >= 3 * width) -- no byte outside
+ * [row, row + 3 * width) is touched; the store width (16, 8, 4, 2 or 1 bytes)
+ * follows the alignment of out and its strides, the bytes are the same; dense
+ * 16-byte-aligned images are the fast case.  FOUND_POINTS needs width < 2^20.
+ * spec->means / values: device
+ * pointers, frames back to back.  minmax: device pointer, [n][2] (smin, smax), or
+ * NULL.  Asynchronous on the context's stream.  Unknown layer bits, a layer
+ * whose pointer is NULL, a radius outside 0..3, a non-finite alpha / beta,
+ * width or height < 9, or out_stride < 3 * width: MVSV_E_INVALID_ARG before any
+ * launch. */
+MVSV_API int mvsv_view_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t stride, size_t frame_stride,
+                              int width, int height, const mvsv_view_spec* spec, uint8_t* out, size_t out_stride,
+                              size_t out_frame_stride, int16_t* minmax);
+/* Same for one host map into a host image (synchronous); spec->means / values
+ * are host pointers, minmax: 2 int16 on the host, or NULL. */
+MVSV_API int mvsv_view(mvsv_ctx* ctx, const int16_t* dmap, size_t stride, int width, int height,
+                       const mvsv_view_spec* spec, uint8_t* out, size_t out_stride, int16_t* minmax);
+/* The layers alone, painted over an existing host BGR image the way View::draw*Grid
+ * and drawFoundObstacles do it (one after the other; alpha / beta play no part but
+ * must be finite).  Host only, no device needed; the same argument rules. */
+MVSV_API int mvsv_view_draw(uint8_t* bgr, size_t stride, int width, int height, const mvsv_view_spec* spec);
+
 /* ---- frame stream ------------------------------------------
  * A camera loop pushes rectified pairs from host memory and pops int16 maps in
  * push order.  Up to `depth` frames are in flight: the upload of one frame, the
@@ -519,6 +592,28 @@ MVSV_API int mvsv_stream_front_display(mvsv_stream* s, uint8_t* out, size_t out_
 /* Same without the copy: *map points at the frame's dense map (stride = roi
  * width) in the stream's pinned slot, valid until the next push. */
 MVSV_API int mvsv_stream_front_display_view(mvsv_stream* s, const uint8_t** map, int16_t* minmax);
+
+/* The detection view in the stream (either kind): every frame's mvsv_view_device
+ * over roi (NULL: the whole map; at least 9 x 9) is computed after the frame's
+ * mean grid and lattice passes and comes back with the frame, in buffers of its
+ * own (independent of the display).  spec's layers, alpha, beta, tile range and
+ * point_radius are used; its means / values pointers and point range are ignored:
+ *   FOUND_TILES   needs a stream created with a grid_roi equal to roi; the means
+ *                 are the frame's own, on the device
+ *   FOUND_POINTS  needs mvsv_stream_enable_samplepoints with the same ROI; its
+ *                 range and the frame's device values are used.  While the view
+ *                 uses them, mvsv_stream_disable_samplepoints and a change of
+ *                 their ROI are refused.
+ * Allowed only while no frame is pending; a second call replaces the first.
+ * MVSV_E_INVALID_ARG with a message otherwise. */
+MVSV_API int mvsv_stream_enable_view(mvsv_stream* s, const mvsv_rect* roi, const mvsv_view_spec* spec);
+MVSV_API int mvsv_stream_disable_view(mvsv_stream* s);
+/* As mvsv_stream_front_display: the oldest pending frame's view (roi height rows of
+ * 3 * roi width bytes, out_stride bytes apart) and minmax[2], without popping. */
+MVSV_API int mvsv_stream_front_view(mvsv_stream* s, uint8_t* out, size_t out_stride, int16_t* minmax);
+/* Same without the copy: *view points at the frame's dense image (stride = 3 * roi
+ * width) in the stream's pinned slot, valid until the next push. */
+MVSV_API int mvsv_stream_front_view_view(mvsv_stream* s, const uint8_t** view, int16_t* minmax);
 
 /* The point cloud in the stream (either kind): every frame's
  * mvsv_point_cloud_device of dMap(roi) is computed after its SGBM on the same

@@ -97,6 +97,26 @@ inline void normalize(const Mat& dMap, Mat& out, double alpha = 0, double beta =
                                 alpha, beta, out.data, out.step, minmax),
           c);
 }
+// The frame the detection programs show (trgt/demo.cpp:280-298): normalize,
+// cv::cvtColor(GRAY2BGR), View's grids and drawFoundObstacles in one device pass
+// (mvsv_view).  out: CV_8UC3, B, G, R.  layers: MVSV_VIEW_* bits; means81 and
+// meanRange (MeanDisparityDetection's means and mRangeDisparity) for
+// MVSV_VIEW_FOUND_TILES, values and sampleRange (SamplepointDetection's) for
+// MVSV_VIEW_FOUND_POINTS.
+inline void detectionView(const Mat& dMap, Mat& out, int layers, const float* means81 = nullptr,
+                          std::pair<float, float> meanRange = {0.0f, 0.0f}, const float* values = nullptr,
+                          std::pair<float, float> sampleRange = {0.0f, 0.0f}, int pointRadius = 3, double alpha = 0,
+                          double beta = 255, int16_t* minmax = nullptr)
+{
+    if (dMap.type != MAT_16SC1 || dMap.empty()) throw Error(MVSV_E_INVALID_ARG, "detectionView: CV_16S map expected");
+    out.create(dMap.rows, dMap.cols, MAT_8UC3);
+    const mvsv_view_spec spec{layers,         alpha,  beta,          means81,      meanRange.first, meanRange.second,
+                              values, sampleRange.first, sampleRange.second, pointRadius};
+    mvsv_ctx* c = thread_context();
+    check(mvsv_view(c, reinterpret_cast<const int16_t*>(dMap.data), dMap.step / 2, dMap.cols, dMap.rows, &spec,
+                    out.data, out.step, minmax),
+          c);
+}
 // src/utility.cpp:163-174: cv::mean(|Lx| + |Ly|) of the two cv::sepFilter2D responses,
 // on the device (mvsv_sharpness).  The reference passes a view, checkSharpness(
 // s.mLeft(viewArea)) (trgt/liveView.cpp:107-108), and OpenCV's filter engine takes
@@ -134,6 +154,30 @@ inline int pointCloud(const Mat& dMap, const QMatrix& Q, std::vector<mvsv_cloud_
 }
 
 }  // namespace Utility
+
+// inc/view.h, src/view.cpp: the two grids painted over a CV_8UC3 image on the host
+// (mvsv_view_draw: the device view's rules, no device needed).  binning is unused,
+// as in the reference.
+namespace View {
+
+inline void draw_layer(Mat& stream, int layer)
+{
+    if (stream.type != MAT_8UC3 || stream.empty()) throw Error(MVSV_E_INVALID_ARG, "View: CV_8UC3 image expected");
+    const mvsv_view_spec spec{layer, 0, 255, nullptr, 0, 0, nullptr, 0, 0, 3};
+    check(mvsv_view_draw(stream.data, stream.step, stream.cols, stream.rows, &spec), nullptr);
+}
+inline void drawObstacleGrid(Mat& stream, int binning = 0)
+{
+    (void)binning;
+    draw_layer(stream, MVSV_VIEW_OBSTACLE_GRID);
+}
+inline void drawSubimageGrid(Mat& stream, int binning = 0)
+{
+    (void)binning;
+    draw_layer(stream, MVSV_VIEW_SUBIMAGE_GRID);
+}
+
+}  // namespace View
 
 class ply {  // inc/ply.h
 public:
@@ -507,6 +551,22 @@ inline void stream_front_display(mvsv_ctx* ctx, mvsv_stream* s, const DisplaySiz
     check(mvsv_stream_front_display(s, d.rows > 0 ? out.data : nullptr, out.step, minmax), ctx);
 }
 
+// the detection view calls shared by DisparityStream and RawDisparityStream
+inline DisplaySize stream_enable_view(mvsv_ctx* ctx, mvsv_stream* s, int width, int height, int layers, const Rect* roi,
+                                      std::pair<float, float> meanRange, int pointRadius, double alpha, double beta)
+{
+    mvsv_rect r{0, 0, width, height};
+    if (roi) r = {roi->x, roi->y, roi->x + roi->width, roi->y + roi->height};
+    const mvsv_view_spec spec{layers, alpha, beta, nullptr, meanRange.first, meanRange.second, nullptr, 0, 0, pointRadius};
+    check(mvsv_stream_enable_view(s, &r, &spec), ctx);
+    return {r.y1 - r.y0, r.x1 - r.x0};
+}
+inline void stream_front_view(mvsv_ctx* ctx, mvsv_stream* s, const DisplaySize& d, Mat& out, int16_t* minmax)
+{
+    if (d.rows > 0 && d.cols > 0) out.create(d.rows, d.cols, MAT_8UC3);
+    check(mvsv_stream_front_view(s, d.rows > 0 ? out.data : nullptr, out.step, minmax), ctx);
+}
+
 // the point cloud calls shared by DisparityStream and RawDisparityStream: the
 // records kept per frame are what a stream class remembers
 inline int stream_enable_cloud(mvsv_ctx* ctx, mvsv_stream* s, int width, int height, const QMatrix& Q, const Rect* roi,
@@ -623,6 +683,29 @@ public:
         check(mvsv_stream_front_display_view(s_, &map, minmax), ctx_);
         return map;
     }
+    // the detection view (Utility::detectionView of dMap(roi)) with every frame pushed
+    // from now on (no frame may be pending).  MVSV_VIEW_FOUND_TILES: roi must be the
+    // stream's grid_roi, meanRange a MeanDisparityDetection's mRangeDisparity;
+    // MVSV_VIEW_FOUND_POINTS: enableSamplepoints over the same roi first
+    void enableView(int layers, const Rect* roi = nullptr, std::pair<float, float> meanRange = {0.0f, 0.0f},
+                    int pointRadius = 3, double alpha = 0, double beta = 255)
+    {
+        view_ = stream_enable_view(ctx_, s_, w_, h_, layers, roi, meanRange, pointRadius, alpha, beta);
+    }
+    void disableView()
+    {
+        check(mvsv_stream_disable_view(s_), ctx_);
+        view_ = {};
+    }
+    // the oldest pending frame's view (CV_8UC3) and (smin, smax); the frame stays pending
+    void frontView(Mat& out, int16_t* minmax = nullptr) { stream_front_view(ctx_, s_, view_, out, minmax); }
+    // the same image in the stream's pinned host slot (dense, no copy), valid until the next push
+    const uint8_t* frontViewView(int16_t* minmax = nullptr)
+    {
+        const uint8_t* img = nullptr;
+        check(mvsv_stream_front_view_view(s_, &img, minmax), ctx_);
+        return img;
+    }
     // the point cloud (Utility::pointCloud of dMap(roi)) with every frame pushed from
     // now on (no frame may be pending); default roi: the whole map, max_points <= 0:
     // room for every pixel of the roi.  The records stay on the device until asked for.
@@ -663,7 +746,7 @@ private:
     mvsv_stream* s_ = nullptr;
     int w_, h_;
     SampleLayout lattice_;
-    DisplaySize display_;
+    DisplaySize display_, view_;
     int cloud_ = 0;
 };
 

@@ -61,7 +61,7 @@ inline mvsv_ctx* thread_context(int device = 0)
     return h.c;
 }
 
-enum { MAT_8UC1 = 0, MAT_16SC1 = 3 };  // cv::Mat type codes CV_8UC1 / CV_16SC1
+enum { MAT_8UC1 = 0, MAT_16SC1 = 3, MAT_8UC3 = 16 };  // cv::Mat type codes CV_8UC1 / CV_16SC1 / CV_8UC3
 
 struct Rect {
     int x, y, width, height;
@@ -76,7 +76,7 @@ struct Mat {
 
     Mat() = default;
     Mat(int r, int c, int t) { create(r, c, t); }
-    static size_t elem(int t) { return t == MAT_16SC1 ? 2 : 1; }
+    static size_t elem(int t) { return t == MAT_16SC1 ? 2 : t == MAT_8UC3 ? 3 : 1; }
     // non-owning view on user memory (step in bytes)
     static Mat wrap(void* p, int r, int c, int t, size_t step_bytes)
     {

@@ -411,6 +411,18 @@ public:
     {
         stream_front_display(mCtx, mStream, mDisplay, out, minmax);
     }
+    // the detection view on every frame, as on DisparityStream
+    void enableView(int layers, const Rect* roi = nullptr, std::pair<float, float> meanRange = {0.0f, 0.0f},
+                    int pointRadius = 3, double alpha = 0, double beta = 255)
+    {
+        mView = stream_enable_view(mCtx, mStream, mW, mH, layers, roi, meanRange, pointRadius, alpha, beta);
+    }
+    void disableView()
+    {
+        check(mvsv_stream_disable_view(mStream), mCtx);
+        mView = {};
+    }
+    void frontView(Mat& out, int16_t* minmax = nullptr) { stream_front_view(mCtx, mStream, mView, out, minmax); }
     // the focus measure of every pushed raw pair (what trgt/liveView.cpp prints),
     // as on DisparityStream; the view areas lie in the raw frame
     void enableSharpness(const Rect* roi_left = nullptr, const Rect* roi_right = nullptr)
@@ -439,7 +451,7 @@ private:
     mvsv_stream* mStream = nullptr;
     int mRawW, mRawH, mW = 0, mH = 0;
     SampleLayout mLattice;
-    DisplaySize mDisplay;
+    DisplaySize mDisplay, mView;
     int mCloud = 0;
     bool mKeep;
 };

@@ -17,7 +17,9 @@ from .detection import (DisparityStream, MeanDisparityDetection, Samplepoint, Sa
 from .calibration import Stereosystem, read_matrix, stereo_rectify, write_matrices
 from .rectify import (convert_maps, init_undistort_rectify_map, rectify_pair, remap, remap_fixed, undistort_maps,
                       undistort_pair)
-from .utility import CLOUD_DTYPE, Utility, dMapValues, minmax, normalize_minmax, ply, point_cloud, reproject, sharpness
+from .utility import (CLOUD_DTYPE, VIEW_FOUND_POINTS, VIEW_FOUND_TILES, VIEW_OBSTACLE_GRID, VIEW_SUBIMAGE_GRID, Utility,
+                      View, dMapValues, detection_view, minmax, normalize_minmax, ply, point_cloud, reproject,
+                      sharpness)
 
 __all__ = [
     "Disparity", "StereoBM", "StereoSGBM", "Stereopair", "sgbmParameters", "MvsvError",
@@ -31,5 +33,6 @@ __all__ = [
     "samplepoint_values", "samplepoint_detect", "SAMPLE_HIT_DTYPE",
     "normalize_minmax", "minmax", "point_cloud", "CLOUD_DTYPE",
     "sharpness", "undistort_maps", "remap_fixed", "undistort_pair",
+    "detection_view", "View", "VIEW_SUBIMAGE_GRID", "VIEW_OBSTACLE_GRID", "VIEW_FOUND_TILES", "VIEW_FOUND_POINTS",
 ]
 __version__ = "1.0.0"

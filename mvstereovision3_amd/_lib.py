@@ -91,6 +91,14 @@ class Rect(ctypes.Structure):
                 ("y1", ctypes.c_int)]
 
 
+class ViewSpec(ctypes.Structure):
+    """mvsv_view_spec: the layers of a detection view and what they need."""
+    _fields_ = [("layers", ctypes.c_int), ("alpha", ctypes.c_double), ("beta", ctypes.c_double),
+                ("means", ctypes.c_void_p), ("tile_first", ctypes.c_float), ("tile_second", ctypes.c_float),
+                ("values", ctypes.c_void_p), ("point_first", ctypes.c_float), ("point_second", ctypes.c_float),
+                ("point_radius", ctypes.c_int)]
+
+
 class Rectification(ctypes.Structure):
     """mvsv_rectification: what mvsv_stream_create_raw takes over from Stereosystem."""
     _fields_ = [("raw_width", ctypes.c_int), ("raw_height", ctypes.c_int),
@@ -168,6 +176,13 @@ def _declare(lib, strict=True):
         "mvsv_stream_disable_display": ([P], I),
         "mvsv_stream_front_display": ([P, P, Z, P], I),
         "mvsv_stream_front_display_view": ([P, ctypes.POINTER(P), P], I),
+        "mvsv_view_device": ([P, I, P, Z, Z, I, I, P, P, Z, Z, P], I),
+        "mvsv_view": ([P, P, Z, I, I, P, P, Z, P], I),
+        "mvsv_view_draw": ([P, Z, I, I, P], I),
+        "mvsv_stream_enable_view": ([P, P, P], I),
+        "mvsv_stream_disable_view": ([P], I),
+        "mvsv_stream_front_view": ([P, P, Z, P], I),
+        "mvsv_stream_front_view_view": ([P, ctypes.POINTER(P), P], I),
         "mvsv_point_cloud_device": ([P, I, P, Z, Z, I, I, P, P, I, P, P], I),
         "mvsv_point_cloud": ([P, P, Z, I, I, P, P, I, ctypes.POINTER(I), P], I),
         "mvsv_stream_enable_cloud": ([P, P, P, I], I),

@@ -809,6 +809,73 @@ int mvsv_normalize_minmax(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, 
     }());
 }
 
+// the rules of a one-shot view call that need no device; a message, or nullptr
+static const char* view_call_check(const int16_t* dmap, size_t st, int W, int H, const mvsv_view_spec* spec,
+                                   const uint8_t* out, size_t os)
+{
+    if (const char* why = view_check(spec, W, H)) return why;
+    if (!dmap || !out || st < (size_t)W || os < 3 * (size_t)W) return "null view map / image or stride too small";
+    if ((spec->layers & MVSV_VIEW_FOUND_TILES) && !spec->means) return "FOUND_TILES needs means";
+    if ((spec->layers & MVSV_VIEW_FOUND_POINTS) && !spec->values) return "FOUND_POINTS needs values";
+    return nullptr;
+}
+
+int mvsv_view_draw(uint8_t* img, size_t stride, int W, int H, const mvsv_view_spec* spec)
+{
+    if (view_call_check((const int16_t*)img, (size_t)std::max(W, 0), W, H, spec, img, stride)) return MVSV_E_INVALID_ARG;
+    view_draw_host(img, stride, W, H, *spec);
+    return MVSV_OK;
+}
+
+int mvsv_view_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
+                     const mvsv_view_spec* spec, uint8_t* out, size_t os, size_t ofs, int16_t* minmax)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0) return set_error(ctx, MVSV_E_INVALID_ARG, "bad view arguments");
+    if (const char* why = view_call_check(dmap, st, W, H, spec, out, os)) return set_error(ctx, MVSV_E_INVALID_ARG, why);
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, view_device(ctx, n, dmap, st, fs, W, H, *spec, out, os, ofs, minmax));
+}
+
+int mvsv_view(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, const mvsv_view_spec* spec, uint8_t* out,
+              size_t os, int16_t* minmax)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (const char* why = view_call_check(dmap, st, W, H, spec, out, os)) return set_error(ctx, MVSV_E_INVALID_ARG, why);
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, [&]() -> int {  // every exit after an enqueue
+    // staged rows are a multiple of 8 elements apart: the packed path for any width
+    const size_t ws = ((size_t)W + 7) & ~(size_t)7, px = ws * H, ob = (3 * (size_t)W * H + 15) & ~(size_t)15;
+    int sx, sy, nx, ny;
+    sample_layout(W, H, &sx, &sy, &nx, &ny);
+    const size_t npts = (spec->layers & MVSV_VIEW_FOUND_POINTS) ? (size_t)nx * ny : 0;
+    int rc;
+    if ((rc = ensure(ctx, ctx->h_out, px * 2 + ob + 16 + (81 + npts) * sizeof(float), "view staging"))) return rc;
+    int16_t* d = (int16_t*)ctx->h_out.ptr;
+    uint8_t* o = (uint8_t*)(d + px);
+    int16_t* mm = (int16_t*)(o + ob);
+    float* means = (float*)(o + ob + 16);
+    float* values = means + 81;
+    mvsv_view_spec dspec = *spec;
+    dspec.means = means;
+    dspec.values = values;
+    hipStream_t s = ctx->stream;
+    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, ws * 2, dmap, st * 2, (size_t)W * 2, H, hipMemcpyHostToDevice, s),
+                        "H2D map")) ||
+        ((spec->layers & MVSV_VIEW_FOUND_TILES) &&
+         (rc = check_hip(ctx, hipMemcpyAsync(means, spec->means, 81 * sizeof(float), hipMemcpyHostToDevice, s),
+                         "H2D means"))) ||
+        (npts && (rc = check_hip(ctx, hipMemcpyAsync(values, spec->values, npts * sizeof(float),
+                                                     hipMemcpyHostToDevice, s), "H2D sample values"))) ||
+        (rc = view_device(ctx, 1, d, ws, px, W, H, dspec, o, 3 * (size_t)W, ob, mm)) ||
+        (rc = check_hip(ctx, hipMemcpy2DAsync(out, os, o, 3 * (size_t)W, 3 * (size_t)W, H, hipMemcpyDeviceToHost, s),
+                        "D2H view")) ||
+        (minmax && (rc = check_hip(ctx, hipMemcpyAsync(minmax, mm, 4, hipMemcpyDeviceToHost, s), "D2H min / max"))))
+        return rc;
+    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
+    }());
+}
+
 // Host-pointer path: stage through cached device buffers, run, copy back, sync.
 static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs,
                      int W, int H, int16_t* out, size_t os, bool sgbm, const void* params)

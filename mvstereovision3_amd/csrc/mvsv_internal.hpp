@@ -293,6 +293,20 @@ int minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t f
                   int16_t* minmax);
 int normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
                             double alpha, double beta, uint8_t* out, size_t os, size_t ofs, int16_t* minmax);
+// What the display kernels share with the detection view (mvsv_post.hip).
+// display_split: the head | packed groups | tail walk of a row (head = W: narrow
+// loads only).  minmax_partials: *nblk (min, max) pairs per frame into ctx->mm_part.
+void display_split(const int16_t* dmap, size_t st, size_t fs, int n, int W, int* head, int* nvec);
+int minmax_partials(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H, bool positive_only,
+                    int* nblk);
+// Detection view (mvsv_view.hip): the BGR frame of every map with the layers of
+// spec drawn in (include/mvsv.h); spec's means / values are device pointers,
+// [n][81] and [n][nx * ny].  view_check: the argument rules, without a device.
+const char* view_check(const mvsv_view_spec* spec, int W, int H);
+int view_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
+                const mvsv_view_spec& spec, uint8_t* out, size_t os, size_t ofs, int16_t* minmax);
+// the layers of spec painted over a host BGR image, one after the other (host pointers)
+void view_draw_host(uint8_t* img, size_t stride, int W, int H, const mvsv_view_spec& spec);
 // Focus measure (mvsv_post.hip): S4 (include/mvsv.h) of roi q of every u8 frame
 // into sums[f * ss]; q non-empty and inside the W x H image, strides in bytes.
 int sharpness_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t st, size_t fs, int W, int H, const mvsv_rect& q,

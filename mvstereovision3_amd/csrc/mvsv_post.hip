@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "mvsv_device.hpp"
+#include "mvsv_display.hpp"
 #include "mvsv_internal.hpp"
 
 namespace mvsv {
@@ -828,14 +829,6 @@ __global__ __launch_bounds__(1024) void sample_detect_kernel(const float* __rest
 constexpr int kMmBlocks = 64;  // partial pairs per frame at most: one wave folds them
 constexpr int kNormRows = 8;   // rows per block of normalize_u8_kernel (two per wave)
 
-__device__ __forceinline__ int wave_max_i32(int v)
-{
-    v = row_max_i32(v);
-    const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-    const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-    return max(max(a, b), max(c, d));
-}
-
 // Min and max of the part of a frame its block's waves walk: one (min, max)
 // pair per block, written unconditionally -- no atomics, no init pass, the same
 // partials on every run.  kPositive: only values > 0 count (calcMinMaxDisparity's
@@ -876,16 +869,6 @@ __global__ __launch_bounds__(256) void minmax_kernel(const int16_t* __restrict__
     if (threadIdx.x == 0)
         partials[(size_t)f * gridDim.x + blockIdx.x] = make_int2(min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3])),
                                                                  max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3])));
-}
-
-// a frame's nblk <= 64 partial pairs folded by one (whole) wave; wave-uniform result
-__device__ __forceinline__ void fold_partials(const int2* __restrict__ partials, int f, int nblk, int lane, int& lo,
-                                              int& hi)
-{
-    int2 p = make_int2(32767, -32768);
-    if (lane < nblk) p = partials[(size_t)f * nblk + lane];
-    lo = wave_min_i32(p.x);
-    hi = wave_max_i32(p.y);
 }
 
 __global__ __launch_bounds__(64) void minmax_final_kernel(const int2* __restrict__ partials, int nblk,
@@ -1028,33 +1011,9 @@ __global__ __launch_bounds__(64) void sharpness_fold_kernel(const unsigned long 
     if (threadIdx.x == 0) sums[(size_t)blockIdx.x * ss] = (int64_t)t;
 }
 
-// OpenCV 3.4's arithmetic (normalize -> Mat::convertTo, CV_16S -> CV_8U, SSE2 /
-// scalar form): scale and shift in double, every operation rounded on its own;
-// then per pixel a float product and a float sum, each rounded, and a convert
-// with round-half-to-even and saturation.  The library is built with the
-// compiler's default contraction, which would fuse smin * scale into the
-// subtraction and the pixel's product into its sum (the rounding intrinsics
-// are plain operators once inlined): contraction is off in these two functions.
-__device__ __forceinline__ void display_scale(int smin, int smax, double dmin, double dmax, float& sf, float& hf)
-{
-#pragma clang fp contract(off)
-    const double range = (double)smax - (double)smin;
-    const double recip = range > DBL_EPSILON ? 1.0 / range : 0.0;
-    const double scale = (dmax - dmin) * recip;
-    const double prod = (double)smin * scale;
-    const double shift = dmin - prod;
-    sf = (float)scale;
-    hf = (float)shift;
-}
-
-__device__ __forceinline__ uint32_t display_u8(int v, float sf, float hf)
-{
-#pragma clang fp contract(off)
-    const float p = (float)v * sf;
-    const float t = p + hf;
-    return (uint32_t)clampi(__float2int_rn(t), 0, 255);
-}
-
+// The display byte itself (display_scale, display_u8: OpenCV 3.4's arithmetic
+// with contraction off) is in mvsv_display.hpp, shared with the detection view.
+//
 // Block (tile, frame): kNormRows rows of a frame to 8 bit.  Wave 0 folds the
 // frame's partials and lane 0 derives (sf, hf) once for the block.  A packed group
 // is 8 pixels = 8 output bytes, stored as one, two, four or eight stores by the
@@ -1421,15 +1380,15 @@ int sample_detect_device(mvsv_ctx* ctx, int n, const float* values, int W, int H
 // row and frame strides that are multiples of 8 elements (16 bytes), any
 // 2-byte-aligned base -- head = the 0..7 elements up to the next 16-byte
 // boundary.  Other strides take the narrow path (head = W: 2-byte loads only).
-static void display_split(const int16_t* dmap, size_t st, size_t fs, int n, int W, int* head, int* nvec)
+void display_split(const int16_t* dmap, size_t st, size_t fs, int n, int W, int* head, int* nvec)
 {
     const bool packed = st % 8 == 0 && (n == 1 || fs % 8 == 0) && ((uintptr_t)dmap & 1) == 0;
     *head = packed ? std::min(W, (int)(((16 - ((uintptr_t)dmap & 15)) & 15) / 2)) : W;
     *nvec = (W - *head) / 8;
 }
 
-static int minmax_partials(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
-                           bool positive_only, int* nblk)
+int minmax_partials(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H, bool positive_only,
+                    int* nblk)
 {
     int rc, head, nvec;
     // room for 16 frames at least: the usual batches never grow (and so never synchronise) it

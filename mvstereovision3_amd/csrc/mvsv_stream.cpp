@@ -217,6 +217,18 @@ struct mvsv_stream {
     size_t disp_px = 0, disp_slot_bytes = 0;
     uint8_t* disp_map(long i) const { return hDisp + (size_t)i * disp_slot_bytes; }
     int16_t* disp_minmax(long i) const { return (int16_t*)(disp_map(i) + ((disp_px + 1) & ~(size_t)1)); }
+    // the detection view of view_roi of every frame (mvsv_stream_enable_view): a
+    // dense BGR image and (smin, smax) per slot, on the device and in one pinned
+    // host block; view_spec's pointers are set per launch
+    bool view = false;
+    mvsv_rect view_roi{};
+    mvsv_view_spec view_spec{};
+    uint8_t* dView = nullptr;    // [depth][rh][rw][3]
+    int16_t* dViewMM = nullptr;  // [depth][2]
+    uint8_t* hView = nullptr;    // pinned: [depth] x (image, min, max), view_slot_bytes each
+    size_t view_bytes = 0, view_slot_bytes = 0;
+    uint8_t* view_img(long i) const { return hView + (size_t)i * view_slot_bytes; }
+    int16_t* view_minmax(long i) const { return (int16_t*)(view_img(i) + ((view_bytes + 1) & ~(size_t)1)); }
     // the point cloud of cloud_roi of every frame (mvsv_stream_enable_cloud): the
     // records stay in a device ring, (count, min, max) per slot come to the host
     bool cloud = false;
@@ -268,6 +280,17 @@ static void display_free(mvsv_stream* st)
     st->disp = false;
 }
 
+static void view_free(mvsv_stream* st)
+{
+    if (st->dView) (void)hipFree(st->dView);
+    if (st->dViewMM) (void)hipFree(st->dViewMM);
+    if (st->hView) (void)hipHostFree(st->hView);
+    st->dView = nullptr;
+    st->dViewMM = nullptr;
+    st->hView = nullptr;
+    st->view = false;
+}
+
 static void samplepoints_free(mvsv_stream* st)
 {
     if (st->dSpVal) (void)hipFree(st->dSpVal);
@@ -312,6 +335,7 @@ static void stream_free(mvsv_stream* st)
     if (st->dCropR) (void)hipFree(st->dCropR);
     samplepoints_free(st);
     display_free(st);
+    view_free(st);
     cloud_free(st);
     sharpness_free(st);
     if (st->rep) (void)hipHostFree(st->rep);
@@ -548,6 +572,18 @@ static int stream_launch(mvsv_stream* st)
                                              st->disp_alpha, st->disp_beta, st->dDisp + (size_t)i0 * st->disp_px, rw,
                                              st->disp_px, st->dDispMM + 2 * i0);
         }
+        if (status == MVSV_OK && st->view) {  // after the mean grid and the lattice: it reads both
+            const mvsv_rect& q = st->view_roi;
+            const int rw = q.x1 - q.x0, rh = q.y1 - q.y0;
+            mvsv_view_spec spec = st->view_spec;
+            spec.means = first.dMeans;
+            spec.values = st->dSpVal ? st->dSpVal + (size_t)i0 * st->sp_npts : nullptr;
+            spec.point_first = st->sp_first;
+            spec.point_second = st->sp_second;
+            status = view_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, rw, rh, spec,
+                                 st->dView + (size_t)i0 * st->view_bytes, 3 * (size_t)rw, st->view_bytes,
+                                 st->dViewMM + 2 * i0);
+        }
         if (status == MVSV_OK && st->cloud) {
             const mvsv_rect& q = st->cloud_roi;
             status = point_cloud_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, q.x1 - q.x0, q.y1 - q.y0,
@@ -608,6 +644,14 @@ static int stream_launch(mvsv_stream* st)
                 if ((rc = check_hip(c, hipMemcpyAsync(st->disp_map(i), st->dDisp + (size_t)i * st->disp_px, st->disp_px,
                                                       hipMemcpyDeviceToHost, st->down), "stream D2H")) ||
                     (rc = check_hip(c, hipMemcpyAsync(st->disp_minmax(i), st->dDispMM + 2 * i, 2 * sizeof(int16_t),
+                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")))
+                    return rc;
+            }
+            if (st->view) {
+                const long i = i0 + k;
+                if ((rc = check_hip(c, hipMemcpyAsync(st->view_img(i), st->dView + (size_t)i * st->view_bytes,
+                                                      st->view_bytes, hipMemcpyDeviceToHost, st->down), "stream D2H")) ||
+                    (rc = check_hip(c, hipMemcpyAsync(st->view_minmax(i), st->dViewMM + 2 * i, 2 * sizeof(int16_t),
                                                       hipMemcpyDeviceToHost, st->down), "stream D2H")))
                     return rc;
             }
@@ -854,11 +898,18 @@ int mvsv_stream_pop_view(mvsv_stream* st, const int16_t** map, float* means)
     return MVSV_OK;
 }
 
+static bool view_uses_samplepoints(const mvsv_stream* st)
+{
+    return st->view && (st->view_spec.layers & MVSV_VIEW_FOUND_POINTS);
+}
+
 int mvsv_stream_disable_samplepoints(mvsv_stream* st)
 {
     if (!st) return MVSV_E_INVALID_ARG;
     if (st->head != st->tail)
         return set_error(st->ctx, MVSV_E_INVALID_ARG, "sample points change only while no frame is pending");
+    if (view_uses_samplepoints(st))
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the view draws the found points: disable the view first");
     DeviceGuard dev_guard(st->ctx->device);
     samplepoints_free(st);  // every frame was popped: nothing in flight uses the buffers
     return MVSV_OK;
@@ -875,6 +926,9 @@ int mvsv_stream_enable_samplepoints(mvsv_stream* st, const mvsv_rect* roi, int r
     const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, st->W, st->H};
     if (q.x0 < 0 || q.y0 < 0 || q.x1 > st->W || q.y1 > st->H || q.x1 <= q.x0 || q.y1 <= q.y0)
         return set_error(ctx, MVSV_E_INVALID_ARG, "sample point ROI empty or outside the image");
+    if (view_uses_samplepoints(st) && !(q.x0 == st->view_roi.x0 && q.y0 == st->view_roi.y0 && q.x1 == st->view_roi.x1 &&
+                                        q.y1 == st->view_roi.y1))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "the view draws the found points of its own ROI: disable the view first");
     int sx, sy, nx, ny;
     sample_layout(q.x1 - q.x0, q.y1 - q.y0, &sx, &sy, &nx, &ny);
     const int npts = nx * ny;
@@ -979,10 +1033,10 @@ int mvsv_stream_enable_display(mvsv_stream* st, const mvsv_rect* roi, double alp
 }
 
 // the oldest pending frame, complete: its slot index in *idx
-static int display_front(mvsv_stream* st, long* idx)
+static int front_slot(mvsv_stream* st, bool enabled, const char* not_enabled, long* idx)
 {
     mvsv_ctx* ctx = st->ctx;
-    if (!st->disp) return set_error(ctx, MVSV_E_INVALID_ARG, "the display is not enabled on this stream");
+    if (!enabled) return set_error(ctx, MVSV_E_INVALID_ARG, not_enabled);
     if (st->head == st->tail) return set_error(ctx, MVSV_E_INVALID_ARG, "stream empty");
     *idx = st->tail % (long)st->slots.size();
     auto& s = st->slots[*idx];
@@ -994,6 +1048,11 @@ static int display_front(mvsv_stream* st, long* idx)
     if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[*idx], __ATOMIC_ACQUIRE) != 0))
         return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
     return MVSV_OK;
+}
+
+static int display_front(mvsv_stream* st, long* idx)
+{
+    return front_slot(st, st->disp, "the display is not enabled on this stream", idx);
 }
 
 int mvsv_stream_front_display(mvsv_stream* st, uint8_t* out, size_t out_stride, int16_t* minmax)
@@ -1184,6 +1243,87 @@ int mvsv_stream_front_cloud_device(mvsv_stream* st, const mvsv_cloud_point** rec
     int rc;
     if ((rc = cloud_front(st, &idx, count, minmax))) return rc;
     *records_dev = st->dCloud + (size_t)idx * st->cloud_max;
+    return MVSV_OK;
+}
+
+static bool same_rect(const mvsv_rect& a, const mvsv_rect& b)
+{
+    return a.x0 == b.x0 && a.y0 == b.y0 && a.x1 == b.x1 && a.y1 == b.y1;
+}
+
+int mvsv_stream_disable_view(mvsv_stream* st)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (st->head != st->tail)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the view changes only while no frame is pending");
+    DeviceGuard dev_guard(st->ctx->device);
+    view_free(st);  // every frame was popped: nothing in flight uses the buffers
+    return MVSV_OK;
+}
+
+int mvsv_stream_enable_view(mvsv_stream* st, const mvsv_rect* roi, const mvsv_view_spec* spec)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, st->W, st->H};
+    if (q.x0 < 0 || q.y0 < 0 || q.x1 > st->W || q.y1 > st->H || q.x1 <= q.x0 || q.y1 <= q.y0)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "view ROI empty or outside the image");
+    if (const char* why = view_check(spec, q.x1 - q.x0, q.y1 - q.y0)) return set_error(ctx, MVSV_E_INVALID_ARG, why);
+    if (st->head != st->tail)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "the view changes only while no frame is pending");
+    if ((spec->layers & MVSV_VIEW_FOUND_TILES) && !(st->grid && same_rect(st->roi, q)))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "FOUND_TILES needs a stream created with a grid_roi equal to the view's ROI");
+    if ((spec->layers & MVSV_VIEW_FOUND_POINTS) && !(st->sp && same_rect(st->sp_roi, q)))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "FOUND_POINTS needs sample points enabled with the view's ROI");
+    DeviceGuard dev_guard(ctx->device);
+    view_free(st);
+    st->view_roi = q;
+    st->view_spec = *spec;
+    st->view_bytes = 3 * (size_t)(q.x1 - q.x0) * (q.y1 - q.y0);
+    st->view_slot_bytes = (((st->view_bytes + 1) & ~(size_t)1) + 2 * sizeof(int16_t) + 15) & ~(size_t)15;
+    const size_t depth = st->slots.size();
+    const bool ok = hipMalloc((void**)&st->dView, depth * st->view_bytes) == hipSuccess &&
+                    hipMalloc((void**)&st->dViewMM, depth * 2 * sizeof(int16_t)) == hipSuccess &&
+                    hipHostMalloc((void**)&st->hView, depth * st->view_slot_bytes, hipHostMallocDefault) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        view_free(st);
+        return set_error(ctx, MVSV_E_OOM, "view buffer allocation failed");
+    }
+    st->view = true;
+    return MVSV_OK;
+}
+
+static int view_front(mvsv_stream* st, long* idx)
+{
+    return front_slot(st, st->view, "the view is not enabled on this stream", idx);
+}
+
+int mvsv_stream_front_view(mvsv_stream* st, uint8_t* out, size_t out_stride, int16_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    const size_t rb = 3 * (size_t)(st->view_roi.x1 - st->view_roi.x0);
+    if (st->view && out && out_stride < rb)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "view stride smaller than three times the ROI's width");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = view_front(st, &idx))) return rc;
+    if (out) copy_rows(out, out_stride, st->view_img(idx), rb, rb, st->view_roi.y1 - st->view_roi.y0, 0, 1);
+    if (minmax) std::memcpy(minmax, st->view_minmax(idx), 2 * sizeof(int16_t));
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_view_view(mvsv_stream* st, const uint8_t** view, int16_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (!view) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null view pointer");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = view_front(st, &idx))) return rc;
+    *view = st->view_img(idx);
+    if (minmax) std::memcpy(minmax, st->view_minmax(idx), 2 * sizeof(int16_t));
     return MVSV_OK;
 }
 

@@ -692,6 +692,65 @@ class DisparityStream:
                                               mm.ctypes.data), self._ctx.handle)
         return out, (int(mm[0]), int(mm[1]))
 
+    def enable_view(self, layers, roi=None, mean_detector_or_range=None, point_radius=3, alpha=0, beta=255):
+        """The detection view of every frame from now on (utility.detection_view of
+        dMap(roi): display bytes as BGR, View's grids, the found tiles and points),
+        computed on the device after the frame's mean grid and lattice
+        (mvsv_stream_enable_view); only while no frame is pending.
+        VIEW_FOUND_TILES needs a stream whose grid_roi equals roi and
+        mean_detector_or_range: a MeanDisparityDetection (its mRangeDisparity) or
+        (first, second).  VIEW_FOUND_POINTS needs enable_samplepoints with the same
+        roi and uses its range."""
+        self._live()
+        self._view_views_gone("enable_view")
+        from .utility import view_spec
+        rng = mean_detector_or_range
+        if hasattr(rng, "mRangeDisparity"):
+            rng = rng.mRangeDisparity
+        spec = view_spec(layers, rng, None, point_radius, alpha, beta)
+        r = Rect(*(int(v) for v in roi)) if roi is not None else None
+        check(lib().mvsv_stream_enable_view(self._h, ctypes.byref(r) if r is not None else None, ctypes.byref(spec)),
+              self._ctx.handle)
+        self._view_shape = (self.height, self.width, 3) if r is None else (r.y1 - r.y0, r.x1 - r.x0, 3)
+
+    def disable_view(self):
+        self._live()
+        self._view_views_gone("disable_view")
+        check(lib().mvsv_stream_disable_view(self._h), self._ctx.handle)
+        self._view_shape = None
+
+    def _view_views_gone(self, what):
+        # the pinned view slots are reallocated: no view may point into them
+        with self._views_lock:
+            if getattr(self, "_view_views", 0) > 0:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: a front_view view is still alive")
+
+    def front_view(self, copy=True):
+        """(image, (smin, smax)) of the oldest pending frame, which stays pending (pop
+        it afterwards): the uint8 BGR detection view (h, w, 3) of the enabled roi and
+        the min / max it was normalised with.  copy="view": a read-only view of the
+        image in the stream's pinned host slot, valid until the next push."""
+        self._live()
+        shape = getattr(self, "_view_shape", None) or (0, 0, 3)
+        mm = np.zeros(2, np.int16)
+        if copy == "view":
+            ptr = ctypes.c_void_p()
+            check(lib().mvsv_stream_front_view_view(self._h, ctypes.byref(ptr), mm.ctypes.data), self._ctx.handle)
+            buf = (ctypes.c_uint8 * (shape[0] * shape[1] * 3)).from_address(ptr.value)
+            buf._owner = self
+            with self._views_lock:
+                self._live_views += 1
+                self._view_views = getattr(self, "_view_views", 0) + 1
+            fin = weakref.finalize(buf, DisparityStream._view_view_released, self)
+            fin.atexit = False
+            view = np.ctypeslib.as_array(buf).reshape(shape)
+            view.flags.writeable = False
+            return view, (int(mm[0]), int(mm[1]))
+        out = np.empty(shape, np.uint8)
+        check(lib().mvsv_stream_front_view(self._h, out.ctypes.data if out.size else None, 3 * shape[1],
+                                           mm.ctypes.data), self._ctx.handle)
+        return out, (int(mm[0]), int(mm[1]))
+
     def enable_cloud(self, Q, roi=None, max_points=None):
         """The point cloud of every frame from now on: the pixels with v > 0 of
         dMap(roi) in raster order, as Utility::dmap2pcl writes them
@@ -778,6 +837,12 @@ class DisparityStream:
     def _display_view_released(stream):
         with stream._views_lock:
             stream._disp_views -= 1
+        DisparityStream._view_released(stream)
+
+    @staticmethod
+    def _view_view_released(stream):
+        with stream._views_lock:
+            stream._view_views -= 1
         DisparityStream._view_released(stream)
 
     @staticmethod

@@ -307,6 +307,154 @@ def normalize_minmax(dmap, alpha=0, beta=255, out=None, return_minmax=False):
     return out
 
 
+VIEW_SUBIMAGE_GRID = 1
+VIEW_OBSTACLE_GRID = 2
+VIEW_FOUND_TILES = 4
+VIEW_FOUND_POINTS = 8
+
+
+def _view_layer_input(given, rng, built_attr, what):
+    """(float32 array or device tensor or None, (first, second)) of a layer's input:
+    raw values and a range, or a detector whose mRangeDisparity and built values are taken."""
+    if hasattr(given, "mRangeDisparity"):
+        if rng is None:
+            rng = given.mRangeDisparity
+        built = getattr(given, built_attr)
+        given = np.asarray(built, np.float32) if len(built) else None
+    if rng is None:
+        rng = (0.0, 0.0)
+    if len(rng) != 2:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"detection_view: {what} range must be (first, second)")
+    return given, (float(rng[0]), float(rng[1]))
+
+
+def view_spec(layers, mean_range=None, sample_range=None, point_radius=3, alpha=0, beta=255):
+    """An mvsv_view_spec without pointers."""
+    s = _lib.ViewSpec()
+    s.layers = int(layers)
+    s.alpha, s.beta = float(alpha), float(beta)
+    s.tile_first, s.tile_second = mean_range if mean_range is not None else (0.0, 0.0)
+    s.point_first, s.point_second = sample_range if sample_range is not None else (0.0, 0.0)
+    s.point_radius = int(point_radius)
+    return s
+
+
+def detection_view(dmap, layers, means=None, mean_range=None, values=None, sample_range=None, point_radius=3,
+                   alpha=0, beta=255, out=None, return_minmax=False):
+    """The annotated BGR frame of the reference's detection programs
+    (trgt/demo.cpp:280-298): cv::normalize(NORM_MINMAX, CV_8U), GRAY2BGR, View's
+    grids and drawFoundObstacles, in one pass on the GPU (mvsv_view_device).
+
+    dmap: int16, (H, W) or a batch (N, H, W), at least 9 x 9.  A torch device tensor
+    (any view with unit column stride) gives a uint8 device tensor (..., H, W, 3) in
+    B, G, R order, asynchronously on the current stream; a numpy map gives a numpy
+    image.  layers: VIEW_* bits.  means: 81 (or N x 81) tile means and mean_range =
+    (first, second) for VIEW_FOUND_TILES, or a MeanDisparityDetection (its
+    mRangeDisparity, and its means if built).  values: the lattice values and
+    sample_range for VIEW_FOUND_POINTS, or a SamplepointDetection.  point_radius:
+    0..3.  out: an image of that shape to write into (unit channel stride, pixels 3
+    bytes apart).  return_minmax: also return (smin, smax), (2,) or (N, 2)."""
+    means, mean_range = _view_layer_input(means, mean_range, "mMeanMap", "mean")
+    values, sample_range = _view_layer_input(values, sample_range, "mDistanceVec", "sample")
+    spec = view_spec(layers, mean_range, sample_range, point_radius, alpha, beta)
+    if type(dmap).__module__.startswith("torch") and dmap.is_cuda:
+        import torch
+        d, batched, ctx = _device_frames(dmap, "detection_view")
+        n, H, W = d.shape
+        shape = tuple(dmap.shape) + (3,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dmap.device)
+        elif not (type(out).__module__.startswith("torch") and out.is_cuda and out.dtype == torch.uint8 and
+                  tuple(out.shape) == shape and out.stride(-1) == 1 and out.stride(-2) == 3):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG,
+                            "detection_view: out must be a uint8 device tensor (..., H, W, 3) with dense pixels")
+        o = out if batched else out.unsqueeze(0)
+
+        def flat(a):  # float32 on the device, frames back to back
+            if a is None:
+                return None
+            return torch.as_tensor(a, dtype=torch.float32, device=dmap.device).reshape(-1).contiguous()
+        tm, tv = flat(means), flat(values)
+        if tm is not None and tm.numel() != 81 * n:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "detection_view: 81 means per frame expected")
+        if tv is not None:
+            from .disparity import samplepoint_layout
+            _, _, nx, ny = samplepoint_layout(W, H)
+            if tv.numel() != nx * ny * n:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "detection_view: one value per lattice point and frame expected")
+            if tv.numel() == 0:
+                tv = torch.zeros(1, dtype=torch.float32, device=dmap.device)  # no lattice: never read
+        spec.means = tm.data_ptr() if tm is not None else None
+        spec.values = tv.data_ptr() if tv is not None else None
+        mm = torch.empty((n, 2), dtype=torch.int16, device=dmap.device) if return_minmax else None
+        check(lib().mvsv_view_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H, ctypes.byref(spec),
+                                     o.data_ptr(), o.stride(1), o.stride(0),
+                                     mm.data_ptr() if return_minmax else None), ctx.handle)
+        if return_minmax:
+            return out, (mm if batched else mm[0])
+        return out
+    d = np.asarray(dmap)
+    if d.ndim not in (2, 3) or d.dtype != np.int16:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "detection_view: 2-D or 3-D int16 map expected")
+    if d.strides[-1] != 2:
+        d = np.ascontiguousarray(d)
+    if out is None:
+        out = np.empty(d.shape + (3,), np.uint8)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.shape == d.shape + (3,) and
+              out.strides[-1] == 1 and out.strides[-2] == 3):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG,
+                        "detection_view: out must be a uint8 array (..., H, W, 3) with dense pixels")
+    frames = d if d.ndim == 3 else d[None]
+    outs = out if d.ndim == 3 else out[None]
+    n = len(frames)
+    hm = np.ascontiguousarray(np.asarray(means, np.float32).reshape(n, 81)) if means is not None else None
+    hv = np.ascontiguousarray(np.asarray(values, np.float32).reshape(n, -1)) if values is not None else None
+    if hv is not None:
+        from .disparity import samplepoint_layout
+        _, _, nx, ny = samplepoint_layout(d.shape[-1], d.shape[-2])
+        if hv.shape[1] != nx * ny:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "detection_view: one value per lattice point and frame expected")
+        if hv.shape[1] == 0:
+            hv = np.zeros((n, 1), np.float32)  # no lattice: a pointer that is never read
+    mm = np.empty((n, 2), np.int16)
+    ctx = context(0)
+    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    for k, (f, o, m) in enumerate(zip(frames, outs, mm)):
+        spec.means = hm[k].ctypes.data if hm is not None else None
+        spec.values = hv[k].ctypes.data if hv is not None else None
+        check(lib().mvsv_view(ctx.handle, f.ctypes.data, f.strides[0] // 2, f.shape[1], f.shape[0], ctypes.byref(spec),
+                              o.ctypes.data, o.strides[0], m.ctypes.data), ctx.handle)
+    if return_minmax:
+        return out, (mm if d.ndim == 3 else mm[0])
+    return out
+
+
+class View:
+    """Static mirror of namespace View (inc/view.h, src/view.cpp): the two grids,
+    painted in place over a host BGR image (H, W, 3) by the library's host painter
+    (mvsv_view_draw), whose rules are the device view's."""
+
+    @staticmethod
+    def _draw(img, layer):
+        if not (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3 and
+                img.strides[2] == 1 and img.strides[1] == 3 and img.flags.writeable):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "View: a writeable uint8 BGR image (H, W, 3) with dense pixels expected")
+        spec = view_spec(layer)
+        rc = lib().mvsv_view_draw(img.ctypes.data, img.strides[0], img.shape[1], img.shape[0], ctypes.byref(spec))
+        if rc:
+            raise MvsvError(rc, "View: the image must be at least 9 x 9")
+
+    @staticmethod
+    def drawObstacleGrid(img, binning=0):
+        """src/view.cpp: the 3 x 3 grid, red (binning is unused, as in the reference)."""
+        View._draw(img, VIEW_OBSTACLE_GRID)
+
+    @staticmethod
+    def drawSubimageGrid(img, binning=0):
+        """src/view.cpp: the lines of the 9 x 9 grid that are no obstacle grid lines, (100, 0, 0)."""
+        View._draw(img, VIEW_SUBIMAGE_GRID)
+
+
 def point_cloud(dmap, Q, max_points=None, return_minmax=False, out=None):
     """The valid pixels (v > 0) of an int16 map as a point cloud, compacted on the
     GPU in raster order -- what Utility::dmap2pcl makes of a map (src/utility.cpp:
