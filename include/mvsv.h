@@ -74,6 +74,12 @@
  *   mvsv_remap_fixed_device /         maps, and Stereosystem::getUndistortedImagepair
  *   mvsv_undistort_pair               src/Stereosystem.cpp:179-191 (trgt/liveUndistortion.cpp:58,
  *                                     example/images.cpp:95)
+ *   mvsv_prepare_gray(_device)        cv::resize(.., 0.5, 0.5, INTER_AREA) + cv::cvtColor(BGR2GRAY)
+ *                                     of trgt/disparityTest.cpp:201-211, one kernel
+ *   mvsv_stream_create_bm /           Disparity::bm (trgt/disparityTest.cpp:268) as a stream's
+ *   _create_raw_bm / _set_bm_params   matcher, beside Disparity::sgbm (:267)
+ *   mvsv_stream_enable_bgr /          colour pairs into a stream: uploaded as BGR, prepared on
+ *   _push_bgr                         the device ahead of the matcher
  *
  * Conventions
  *   - Plain C types only; no exceptions cross this boundary.
@@ -685,6 +691,42 @@ MVSV_API int mvsv_stream_disable_sharpness(mvsv_stream* s);
  * launch failed (as pop reports it). */
 MVSV_API int mvsv_stream_front_sharpness(mvsv_stream* s, double value[2], int64_t sum4[2]);
 
+/* ---- StereoBM streams (trgt/disparityTest.cpp:267-268 runs both matchers) -----------
+ * A stream computes its frames with one matcher at a time.  create_bm / create_raw_bm
+ * are mvsv_stream_create / mvsv_stream_create_raw with StereoBM (mvsv_bm_device) as the
+ * matcher.  mvsv_stream_set_bm_params switches a stream of either origin to StereoBM
+ * for the frames pushed from now on, mvsv_stream_set_params to SGBM; each validates
+ * against the stream's size and first launches the frames already pushed, so a
+ * frame-batch launch never mixes matchers or parameter sets.  Everything behind the
+ * matcher (mean grid, sample points, display, view, cloud, sharpness, pop*, batch,
+ * inflight lanes, raw rectification) is a function of the int16 map and works alike;
+ * StereoBM's FILTERED value (min_disparity - 1) * 16 goes through each product's own
+ * rule.  The strip-wait report (MVSV_E_TIMEOUT) is SGBM's: a StereoBM frame never has it. */
+enum { MVSV_MATCHER_SGBM = 0, MVSV_MATCHER_BM = 1 };
+MVSV_API int mvsv_stream_create_bm(mvsv_ctx* ctx, int width, int height, const mvsv_bm_params* p, int depth,
+                                   const mvsv_rect* grid_roi, mvsv_stream** out);
+MVSV_API int mvsv_stream_create_raw_bm(mvsv_ctx* ctx, const mvsv_rectification* rect, const mvsv_bm_params* p,
+                                       int depth, const mvsv_rect* grid_roi, mvsv_stream** out);
+MVSV_API int mvsv_stream_set_bm_params(mvsv_stream* s, const mvsv_bm_params* p);
+/* the matcher of the frames pushed from now on (MVSV_MATCHER_*); -1 for a null stream */
+MVSV_API int mvsv_stream_matcher(const mvsv_stream* s);
+
+/* ---- colour frames into a stream of rectified pairs ---------------------------------
+ * mvsv_stream_enable_bgr: the stream also takes src_width x src_height interleaved BGR
+ * pairs (mvsv_stream_push_bgr); each is uploaded once as BGR and mvsv_prepare_gray_device
+ * (halve, variant) writes the frame's grey pair on the device ahead of its matcher, the
+ * way a raw stream rectifies.  mvsv_prepare_size(src_width, src_height, halve) must equal
+ * the stream's size.  Only on a stream of rectified pairs, only while no frame is pending
+ * (MVSV_E_INVALID_ARG otherwise); a second call replaces the first.  mvsv_stream_push
+ * (grey) stays valid, and grey and BGR frames may alternate.  The sharpness product of a
+ * BGR frame is measured on its prepared grey pair (the stream's size), as for a grey frame.
+ * mvsv_stream_push_bgr: strides in bytes, >= 3 * src_width; MVSV_E_INVALID_ARG on a raw
+ * stream, without enable_bgr, and when depth frames are pending. */
+MVSV_API int mvsv_stream_enable_bgr(mvsv_stream* s, int src_width, int src_height, int halve, int variant);
+MVSV_API int mvsv_stream_disable_bgr(mvsv_stream* s);
+MVSV_API int mvsv_stream_push_bgr(mvsv_stream* s, const uint8_t* left, size_t left_stride, const uint8_t* right,
+                                  size_t right_stride);
+
 /* ---- camera set-up: undistorted pairs (Stereosystem::getUndistortedImagepair) -------
  * cv::undistort(src, dst, K, dist) of OpenCV 3.4 (no new camera matrix: Ar = K) works
  * in stripes of min(max(1, 4096 / W), H) rows; for the stripe starting at row y0 it
@@ -770,6 +812,34 @@ MVSV_API int mvsv_resize_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t
                                 double fy, uint8_t* dst, size_t dst_stride, size_t dst_frame_stride);
 MVSV_API int mvsv_resize(mvsv_ctx* ctx, const uint8_t* src, size_t src_stride, int src_width,
                          int src_height, double fx, double fy, uint8_t* dst, size_t dst_stride);
+
+/* ---- grey pair preparation: colour frames in (trgt/disparityTest.cpp:201-211) -------
+ * What the reference's file-driven harness does to an image between cv::imread and
+ * the matchers, on interleaved 8-bit BGR (CV_8UC3), in one kernel:
+ *   halve = 1: cv::resize(src, dst, Size(), 0.5, 0.5, INTER_AREA) -- every channel by
+ *              mvsv_resize's 2x2 rule ((a+b+c+d+2) >> 2 on whole blocks, the float mean
+ *              rounded half to even on blocks clipped by an odd width or height), each
+ *              channel rounded to 8 bits --, then
+ *   always:    cv::cvtColor(BGR2GRAY) for 8 bit:
+ *              MVSV_GRAY_Q14  (B*1868 + G*9617 + R*4899 + 8192) >> 14   (OpenCV up to
+ *                             the early 3.4 releases; the default)
+ *              MVSV_GRAY_Q15  (B*3735 + G*19235 + R*9798 + 16384) >> 15 (later releases)
+ * halve = 0 is the conversion alone; any other value is MVSV_E_INVALID_ARG.
+ * mvsv_prepare_size: the grey image's size (mvsv_resize_size(w, h, 0.5, 0.5) when
+ * halving: cvRound, half to even; a 1-pixel side halves to 0 and is invalid).  Host only.
+ * mvsv_prepare_gray_device: n frames, device pointers, strides in bytes, any base
+ * alignment and any stride >= 3 * src_width (a BGR ROI view); sources whose base and
+ * strides are multiples of 4 are read with packed loads.  No byte outside
+ * [row, row + 3 * src_width) is read, none outside [row, row + dst_width) written.
+ * Asynchronous on the context's stream.
+ * mvsv_prepare_gray: one host image, synchronous. */
+enum { MVSV_GRAY_Q14 = 0, MVSV_GRAY_Q15 = 1 };
+MVSV_API int mvsv_prepare_size(int src_width, int src_height, int halve, int* dst_width, int* dst_height);
+MVSV_API int mvsv_prepare_gray_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t stride, size_t frame_stride,
+                                      int src_width, int src_height, int halve, int variant, uint8_t* dst,
+                                      size_t dst_stride, size_t dst_frame_stride);
+MVSV_API int mvsv_prepare_gray(mvsv_ctx* ctx, const uint8_t* bgr, size_t stride, int src_width, int src_height,
+                               int halve, int variant, uint8_t* dst, size_t dst_stride);
 
 /* cv::initUndistortRectifyMap(K, dist, R, P, size, CV_32FC1): K 3x3, dist =
  * (k1, k2, p1, p2[, k3[, k4, k5, k6]]) with ndist in {0, 4, 5, 8}, R 3x3, P 3x3 or

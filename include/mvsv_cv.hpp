@@ -76,6 +76,22 @@ inline void compute(const cv::Ptr<cv::StereoBM>& m, const cv::Mat& L, const cv::
     if (rc < 0) CV_Error(cv::Error::StsOutOfRange, mvsv_last_error(c));
 }
 
+// The two calls trgt/disparityTest.cpp:201-211 makes on an image ahead of the
+// matchers -- cv::resize(.., 0.5, 0.5, INTER_AREA) with halve, cv::cvtColor(BGR2GRAY)
+// -- as one device pass: CV_8UC3 in, CV_8UC1 out.
+inline void prepareGray(const cv::Mat& bgr, cv::Mat& gray, bool halve = true, int variant = MVSV_GRAY_Q14)
+{
+    CV_Assert(bgr.type() == CV_8UC3 && !bgr.empty());
+    int w = 0, h = 0;
+    if (mvsv_prepare_size(bgr.cols, bgr.rows, halve ? 1 : 0, &w, &h) < 0)
+        CV_Error(cv::Error::StsOutOfRange, "prepareGray: the image halves to nothing");
+    gray.create(h, w, CV_8UC1);
+    mvsv_ctx* c = mvsv::thread_context();
+    int rc = mvsv_prepare_gray(c, bgr.data, bgr.step, bgr.cols, bgr.rows, halve ? 1 : 0, variant, gray.data,
+                               gray.step);
+    if (rc < 0) CV_Error(cv::Error::StsError, mvsv_last_error(c));
+}
+
 }  // namespace mvsv_cv
 
 #endif  // MVSV_CV_HPP

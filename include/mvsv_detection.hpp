@@ -97,6 +97,20 @@ inline void normalize(const Mat& dMap, Mat& out, double alpha = 0, double beta =
                                 alpha, beta, out.data, out.step, minmax),
           c);
 }
+// What trgt/disparityTest.cpp:201-211 does to an image ahead of the matchers, on the
+// device (mvsv_prepare_gray): with halve, cv::resize(.., 0.5, 0.5, INTER_AREA) of the
+// CV_8UC3 image, then cv::cvtColor(BGR2GRAY) in the arithmetic of `variant`
+// (MVSV_GRAY_Q14 / MVSV_GRAY_Q15).  out: CV_8UC1 of mvsv_prepare_size.
+inline void prepareGray(const Mat& bgr, Mat& out, bool halve = true, int variant = MVSV_GRAY_Q14)
+{
+    if (bgr.type != MAT_8UC3 || bgr.empty()) throw Error(MVSV_E_INVALID_ARG, "prepareGray: CV_8UC3 image expected");
+    int w = 0, h = 0;
+    if (mvsv_prepare_size(bgr.cols, bgr.rows, halve ? 1 : 0, &w, &h) < 0)
+        throw Error(MVSV_E_INVALID_ARG, "prepareGray: the image halves to nothing");
+    out.create(h, w, MAT_8UC1);
+    mvsv_ctx* c = thread_context();
+    check(mvsv_prepare_gray(c, bgr.data, bgr.step, bgr.cols, bgr.rows, halve ? 1 : 0, variant, out.data, out.step), c);
+}
 // The frame the detection programs show (trgt/demo.cpp:280-298): normalize,
 // cv::cvtColor(GRAY2BGR), View's grids and drawFoundObstacles in one device pass
 // (mvsv_view).  out: CV_8UC3, B, G, R.  layers: MVSV_VIEW_* bits; means81 and
@@ -610,9 +624,18 @@ inline Sharpness stream_front_sharpness(mvsv_ctx* ctx, mvsv_stream* s)
 }
 
 // Camera loop without the worker thread: push rectified pairs, pop maps (and the
-// 9x9 means of the work ROI) in order; up to `depth` frames in flight.
+// 9x9 means of the work ROI) in order; up to `depth` frames in flight.  The matcher
+// is a StereoSGBM or a StereoBM (trgt/disparityTest.cpp:267-268 runs both); setParams
+// takes either and switches the frames pushed from then on.
 class DisparityStream {
 public:
+    DisparityStream(const StereoBM& matcher, int width, int height, int depth = 3, const Rect* grid_roi = nullptr)
+        : ctx_(thread_context()), w_(width), h_(height)
+    {
+        mvsv_rect r{};
+        if (grid_roi) r = {grid_roi->x, grid_roi->y, grid_roi->x + grid_roi->width, grid_roi->y + grid_roi->height};
+        check(mvsv_stream_create_bm(ctx_, width, height, &matcher.p, depth, grid_roi ? &r : nullptr, &s_), ctx_);
+    }
     DisparityStream(const StereoSGBM& matcher, int width, int height, int depth = 3,
                     const Rect* grid_roi = nullptr)
         : ctx_(thread_context()), w_(width), h_(height)
@@ -629,6 +652,24 @@ public:
     DisparityStream(const DisparityStream&) = delete;
     DisparityStream& operator=(const DisparityStream&) = delete;
     void setParams(const StereoSGBM& matcher) { check(mvsv_stream_set_params(s_, &matcher.params()), ctx_); }
+    void setParams(const StereoBM& matcher) { check(mvsv_stream_set_bm_params(s_, &matcher.p), ctx_); }
+    // MVSV_MATCHER_SGBM / MVSV_MATCHER_BM: what computes the frames pushed from now on
+    int matcher() const { return mvsv_stream_matcher(s_); }
+    // colour pairs (CV_8UC3, src_width x src_height) from now on too (no frame may be
+    // pending): uploaded as BGR, Utility::prepareGray on the device ahead of the matcher;
+    // mvsv_prepare_size of the source must be the stream's size
+    void enableBgr(int src_width, int src_height, bool halve = true, int variant = MVSV_GRAY_Q14)
+    {
+        check(mvsv_stream_enable_bgr(s_, src_width, src_height, halve ? 1 : 0, variant), ctx_);
+    }
+    void disableBgr() { check(mvsv_stream_disable_bgr(s_), ctx_); }
+    void pushBgr(const Mat& left, const Mat& right)
+    {
+        if (left.empty() || left.type != MAT_8UC3 || right.type != MAT_8UC3 || left.rows != right.rows ||
+            left.cols != right.cols)
+            throw Error(MVSV_E_INVALID_ARG, "pushBgr: CV_8UC3 pair of one size expected");
+        check(mvsv_stream_push_bgr(s_, left.data, left.step, right.data, right.step), ctx_);
+    }
     // frames computed `batch` at a time (frame-batch kernels, up to batch-1 frames of latency)
     void setBatch(int batch) { check(mvsv_stream_set_batch(s_, batch), ctx_); }
     // up to n frame-batch launches computed concurrently (1..4)

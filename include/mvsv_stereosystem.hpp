@@ -335,6 +335,32 @@ public:
                        int inflight = 1)
         : mRawW(s.width()), mRawH(s.height()), mKeep(keep_rectified)
     {
+        open(s, &matcher.params(), nullptr, factor, depth, grid_roi, batch, inflight);
+    }
+    // the same loop with StereoBM as the matcher (mvsv_stream_create_raw_bm)
+    RawDisparityStream(const Stereosystem& s, const StereoBM& matcher, float factor = 0.f, int depth = 3,
+                       const mvsv_rect* grid_roi = nullptr, bool keep_rectified = false, int batch = 1,
+                       int inflight = 1)
+        : mRawW(s.width()), mRawH(s.height()), mKeep(keep_rectified)
+    {
+        open(s, nullptr, &matcher.p, factor, depth, grid_roi, batch, inflight);
+    }
+    ~RawDisparityStream() { mvsv_stream_destroy(mStream); }
+    RawDisparityStream(const RawDisparityStream&) = delete;
+    RawDisparityStream& operator=(const RawDisparityStream&) = delete;
+
+    int width() const { return mW; }
+    int height() const { return mH; }
+    int pending() const { return mvsv_stream_pending(mStream); }
+    void set_params(const StereoSGBM& matcher) { check(mvsv_stream_set_params(mStream, &matcher.params()), mCtx); }
+    void set_params(const StereoBM& matcher) { check(mvsv_stream_set_bm_params(mStream, &matcher.p), mCtx); }
+    int matcher() const { return mvsv_stream_matcher(mStream); }
+
+private:
+    // one of sgbm / bm is given
+    void open(const Stereosystem& s, const mvsv_sgbm_params* sgbm, const mvsv_bm_params* bm, float factor, int depth,
+              const mvsv_rect* grid_roi, int batch, int inflight)
+    {
         if (!s.isInit()) throw Error(MVSV_E_INVALID_ARG, "RawDisparityStream: initRectification() has not run");
         mCtx = thread_context();
         mvsv_rectification r{};
@@ -347,8 +373,10 @@ public:
         r.map_stride = (size_t)mRawW;
         r.roi = s.displayROI();
         r.factor = factor;
-        r.keep_rectified = keep_rectified ? 1 : 0;
-        check(mvsv_stream_create_raw(mCtx, &r, &matcher.params(), depth, grid_roi, &mStream), mCtx);
+        r.keep_rectified = mKeep ? 1 : 0;
+        check(sgbm ? mvsv_stream_create_raw(mCtx, &r, sgbm, depth, grid_roi, &mStream)
+                   : mvsv_stream_create_raw_bm(mCtx, &r, bm, depth, grid_roi, &mStream),
+              mCtx);
         int rc = mvsv_stream_size(mStream, &mW, &mH);
         if (rc == MVSV_OK && batch != 1) rc = mvsv_stream_set_batch(mStream, batch);
         if (rc == MVSV_OK && inflight != 1) rc = mvsv_stream_set_inflight(mStream, inflight);
@@ -357,15 +385,8 @@ public:
             check(rc, mCtx);
         }
     }
-    ~RawDisparityStream() { mvsv_stream_destroy(mStream); }
-    RawDisparityStream(const RawDisparityStream&) = delete;
-    RawDisparityStream& operator=(const RawDisparityStream&) = delete;
 
-    int width() const { return mW; }
-    int height() const { return mH; }
-    int pending() const { return mvsv_stream_pending(mStream); }
-    void set_params(const StereoSGBM& matcher) { check(mvsv_stream_set_params(mStream, &matcher.params()), mCtx); }
-
+public:
     void push_raw(const Mat& left, const Mat& right)
     {
         check_pair(left, right);

@@ -6,7 +6,7 @@ src/disparity.cpp:6-108).  Compute lives in hand-written HIP kernels for
 gfx950 behind the C ABI of libmvsv.so (include/mvsv.h); this package is the
 host-side mirror of the reference interface.
 """
-from ._lib import (MODE_HH, MODE_SGBM, MVSV_E_TIMEOUT, OPT_BITSLICE, OPT_BM_TILE_ROWS, OPT_PATH_SCHEDULE,
+from ._lib import (GRAY_Q14, GRAY_Q15, MATCHER_BM, MATCHER_SGBM, MODE_HH, MODE_SGBM, MVSV_E_TIMEOUT, OPT_BITSLICE, OPT_BM_TILE_ROWS, OPT_PATH_SCHEDULE,
                    OPT_STRIP_SPIN_LIMIT, OPT_STRIP_WAVES,
                    PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, VARIANT_FIRSTCOL_FIX,
                    VARIANT_WTA_MIN_D, MvsvError, set_option, synchronize)
@@ -18,8 +18,8 @@ from .calibration import Stereosystem, read_matrix, stereo_rectify, write_matric
 from .rectify import (convert_maps, init_undistort_rectify_map, rectify_pair, remap, remap_fixed, undistort_maps,
                       undistort_pair)
 from .utility import (CLOUD_DTYPE, VIEW_FOUND_POINTS, VIEW_FOUND_TILES, VIEW_OBSTACLE_GRID, VIEW_SUBIMAGE_GRID, Utility,
-                      View, dMapValues, detection_view, minmax, normalize_minmax, ply, point_cloud, reproject,
-                      sharpness)
+                      View, dMapValues, detection_view, minmax, normalize_minmax, ply, point_cloud, prepare_gray, prepare_size,
+                      reproject, sharpness)
 
 __all__ = [
     "Disparity", "StereoBM", "StereoSGBM", "Stereopair", "sgbmParameters", "MvsvError",
@@ -34,5 +34,6 @@ __all__ = [
     "normalize_minmax", "minmax", "point_cloud", "CLOUD_DTYPE",
     "sharpness", "undistort_maps", "remap_fixed", "undistort_pair",
     "detection_view", "View", "VIEW_SUBIMAGE_GRID", "VIEW_OBSTACLE_GRID", "VIEW_FOUND_TILES", "VIEW_FOUND_POINTS",
+    "prepare_gray", "prepare_size", "GRAY_Q14", "GRAY_Q15", "MATCHER_SGBM", "MATCHER_BM",
 ]
 __version__ = "1.0.0"

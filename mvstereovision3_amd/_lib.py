@@ -39,6 +39,10 @@ PREFILTER_NORMALIZED_RESPONSE = 0
 PREFILTER_XSOBEL = 1
 VARIANT_FIRSTCOL_FIX = 1
 VARIANT_WTA_MIN_D = 2
+GRAY_Q14 = 0
+GRAY_Q15 = 1
+MATCHER_SGBM = 0
+MATCHER_BM = 1
 
 NUM_STAGES = 9
 
@@ -205,6 +209,16 @@ def _declare(lib, strict=True):
                               ctypes.POINTER(I)], I),
         "mvsv_resize_device": ([P, I, P, Z, Z, I, I, ctypes.c_double, ctypes.c_double, P, Z, Z], I),
         "mvsv_resize": ([P, P, Z, I, I, ctypes.c_double, ctypes.c_double, P, Z], I),
+        "mvsv_prepare_size": ([I, I, I, ctypes.POINTER(I), ctypes.POINTER(I)], I),
+        "mvsv_prepare_gray_device": ([P, I, P, Z, Z, I, I, I, I, P, Z, Z], I),
+        "mvsv_prepare_gray": ([P, P, Z, I, I, I, I, P, Z], I),
+        "mvsv_stream_create_bm": ([P, I, I, P, I, P, ctypes.POINTER(P)], I),
+        "mvsv_stream_create_raw_bm": ([P, P, P, I, P, ctypes.POINTER(P)], I),
+        "mvsv_stream_set_bm_params": ([P, P], I),
+        "mvsv_stream_matcher": ([P], I),
+        "mvsv_stream_enable_bgr": ([P, I, I, I, I], I),
+        "mvsv_stream_disable_bgr": ([P], I),
+        "mvsv_stream_push_bgr": ([P, P, Z, P, Z], I),
         "mvsv_reproject_device": ([P, I, P, Z, Z, I, I, P, P, Z, Z], I),
         "mvsv_calc_coordinate": ([ctypes.c_float] * 3 + [P, P], None),
         "mvsv_calc_coordinates": ([ctypes.c_int, P, P, P], None),

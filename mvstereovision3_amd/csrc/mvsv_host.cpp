@@ -1094,6 +1094,53 @@ int mvsv_resize(mvsv_ctx* ctx, const uint8_t* src, size_t ss, int sw, int sh, do
     }());
 }
 
+int mvsv_prepare_size(int sw, int sh, int halve, int* dw, int* dh)
+{
+    if (!dw || !dh) return MVSV_E_INVALID_ARG;
+    return prepare_size(sw, sh, halve, dw, dh);
+}
+
+// [cv::resize INTER_AREA 0.5 + cv::cvtColor BGR2GRAY] trgt/disparityTest.cpp:201-211
+int mvsv_prepare_gray_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t ss, size_t sfs, int sw, int sh,
+                             int halve, int variant, uint8_t* dst, size_t ds, size_t dfs)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    int dw, dh;
+    if (n <= 0 || !bgr || !dst || prepare_size(sw, sh, halve, &dw, &dh) || ss < 3 * (size_t)sw || ds < (size_t)dw ||
+        (variant != MVSV_GRAY_Q14 && variant != MVSV_GRAY_Q15))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad prepare arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, prepare_gray_device(ctx, n, bgr, ss, sfs, sw, sh, halve, variant, dst, ds, dfs));
+}
+
+int mvsv_prepare_gray(mvsv_ctx* ctx, const uint8_t* bgr, size_t ss, int sw, int sh, int halve, int variant,
+                      uint8_t* dst, size_t ds)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    int dw, dh;
+    if (!bgr || !dst || prepare_size(sw, sh, halve, &dw, &dh) || ss < 3 * (size_t)sw || ds < (size_t)dw ||
+        (variant != MVSV_GRAY_Q14 && variant != MVSV_GRAY_Q15))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad prepare arguments");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, [&]() -> int {
+    // device rows padded to 4 bytes: the kernel's packed loads
+    const size_t row = 3 * (size_t)sw, drow = (row + 3) & ~(size_t)3, in = drow * sh, outb = (size_t)dw * dh;
+    int rc;
+    if ((rc = ensure(ctx, ctx->h_left, in, "prepare staging")) ||
+        (rc = ensure(ctx, ctx->h_right, outb, "prepare staging")))
+        return rc;
+    hipStream_t s = ctx->stream;
+    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_left.ptr, drow, bgr, ss, row, sh, hipMemcpyHostToDevice, s),
+                        "H2D image")) ||
+        (rc = prepare_gray_device(ctx, 1, (const uint8_t*)ctx->h_left.ptr, drow, in, sw, sh, halve, variant,
+                                  (uint8_t*)ctx->h_right.ptr, dw, outb)) ||
+        (rc = check_hip(ctx, hipMemcpy2DAsync(dst, ds, ctx->h_right.ptr, dw, dw, dh, hipMemcpyDeviceToHost, s),
+                        "D2H image")))
+        return rc;
+    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
+    }());
+}
+
 // [Stereosystem::getRectifiedImagepair] src/Stereosystem.cpp:243-262
 int mvsv_rectify_pair(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs,
                       int W, int H, const float* const* maps, const mvsv_rect* roi, uint8_t* oL,

@@ -272,6 +272,11 @@ int rectify_pair_device(mvsv_ctx* ctx, int n, const uint8_t* raw, int sw, int sh
 int resize_size(int sw, int sh, double fx, double fy, int* dw, int* dh);
 int resize_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh, double fx,
                   double fy, uint8_t* dst, size_t ds, size_t dfs);
+// Grey pair preparation (mvsv_prepare.hip): interleaved BGR -> grey, halved 2 x 2
+// first with halve = 1 (include/mvsv.h); strides in bytes
+int prepare_size(int sw, int sh, int halve, int* dw, int* dh);
+int prepare_gray_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t ss, size_t sfs, int sw, int sh, int halve,
+                        int variant, uint8_t* dst, size_t ds, size_t dfs);
 int reproject_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
                      const float* Q, float* out, size_t os, size_t ofs);
 int mean_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W,

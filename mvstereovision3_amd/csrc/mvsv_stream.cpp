@@ -32,6 +32,12 @@
 // its own HIP stream and scratch buffers), so up to n frame-batch launches run
 // concurrently and one fills the chip's gaps left by another's
 // latency-bound kernels.
+// A stream runs one matcher at a time, SGBM or StereoBM (mvsv_stream_create_bm,
+// mvsv_stream_set_bm_params: trgt/disparityTest.cpp:267-268 runs both on every
+// pair); everything behind the matcher is a function of the int16 map.
+// With mvsv_stream_enable_bgr, a stream of rectified pairs also takes interleaved
+// BGR pairs (mvsv_stream_push_bgr): uploaded once as BGR, halved and converted to
+// grey into the slot's dL / dR ahead of the matcher (disparityTest.cpp:201-211).
 // The host copies of a frame (caller rows -> pinned slot on push, pinned map ->
 // caller rows on pop) are split over a small pool of copy threads that the
 // stream owns (MVSV_STREAM_COPY_THREADS, default 4 including the caller), so a
@@ -148,8 +154,11 @@ struct mvsv_stream {
     std::vector<mvsv_ctx*> lanes;  // [0] = ctx; the rest are owned by the stream
     long runs = 0;                 // launches enqueued (lane = runs % lanes)
     int W = 0, H = 0;
+    int matcher = MVSV_MATCHER_SGBM;  // of the frames pushed from now on
     mvsv_sgbm_params params{};
     SgbmEff eff{};
+    mvsv_bm_params bm_params{};
+    BmEff bm_eff{};
     bool grid = false;
     mvsv_rect roi{};
     hipStream_t up = nullptr, down = nullptr;
@@ -157,6 +166,8 @@ struct mvsv_stream {
         uint8_t *hL = nullptr, *hR = nullptr;  // pinned
         uint8_t *hRectL = nullptr, *hRectR = nullptr;  // pinned, keep_rectified streams
         uint8_t* dRaw = nullptr;                       // [2][rawH][rawW], raw streams
+        uint8_t *hBgr = nullptr, *dBgr = nullptr;      // [2][bgrH][bgrRow], pinned / device, with enable_bgr
+        bool is_bgr = false;                           // the pending frame was pushed as BGR
         int16_t* hOut = nullptr;
         float* hMeans = nullptr;
         uint8_t *dL = nullptr, *dR = nullptr;
@@ -245,7 +256,25 @@ struct mvsv_stream {
     mvsv_rect sharp_roi[2] = {};
     int64_t* dSharp = nullptr;  // [depth][2]
     int64_t* hSharp = nullptr;  // pinned, [depth][2]
+    // colour frames (mvsv_stream_enable_bgr): a pushed BGR pair is staged per slot and
+    // prepared into the slot's dL / dR on the lane's stream
+    bool bgr = false;
+    int bgrW = 0, bgrH = 0, bgr_halve = 0, bgr_variant = 0;
+    size_t bgrRow = 0;            // bytes per staged row: 3 * bgrW rounded up to 4 (packed loads)
+    uint8_t* dBgr_all = nullptr;  // [depth][2][bgrH][bgrRow]
 };
+
+static void bgr_free(mvsv_stream* st)
+{
+    for (auto& s : st->slots) {
+        if (s.hBgr) (void)hipHostFree(s.hBgr);
+        s.hBgr = s.dBgr = nullptr;
+        s.is_bgr = false;
+    }
+    if (st->dBgr_all) (void)hipFree(st->dBgr_all);
+    st->dBgr_all = nullptr;
+    st->bgr = false;
+}
 
 static void sharpness_free(mvsv_stream* st)
 {
@@ -338,6 +367,7 @@ static void stream_free(mvsv_stream* st)
     view_free(st);
     cloud_free(st);
     sharpness_free(st);
+    bgr_free(st);
     if (st->rep) (void)hipHostFree(st->rep);
     if (st->up) (void)hipStreamDestroy(st->up);
     if (st->down) (void)hipStreamDestroy(st->down);
@@ -372,13 +402,30 @@ static bool upload_maps(mvsv_stream* st, const mvsv_rectification* r)
                hipSuccess;
 }
 
-static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, int depth,
+// The copy pool, once a frame's host copies are large enough to be worth splitting.
+static void stream_pool(mvsv_stream* st, size_t frame_bytes)
+{
+    if (st->pool || frame_bytes < kPoolMinBytes) return;
+    int threads = 4;
+    if (const char* v = std::getenv("MVSV_STREAM_COPY_THREADS")) threads = std::max(1, std::min(16, std::atoi(v)));
+    if (threads > 1) {
+        try {
+            st->pool = new CopyPool(threads);
+        } catch (...) {
+            st->pool = nullptr;  // copies on the caller's thread
+        }
+    }
+}
+
+// p: an SGBM stream; bp (p null): a StereoBM stream
+static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, const mvsv_bm_params* bp, int depth,
                          const mvsv_rect* grid_roi, const RawSetup* raw, mvsv_stream** out)
 {
     if (depth < 1 || depth > 64) return set_error(ctx, MVSV_E_INVALID_ARG, "stream depth must be 1..64");
-    SgbmEff e;
+    SgbmEff e{};
+    BmEff be{};
     std::string why;
-    int rc = resolve_sgbm(p, W, H, &e, &why);
+    int rc = p ? resolve_sgbm(p, W, H, &e, &why) : resolve_bm(bp, W, H, &be, &why);
     if (rc) return set_error(ctx, rc, why);
     if (grid_roi && (grid_roi->x0 < 0 || grid_roi->y0 < 0 || grid_roi->x1 > W || grid_roi->y1 > H ||
                      grid_roi->x1 - grid_roi->x0 < 9 || grid_roi->y1 - grid_roi->y0 < 9))
@@ -390,8 +437,14 @@ static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p,
     st->lanes.push_back(ctx);
     st->W = W;
     st->H = H;
-    st->params = *p;
-    st->eff = e;
+    if (p) {
+        st->params = *p;
+        st->eff = e;
+    } else {
+        st->matcher = MVSV_MATCHER_BM;
+        st->bm_params = *bp;
+        st->bm_eff = be;
+    }
     st->grid = grid_roi != nullptr;
     if (grid_roi) st->roi = *grid_roi;
     const size_t px = (size_t)W * H;
@@ -440,17 +493,7 @@ static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p,
              hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
     }
     ok = ok && alloc_report(ctx, depth, &st->rep, &st->rep_dev) == MVSV_OK;
-    if (ok && std::max(px, in_px) * 2 >= kPoolMinBytes) {
-        int threads = 4;
-        if (const char* v = std::getenv("MVSV_STREAM_COPY_THREADS")) threads = std::max(1, std::min(16, std::atoi(v)));
-        if (threads > 1) {
-            try {
-                st->pool = new CopyPool(threads);
-            } catch (...) {
-                st->pool = nullptr;  // copies on the caller's thread
-            }
-        }
-    }
+    if (ok) stream_pool(st, std::max(px, in_px) * 2);
     if (!ok) {
         (void)hipGetLastError();
         stream_free(st);
@@ -465,14 +508,21 @@ int mvsv_stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p, i
 {
     if (!ctx || !out) return MVSV_E_INVALID_ARG;
     *out = nullptr;
-    return stream_create(ctx, W, H, p, depth, grid_roi, nullptr, out);
+    return stream_create(ctx, W, H, p, nullptr, depth, grid_roi, nullptr, out);
 }
 
-int mvsv_stream_create_raw(mvsv_ctx* ctx, const mvsv_rectification* r, const mvsv_sgbm_params* p, int depth,
-                           const mvsv_rect* grid_roi, mvsv_stream** out)
+int mvsv_stream_create_bm(mvsv_ctx* ctx, int W, int H, const mvsv_bm_params* p, int depth, const mvsv_rect* grid_roi,
+                          mvsv_stream** out)
 {
     if (!ctx || !out) return MVSV_E_INVALID_ARG;
     *out = nullptr;
+    if (!p) return set_error(ctx, MVSV_E_INVALID_ARG, "null StereoBM parameters");
+    return stream_create(ctx, W, H, nullptr, p, depth, grid_roi, nullptr, out);
+}
+
+static int stream_create_raw(mvsv_ctx* ctx, const mvsv_rectification* r, const mvsv_sgbm_params* p,
+                             const mvsv_bm_params* bp, int depth, const mvsv_rect* grid_roi, mvsv_stream** out)
+{
     if (!r) return set_error(ctx, MVSV_E_INVALID_ARG, "null rectification");
     // the kernel's tap coordinates are shorts (cv::remap's own limit)
     if (r->raw_width < 1 || r->raw_height < 1 || r->raw_width > 32767 || r->raw_height > 32767)
@@ -491,8 +541,27 @@ int mvsv_stream_create_raw(mvsv_ctx* ctx, const mvsv_rectification* r, const mvs
             return set_error(ctx, MVSV_E_INVALID_ARG, "bad resize factor");
         raw.resized = true;
     }
-    return stream_create(ctx, W, H, p, depth, grid_roi, &raw, out);
+    return stream_create(ctx, W, H, p, bp, depth, grid_roi, &raw, out);
 }
+
+int mvsv_stream_create_raw(mvsv_ctx* ctx, const mvsv_rectification* r, const mvsv_sgbm_params* p, int depth,
+                           const mvsv_rect* grid_roi, mvsv_stream** out)
+{
+    if (!ctx || !out) return MVSV_E_INVALID_ARG;
+    *out = nullptr;
+    return stream_create_raw(ctx, r, p, nullptr, depth, grid_roi, out);
+}
+
+int mvsv_stream_create_raw_bm(mvsv_ctx* ctx, const mvsv_rectification* r, const mvsv_bm_params* p, int depth,
+                              const mvsv_rect* grid_roi, mvsv_stream** out)
+{
+    if (!ctx || !out) return MVSV_E_INVALID_ARG;
+    *out = nullptr;
+    if (!p) return set_error(ctx, MVSV_E_INVALID_ARG, "null StereoBM parameters");
+    return stream_create_raw(ctx, r, nullptr, p, depth, grid_roi, out);
+}
+
+int mvsv_stream_matcher(const mvsv_stream* st) { return st ? st->matcher : -1; }
 
 int mvsv_stream_size(const mvsv_stream* st, int* width, int* height)
 {
@@ -523,6 +592,30 @@ static int stream_rectify(mvsv_stream* st, mvsv_ctx* ctx, long i0, int n)
                          st->W, px);
 }
 
+// The frames of a run that were pushed as BGR: their grey pairs into the slots'
+// dL / dR on the lane's stream, one launch per side and stretch of such slots.
+static int stream_prepare(mvsv_stream* st, mvsv_ctx* ctx, long i0, int n)
+{
+    const size_t px = (size_t)st->W * st->H, side = (size_t)st->bgrH * st->bgrRow;
+    for (int k = 0; k < n;) {
+        if (!st->slots[i0 + k].is_bgr) {
+            k++;
+            continue;
+        }
+        int m = 1;
+        while (k + m < n && st->slots[i0 + k + m].is_bgr) m++;
+        auto& s = st->slots[i0 + k];
+        int rc;
+        if ((rc = prepare_gray_device(ctx, m, s.dBgr, st->bgrRow, 2 * side, st->bgrW, st->bgrH, st->bgr_halve,
+                                      st->bgr_variant, s.dL, st->W, px)) ||
+            (rc = prepare_gray_device(ctx, m, s.dBgr + side, st->bgrRow, 2 * side, st->bgrW, st->bgrH, st->bgr_halve,
+                                      st->bgr_variant, s.dR, st->W, px)))
+            return rc;
+        k += m;
+    }
+    return MVSV_OK;
+}
+
 // Enqueue compute + download for the pushed frames [launched, head): one
 // frame-batch launch per run of consecutive slots (a run ends at the ring's end).
 static int stream_launch(mvsv_stream* st)
@@ -546,9 +639,11 @@ static int stream_launch(mvsv_stream* st)
         first.run_len = n;
         int* prev_target = ctx->report_target;
         ctx->report_target = st->rep_dev + i0;
-        int status = st->raw ? stream_rectify(st, ctx, i0, n) : MVSV_OK;
+        int status = st->raw ? stream_rectify(st, ctx, i0, n) : st->bgr ? stream_prepare(st, ctx, i0, n) : MVSV_OK;
         if (status == MVSV_OK)
-            status = sgbm_device(ctx, n, first.dL, W, px, first.dR, W, px, W, H, st->eff, first.dOut, W, px);
+            status = st->matcher == MVSV_MATCHER_BM
+                         ? bm_device(ctx, n, first.dL, W, px, first.dR, W, px, W, H, st->bm_eff, first.dOut, W, px)
+                         : sgbm_device(ctx, n, first.dL, W, px, first.dR, W, px, W, H, st->eff, first.dOut, W, px);
         ctx->report_target = prev_target;
         if (status == MVSV_OK && st->grid) {
             const mvsv_rect& q = st->roi;
@@ -739,6 +834,22 @@ int mvsv_stream_set_params(mvsv_stream* st, const mvsv_sgbm_params* p)
     if ((rc = stream_launch(st))) return rc;  // pending frames keep the old parameters
     st->params = *p;  // applies to frames pushed from now on (trgt/mean_test.cpp:348 setters)
     st->eff = e;
+    st->matcher = MVSV_MATCHER_SGBM;
+    return MVSV_OK;
+}
+
+int mvsv_stream_set_bm_params(mvsv_stream* st, const mvsv_bm_params* p)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    BmEff e;
+    std::string why;
+    int rc = resolve_bm(p, st->W, st->H, &e, &why);
+    if (rc) return set_error(st->ctx, rc, why);
+    DeviceGuard dev_guard(st->ctx->device);
+    if ((rc = stream_launch(st))) return rc;  // pending frames keep their matcher and parameters
+    st->bm_params = *p;
+    st->bm_eff = e;
+    st->matcher = MVSV_MATCHER_BM;
     return MVSV_OK;
 }
 
@@ -755,6 +866,7 @@ int mvsv_stream_push(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t
         return set_error(ctx, MVSV_E_INVALID_ARG, "stream full: pop a frame first");
     DeviceGuard dev_guard(ctx->device);
     auto& s = st->slots[st->head % st->slots.size()];
+    s.is_bgr = false;
     const int W = st->W, H = st->H;
     // the slot's previous frame was popped, so its copies are complete
     auto copy_in = [&](int part, int parts) {
@@ -773,6 +885,86 @@ int mvsv_stream_push(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t
         return rc;
     st->head++;
     // a full group, or a group that would otherwise wrap past the ring's end
+    if (ring_launch_after_push(st->head, st->launched, st->batch, (long)st->slots.size()))
+        return stream_launch(st);
+    return MVSV_OK;
+}
+
+int mvsv_stream_disable_bgr(mvsv_stream* st)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (st->head != st->tail)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "colour input changes only while no frame is pending");
+    DeviceGuard dev_guard(st->ctx->device);
+    bgr_free(st);  // every frame was popped: nothing in flight uses the buffers
+    return MVSV_OK;
+}
+
+int mvsv_stream_enable_bgr(mvsv_stream* st, int sw, int sh, int halve, int variant)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (st->raw) return set_error(ctx, MVSV_E_INVALID_ARG, "colour input is for streams of rectified pairs");
+    if (st->head != st->tail)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "colour input changes only while no frame is pending");
+    int dw, dh;
+    if (prepare_size(sw, sh, halve, &dw, &dh) || dw != st->W || dh != st->H)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "mvsv_prepare_size of the colour frame is not the stream's size");
+    if (variant != MVSV_GRAY_Q14 && variant != MVSV_GRAY_Q15)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "unknown grey variant");
+    DeviceGuard dev_guard(ctx->device);
+    bgr_free(st);
+    st->bgrW = sw;
+    st->bgrH = sh;
+    st->bgr_halve = halve;
+    st->bgr_variant = variant;
+    st->bgrRow = (3 * (size_t)sw + 3) & ~(size_t)3;
+    const size_t pair = 2 * (size_t)sh * st->bgrRow;
+    bool ok = hipMalloc((void**)&st->dBgr_all, pair * st->slots.size()) == hipSuccess;
+    for (size_t i = 0; ok && i < st->slots.size(); i++) {
+        st->slots[i].dBgr = st->dBgr_all + i * pair;
+        ok = hipHostMalloc((void**)&st->slots[i].hBgr, pair, hipHostMallocDefault) == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        bgr_free(st);
+        return set_error(ctx, MVSV_E_OOM, "colour staging allocation failed");
+    }
+    stream_pool(st, pair);
+    st->bgr = true;
+    return MVSV_OK;
+}
+
+int mvsv_stream_push_bgr(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (st->raw) return set_error(ctx, MVSV_E_INVALID_ARG, "raw stream: push raw pairs with mvsv_stream_push_raw");
+    if (!st->bgr) return set_error(ctx, MVSV_E_INVALID_ARG, "colour input is not enabled on this stream");
+    const size_t row = 3 * (size_t)st->bgrW;
+    if (!L || !R || ls < row || rs < row)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "null frame or stride smaller than three times the width");
+    if (ring_full(st->head, st->tail, (long)st->slots.size()))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "stream full: pop a frame first");
+    DeviceGuard dev_guard(ctx->device);
+    auto& s = st->slots[st->head % st->slots.size()];
+    const int H = st->bgrH;
+    const size_t side = (size_t)H * st->bgrRow;
+    // the slot's previous frame was popped, so its copies and its preparation are complete
+    auto copy_in = [&](int part, int parts) {
+        copy_rows(s.hBgr, st->bgrRow, L, ls, row, H, part, parts);
+        copy_rows(s.hBgr + side, st->bgrRow, R, rs, row, H, part, parts);
+    };
+    if (st->pool)
+        st->pool->run(copy_in);
+    else
+        copy_in(0, 1);
+    int rc;
+    if ((rc = check_hip(ctx, hipMemcpyAsync(s.dBgr, s.hBgr, 2 * side, hipMemcpyHostToDevice, st->up), "stream H2D")) ||
+        (rc = check_hip(ctx, hipEventRecord(s.uploaded, st->up), "stream event")))
+        return rc;
+    s.is_bgr = true;
+    st->head++;
     if (ring_launch_after_push(st->head, st->launched, st->batch, (long)st->slots.size()))
         return stream_launch(st);
     return MVSV_OK;

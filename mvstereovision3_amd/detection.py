@@ -407,19 +407,37 @@ class DisparityStream:
     up to that many groups run concurrently on the stream's compute lanes.
     DisparityStream.raw(...) opens the same pipeline for raw camera pairs
     (push_raw): rectification, crop and resize run on the device too.
+    matcher: a StereoSGBM or a StereoBM (mvsv_stream_create_bm), here and in
+    set_params, which may switch between the two; anything else raises.
+    enable_bgr / push_bgr: colour pairs, halved and converted on the device.
     """
+
+    @staticmethod
+    def _matcher_kind(matcher):
+        """MATCHER_SGBM / MATCHER_BM of a matcher object, by its parameter block."""
+        p = getattr(matcher, "_params", None)
+        if isinstance(p, _lib.SgbmParams):
+            return _lib.MATCHER_SGBM
+        if isinstance(p, _lib.BmParams):
+            return _lib.MATCHER_BM
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG,
+                        f"DisparityStream: a StereoSGBM or StereoBM matcher expected, not {type(matcher).__name__}")
 
     def __init__(self, matcher, width, height, depth=3, grid_roi=None, device=0, batch=1,
                  inflight=1):
+        self._h = None
+        self._close_pending = False
+        kind = self._matcher_kind(matcher)
         self._ctx = context(device)
         self.width, self.height = width, height
         self._params = matcher._params
         self._grid = grid_roi is not None
         roi = Rect(*grid_roi) if grid_roi is not None else None
         h = ctypes.c_void_p()
-        check(lib().mvsv_stream_create(self._ctx.handle, width, height, ctypes.byref(self._params),
-                                       depth, ctypes.byref(roi) if roi is not None else None,
-                                       ctypes.byref(h)), self._ctx.handle)
+        create = lib().mvsv_stream_create_bm if kind == _lib.MATCHER_BM else lib().mvsv_stream_create
+        check(create(self._ctx.handle, width, height, ctypes.byref(self._params),
+                     depth, ctypes.byref(roi) if roi is not None else None,
+                     ctypes.byref(h)), self._ctx.handle)
         self._raw_shape = None
         self._keep = False
         self._opened(h, batch, inflight)
@@ -443,6 +461,7 @@ class DisparityStream:
         returns the unresized crop (src/Stereosystem.cpp:298-311) does not apply
         here.  keep_rectified: pop(rectified=True) also returns the rectified pair.
         """
+        kind = cls._matcher_kind(matcher)
         s = stereosystem_or_maps
         if hasattr(s, "initRectification"):
             if not s.mIsInit and not s.initRectification():
@@ -473,9 +492,10 @@ class DisparityStream:
         h = ctypes.c_void_p()
         self._h = None
         self._close_pending = False
-        check(lib().mvsv_stream_create_raw(self._ctx.handle, ctypes.byref(r), ctypes.byref(self._params),
-                                           depth, ctypes.byref(g) if g is not None else None,
-                                           ctypes.byref(h)), self._ctx.handle)
+        create = lib().mvsv_stream_create_raw_bm if kind == _lib.MATCHER_BM else lib().mvsv_stream_create_raw
+        check(create(self._ctx.handle, ctypes.byref(r), ctypes.byref(self._params),
+                     depth, ctypes.byref(g) if g is not None else None,
+                     ctypes.byref(h)), self._ctx.handle)
         w, hh = ctypes.c_int(), ctypes.c_int()
         check(lib().mvsv_stream_size(h, ctypes.byref(w), ctypes.byref(hh)), self._ctx.handle)
         self.width, self.height = w.value, hh.value
@@ -508,8 +528,47 @@ class DisparityStream:
         check(lib().mvsv_stream_set_batch(self._h, int(batch)), self._ctx.handle)
 
     def set_params(self, matcher):
+        """New parameters -- and the matcher, StereoSGBM or StereoBM -- for the frames
+        pushed from now on (mvsv_stream_set_params / mvsv_stream_set_bm_params)."""
+        kind = self._matcher_kind(matcher)
+        setter = lib().mvsv_stream_set_bm_params if kind == _lib.MATCHER_BM else lib().mvsv_stream_set_params
+        check(setter(self._live(), ctypes.byref(matcher._params)), self._ctx.handle)
         self._params = matcher._params
-        check(lib().mvsv_stream_set_params(self._h, ctypes.byref(self._params)), self._ctx.handle)
+
+    def matcher(self):
+        """MATCHER_SGBM or MATCHER_BM: what computes the frames pushed from now on."""
+        return int(lib().mvsv_stream_matcher(self._live()))
+
+    def enable_bgr(self, src_shape, halve=True, variant=_lib.GRAY_Q14):
+        """The stream (of rectified pairs) also takes colour pairs from now on:
+        src_shape = (height, width) of the BGR frames, whose prepare_size must be the
+        stream's size; each pushed pair is uploaded as BGR and utility.prepare_gray
+        runs on the device ahead of the matcher (mvsv_stream_enable_bgr).  Only while
+        no frame is pending.  A BGR frame's sharpness is that of its prepared pair."""
+        h, w = int(src_shape[0]), int(src_shape[1])
+        check(lib().mvsv_stream_enable_bgr(self._live(), w, h, 1 if halve else 0, int(variant)), self._ctx.handle)
+        self._bgr_shape = (h, w, 3)
+
+    def disable_bgr(self):
+        check(lib().mvsv_stream_disable_bgr(self._live()), self._ctx.handle)
+        self._bgr_shape = None
+
+    def push_bgr(self, left, right):
+        """Push a colour pair: uint8 (height, width, 3) BGR arrays of enable_bgr's shape."""
+        self._live()
+        shape = getattr(self, "_bgr_shape", None)
+        if shape is None:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "push_bgr: enable_bgr first (a stream of rectified pairs)")
+        L = np.asarray(left)
+        R = np.asarray(right)
+        if L.shape != shape or R.shape != shape or L.dtype != np.uint8 or R.dtype != np.uint8:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "push_bgr: uint8 BGR pair of enable_bgr's shape expected")
+        if L.strides[1:] != (3, 1):
+            L = np.ascontiguousarray(L)
+        if R.strides[1:] != (3, 1):
+            R = np.ascontiguousarray(R)
+        check(lib().mvsv_stream_push_bgr(self._h, L.ctypes.data, L.strides[0], R.ctypes.data, R.strides[0]),
+              self._ctx.handle)
 
     def pending(self):
         return int(lib().mvsv_stream_pending(self._h))

@@ -193,6 +193,61 @@ def sharpness(frames, roi=None, return_sums=False):
     return (values, sums) if return_sums else values
 
 
+def prepare_size(src_width, src_height, halve=True):
+    """(width, height) of the grey image prepare_gray makes (mvsv_prepare_size):
+    cvRound of half of each side when halving, half to even."""
+    w, h = ctypes.c_int(), ctypes.c_int()
+    check(lib().mvsv_prepare_size(int(src_width), int(src_height), 1 if halve else 0, ctypes.byref(w),
+                                  ctypes.byref(h)))
+    return w.value, h.value
+
+
+def prepare_gray(bgr, halve=True, variant=_lib.GRAY_Q14):
+    """What trgt/disparityTest.cpp does to a colour image ahead of the matchers
+    (:201-211), on the GPU in one kernel: with halve, cv::resize(.., 0.5, 0.5,
+    INTER_AREA) of the 3-channel image, then cv::cvtColor(BGR2GRAY); variant
+    GRAY_Q14 (OpenCV up to the early 3.4 releases) or GRAY_Q15 (later ones).
+
+    bgr: uint8 interleaved BGR, (H, W, 3) or a batch (N, H, W, 3).  A torch device
+    tensor (any view whose pixels are 3 contiguous bytes, columns 3 bytes apart)
+    gives a uint8 device tensor (h, w) / (N, h, w), asynchronously on the current
+    stream; a numpy array gives a numpy array."""
+    hv = 1 if halve else 0
+    if type(bgr).__module__.startswith("torch"):
+        import torch
+        if not (bgr.is_cuda and bgr.dtype == torch.uint8 and bgr.dim() in (3, 4) and bgr.shape[-1] == 3):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "prepare_gray: uint8 device tensor (H, W, 3) or (N, H, W, 3) expected")
+        batched = bgr.dim() == 4
+        d = bgr if batched else bgr.unsqueeze(0)
+        if d.stride(3) != 1 or d.stride(2) != 3:
+            d = d.contiguous()
+        n, H, W, _ = d.shape
+        w, h = prepare_size(W, H, halve)
+        ctx = context(bgr.device.index or 0)
+        check(lib().mvsv_set_stream(ctx.handle, ctypes.c_void_p(torch.cuda.current_stream(bgr.device).cuda_stream)),
+              ctx.handle)
+        out = torch.empty((n, h, w), dtype=torch.uint8, device=bgr.device)
+        check(lib().mvsv_prepare_gray_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H, hv,
+                                             int(variant), out.data_ptr(), w, h * w), ctx.handle)
+        return out if batched else out[0]
+    a = np.asarray(bgr)
+    if a.ndim not in (3, 4) or a.dtype != np.uint8 or a.shape[-1] != 3:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "prepare_gray: uint8 image (H, W, 3) or (N, H, W, 3) expected")
+    if a.strides[-2:] != (3, 1):
+        a = np.ascontiguousarray(a)
+    batched = a.ndim == 4
+    H, W = a.shape[-3:-1]
+    w, h = prepare_size(W, H, halve)
+    frames = a if batched else a[None]
+    out = np.empty((len(frames), h, w), np.uint8)
+    ctx = context(0)
+    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    for f, o in zip(frames, out):
+        check(lib().mvsv_prepare_gray(ctx.handle, f.ctypes.data, f.strides[0], W, H, hv, int(variant), o.ctypes.data,
+                                      w), ctx.handle)
+    return out if batched else out[0]
+
+
 def reproject(dmap, Q):
     """Utility::calcCoordinate for every pixel of an int16 device map, on the GPU.
 

@@ -9,7 +9,14 @@ Host frames go in, int16 maps and the 81 tile means come back (PCIe included);
 `depth` frames are in flight, computed `batch` at a time.  Also reports the device-resident rate of the same
 matcher on a batch of 8 frames.  Not the headline metric (bench.py is).
 
+--matcher bm / bm-yml: the same loop with StereoBM as the stream's matcher (what
+trgt/disparityTest.cpp:268 runs beside SGBM): StereoBM::create(64, 9), or the values
+of tests/golden/configs/bm.yml.  --bgr: the frames are pushed as 2W x 2H colour
+pairs (mvsv_stream_push_bgr), halved and converted on the device (:201-211); the
+device-resident figure then includes prepare_gray of the batch.
+
     python tools/bench_stream.py [--frames 300] [--depth 24] [--batch 8] [--inflight 2]
+                                 [--matcher sgbm|bm|bm-yml] [--bgr]
 """
 import argparse
 import json
@@ -22,14 +29,23 @@ sys.path.insert(0, ROOT)
 
 
 def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=2, pop="view",
-                   host_probe="full", device_steps=10):
+                   host_probe="full", device_steps=10, matcher="sgbm", bgr=False):
     """The config-5 stream (liveDisparity matcher + MeanDisparityDetection post-pass
     on every frame, host frames in / maps and means out) -> one result dict."""
     import numpy as np
     import torch
 
-    D = 256
-    m = mvsv.StereoSGBM.create(0, D, 9, 8 * 81, 32 * 81)  # trgt/liveDisparity.cpp:61
+    if matcher == "sgbm":
+        m = mvsv.StereoSGBM.create(0, 256, 9, 8 * 81, 32 * 81)  # trgt/liveDisparity.cpp:61
+    elif matcher == "bm":
+        m = mvsv.StereoBM.create(64, 9)
+    elif matcher == "bm-yml":
+        m = mvsv.StereoBM.create(16, 9)
+        if not mvsv.Disparity.loadBMParameters(os.path.join(ROOT, "tests", "golden", "configs", "bm.yml"), m):
+            raise SystemExit("bm.yml cannot be loaded")
+    else:
+        raise SystemExit(f"unknown matcher {matcher}")
+    D = m.getNumDisparities()
     q = json.load(open(os.path.join(ROOT, "tests", "golden", "q_matrix.json")))["Q"]
     Q = np.array(q, np.float32).reshape(4, 4)
     Q[0, 3] *= 2  # afterCalibrationParameters.yml is for 752x480: x2 for 1280x960-class sensors
@@ -38,9 +54,16 @@ def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=
     roi_u, _ = mvsv.create_dmap_rois((H, W), D)
     det = mvsv.MeanDisparityDetection()
     det.init((roi_u[3] - roi_u[1], roi_u[2] - roi_u[0]), Q, 0.1, 1.5)
-    uniq = [mvsv.synth_pair(0x5EED0000 + i, W, H, 0, D) for i in range(8)]
+    if bgr:  # colour frames of twice the size: the grey synthetic pair in every channel
+        uniq = [tuple(np.ascontiguousarray(np.repeat(g[..., None], 3, axis=2))
+                      for g in mvsv.synth_pair(0x5EED0000 + i, 2 * W, 2 * H, 0, 2 * D)) for i in range(8)]
+    else:
+        uniq = [mvsv.synth_pair(0x5EED0000 + i, W, H, 0, D) for i in range(8)]
 
     st = mvsv.DisparityStream(m, W, H, depth=depth, grid_roi=roi_u, batch=batch, inflight=inflight)
+    if bgr:
+        st.enable_bgr((2 * H, 2 * W))
+    push = st.push_bgr if bgr else st.push
     found = 0
     host = {"push": 0.0, "pop": 0.0, "post": 0.0}
 
@@ -60,7 +83,7 @@ def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=
         host["post"] += time.perf_counter() - t2
 
     for i in range(depth):  # warm-up
-        st.push(*uniq[i % 8])
+        push(*uniq[i % 8])
     while st.pending():
         consume()
     host = dict.fromkeys(host, 0.0)
@@ -69,7 +92,7 @@ def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=
         if st.pending() == depth:
             consume()
         t = time.perf_counter()
-        st.push(*uniq[i % 8])
+        push(*uniq[i % 8])
         host["push"] += time.perf_counter() - t
     while st.pending():
         consume()
@@ -81,17 +104,25 @@ def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=
     Lt = torch.from_numpy(np.stack([u[0] for u in uniq])).to(dev)
     Rt = torch.from_numpy(np.stack([u[1] for u in uniq])).to(dev)
     out = torch.empty((8, H, W), dtype=torch.int16, device=dev)
+
+    def compute():
+        if bgr:
+            m.compute(mvsv.prepare_gray(Lt), mvsv.prepare_gray(Rt), out)
+        else:
+            m.compute(Lt, Rt, out)
+
     for _ in range(2):
-        m.compute(Lt, Rt, out)
+        compute()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     for _ in range(device_steps):
-        m.compute(Lt, Rt, out)
+        compute()
         mvsv.mean_disparity_grid(out[:, roi_u[1]:roi_u[3], roi_u[0]:roi_u[2]])
     torch.cuda.synchronize()
     dwall = time.perf_counter() - t1
     return {
-        "workload": f"config5_stream_{W}x{H}_d{D}_mode_sgbm",
+        "workload": f"config5_stream_{W}x{H}_d{D}_mode_sgbm" if matcher == "sgbm" and not bgr else
+                    f"stream_{W}x{H}_d{D}_{matcher}{'_bgr' if bgr else ''}",
         "frames": frames, "depth": depth, "batch": batch, "inflight": inflight,
         "host_probe": host_probe, "pop": pop,
         "stream_fps": round(frames / wall, 2),
@@ -118,12 +149,16 @@ def main():
                          "or a copy into a fresh array (mvsv_stream_pop)")
     ap.add_argument("--host-probe", choices=["full", "no-post", "no-copy"], default="full",
                     help="diagnostics: skip the detection post-pass, or also the map copy of pop")
+    ap.add_argument("--matcher", choices=["sgbm", "bm", "bm-yml"], default="sgbm",
+                    help="the stream's matcher: config 5's SGBM, StereoBM(64, 9), or StereoBM with bm.yml's values")
+    ap.add_argument("--bgr", action="store_true",
+                    help="push 2W x 2H colour pairs; the device halves and converts them (mvsv_stream_push_bgr)")
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=960)
     a = ap.parse_args()
     import mvstereovision3_amd as mvsv
     print(json.dumps(stream_measure(mvsv, a.width, a.height, a.frames, a.depth, a.batch, a.inflight, a.pop,
-                                    a.host_probe)))
+                                    a.host_probe, matcher=a.matcher, bgr=a.bgr)))
 
 
 if __name__ == "__main__":
