@@ -80,6 +80,9 @@
  *   _create_raw_bm / _set_bm_params   matcher, beside Disparity::sgbm (:267)
  *   mvsv_stream_enable_bgr /          colour pairs into a stream: uploaded as BGR, prepared on
  *   _push_bgr                         the device ahead of the matcher
+ *   mvsv_stream_push*_device /        the same loops for a producer and a consumer on the GPU:
+ *   _pop_device / _front_*_device /   frames from device memory, results read where they lie (no
+ *   _set_host_outputs / _fence        counterpart in the reference, whose images live in cv::Mat)
  *
  * Conventions
  *   - Plain C types only; no exceptions cross this boundary.
@@ -726,6 +729,59 @@ MVSV_API int mvsv_stream_enable_bgr(mvsv_stream* s, int src_width, int src_heigh
 MVSV_API int mvsv_stream_disable_bgr(mvsv_stream* s);
 MVSV_API int mvsv_stream_push_bgr(mvsv_stream* s, const uint8_t* left, size_t left_stride, const uint8_t* right,
                                   size_t right_stride);
+
+/* ---- device ends of a stream: frames from device memory, maps handed back there ------
+ * mvsv_stream_push_device / _push_raw_device / _push_bgr_device: n >= 1 frames (strides in
+ * bytes, frame strides between consecutive frames; rows of width, raw_width or
+ * 3 * src_width bytes) become n consecutive pushes -- the frames, their order, the launch
+ * grouping by `batch` and the behaviour at the ring's wrap are those of n single pushes.
+ * n > depth - pending is MVSV_E_INVALID_ARG and pushes nothing; the kind of stream is
+ * checked as by the host calls.  The sources must be memory of the stream's device or
+ * device-accessible host memory (pinned, managed): anything else is MVSV_E_INVALID_ARG
+ * before anything is enqueued.
+ * Ordering is by events, without host synchronisation: the copy into the slots (one
+ * kernel launch per contiguous piece of the ring, so at most two) waits for what is
+ * queued on producer_stream (NULL: the legacy null stream) at the call, and
+ * producer_stream is made to wait for the copy: what the caller enqueues on it after the
+ * call may overwrite or free the sources. */
+MVSV_API int mvsv_stream_push_device(mvsv_stream* s, int n, const uint8_t* left, size_t left_stride,
+                                     size_t left_frame_stride, const uint8_t* right, size_t right_stride,
+                                     size_t right_frame_stride, void* producer_stream);
+MVSV_API int mvsv_stream_push_raw_device(mvsv_stream* s, int n, const uint8_t* left, size_t left_stride,
+                                         size_t left_frame_stride, const uint8_t* right, size_t right_stride,
+                                         size_t right_frame_stride, void* producer_stream);
+MVSV_API int mvsv_stream_push_bgr_device(mvsv_stream* s, int n, const uint8_t* left, size_t left_stride,
+                                         size_t left_frame_stride, const uint8_t* right, size_t right_stride,
+                                         size_t right_frame_stride, void* producer_stream);
+/* Which per-frame products are also copied to the stream's pinned host slots (default:
+ * all).  Only while no frame is pending.  A host getter of a product that is switched
+ * off -- pop / pop_pair with a non-NULL out, pop_view, pop_pair's rectified outputs,
+ * front_display*, front_view* -- returns MVSV_E_INVALID_ARG and leaves the frame pending;
+ * pop with out == NULL still pops.  The means, the sample points, the cloud header, the
+ * sharpness and the display / view (min, max) always come to the host. */
+#define MVSV_HOST_MAP 1
+#define MVSV_HOST_RECTIFIED 2
+#define MVSV_HOST_DISPLAY 4
+#define MVSV_HOST_VIEW 8
+#define MVSV_HOST_ALL 15
+MVSV_API int mvsv_stream_set_host_outputs(mvsv_stream* s, int mask);
+/* Pops the oldest frame (waiting for it on the host, status and MVSV_E_TIMEOUT as pop) and
+ * enqueues the copy of its map into out_dev (device memory, stride in elements) on
+ * consumer_stream (NULL: the legacy null stream); the slot's next frame waits for that copy. */
+MVSV_API int mvsv_stream_pop_device(mvsv_stream* s, int16_t* out_dev, size_t out_stride, float* means,
+                                    void* consumer_stream);
+/* No pop, no copy: pointers into the stream's device rings (rows contiguous), complete
+ * when the call returns and valid until the frame is popped -- the rule of
+ * front_cloud_device.  They work whether or not the matching host output is on.
+ * front_rectified_device needs a stream created with keep_rectified. */
+MVSV_API int mvsv_stream_front_map_device(mvsv_stream* s, const int16_t** map_dev, float* means);
+MVSV_API int mvsv_stream_front_rectified_device(mvsv_stream* s, const uint8_t** left_dev, const uint8_t** right_dev);
+MVSV_API int mvsv_stream_front_display_device(mvsv_stream* s, const uint8_t** map_dev, int16_t* minmax);
+MVSV_API int mvsv_stream_front_view_device(mvsv_stream* s, const uint8_t** bgr_dev, int16_t* minmax);
+/* Everything the stream enqueues from now on (uploads, launches) waits for what is queued
+ * on hip_stream now: for a zero-copy consumer whose reads of a front_*_device pointer may
+ * still be running when it pops the frame, after which the slot may be pushed again. */
+MVSV_API int mvsv_stream_fence(mvsv_stream* s, void* hip_stream);
 
 /* ---- camera set-up: undistorted pairs (Stereosystem::getUndistortedImagepair) -------
  * cv::undistort(src, dst, K, dist) of OpenCV 3.4 (no new camera matrix: Ar = K) works

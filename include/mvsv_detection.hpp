@@ -781,6 +781,39 @@ public:
         check(mvsv_stream_front_cloud_device(s_, &p, count, minmax), ctx_);
         return p;
     }
+    // ---- device ends (mvsv.h "device ends of a stream") ----
+    // n frames of device memory (or device-accessible host memory), strides in bytes,
+    // as n pushes; ordered against hip_stream (nullptr: the null stream) by events, so
+    // work queued on it after the call may overwrite the frames
+    void pushDevice(int n, const uint8_t* left, size_t left_step, size_t left_frame_step, const uint8_t* right,
+                    size_t right_step, size_t right_frame_step, void* hip_stream = nullptr)
+    {
+        check(mvsv_stream_push_device(s_, n, left, left_step, left_frame_step, right, right_step, right_frame_step,
+                                      hip_stream), ctx_);
+    }
+    // the same for CV_8UC3 frames (enableBgr first)
+    void pushBgrDevice(int n, const uint8_t* left, size_t left_step, size_t left_frame_step, const uint8_t* right,
+                       size_t right_step, size_t right_frame_step, void* hip_stream = nullptr)
+    {
+        check(mvsv_stream_push_bgr_device(s_, n, left, left_step, left_frame_step, right, right_step,
+                                          right_frame_step, hip_stream), ctx_);
+    }
+    // pops; the map is copied into device memory (stride in elements) on hip_stream
+    void popDevice(int16_t* out_dev, size_t out_stride, float* means81 = nullptr, void* hip_stream = nullptr)
+    {
+        check(mvsv_stream_pop_device(s_, out_dev, out_stride, means81, hip_stream), ctx_);
+    }
+    // the oldest pending frame's map in the stream's device ring (dense, no copy), valid until it is popped
+    const int16_t* frontMapDevice(float* means81 = nullptr)
+    {
+        const int16_t* map = nullptr;
+        check(mvsv_stream_front_map_device(s_, &map, means81), ctx_);
+        return map;
+    }
+    // MVSV_HOST_* bits: the per-frame products that are also downloaded (no frame may be pending)
+    void hostOutputs(int mask) { check(mvsv_stream_set_host_outputs(s_, mask), ctx_); }
+    // what the stream enqueues from now on waits for what is queued on hip_stream now
+    void fence(void* hip_stream = nullptr) { check(mvsv_stream_fence(s_, hip_stream), ctx_); }
 
 private:
     mvsv_ctx* ctx_;

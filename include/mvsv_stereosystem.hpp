@@ -411,6 +411,26 @@ public:
                                    rectified ? rectified->mRight.step : 0),
               mCtx);
     }
+    // ---- device ends, as on DisparityStream (mvsv.h "device ends of a stream") ----
+    // n raw pairs of device memory (strides in bytes) as n pushes, ordered against hip_stream by events
+    void pushDevice(int n, const uint8_t* left, size_t left_step, size_t left_frame_step, const uint8_t* right,
+                    size_t right_step, size_t right_frame_step, void* hip_stream = nullptr)
+    {
+        check(mvsv_stream_push_raw_device(mStream, n, left, left_step, left_frame_step, right, right_step,
+                                          right_frame_step, hip_stream), mCtx);
+    }
+    void popDevice(int16_t* out_dev, size_t out_stride, float* means = nullptr, void* hip_stream = nullptr)
+    {
+        check(mvsv_stream_pop_device(mStream, out_dev, out_stride, means, hip_stream), mCtx);
+    }
+    const int16_t* frontMapDevice(float* means = nullptr)
+    {
+        const int16_t* map = nullptr;
+        check(mvsv_stream_front_map_device(mStream, &map, means), mCtx);
+        return map;
+    }
+    void hostOutputs(int mask) { check(mvsv_stream_set_host_outputs(mStream, mask), mCtx); }
+    void fence(void* hip_stream = nullptr) { check(mvsv_stream_fence(mStream, hip_stream), mCtx); }
     // the lattice detector on every frame, as on DisparityStream
     void enableSamplepoints(const SamplepointDetection& d, const Rect* roi = nullptr, int max_hits = 0)
     {

@@ -6,7 +6,8 @@ src/disparity.cpp:6-108).  Compute lives in hand-written HIP kernels for
 gfx950 behind the C ABI of libmvsv.so (include/mvsv.h); this package is the
 host-side mirror of the reference interface.
 """
-from ._lib import (GRAY_Q14, GRAY_Q15, MATCHER_BM, MATCHER_SGBM, MODE_HH, MODE_SGBM, MVSV_E_TIMEOUT, OPT_BITSLICE, OPT_BM_TILE_ROWS, OPT_PATH_SCHEDULE,
+from ._lib import (GRAY_Q14, GRAY_Q15, MATCHER_BM, MATCHER_SGBM, MODE_HH, MODE_SGBM, MVSV_E_TIMEOUT, MVSV_HOST_ALL,
+                   MVSV_HOST_DISPLAY, MVSV_HOST_MAP, MVSV_HOST_RECTIFIED, MVSV_HOST_VIEW, OPT_BITSLICE, OPT_BM_TILE_ROWS, OPT_PATH_SCHEDULE,
                    OPT_STRIP_SPIN_LIMIT, OPT_STRIP_WAVES,
                    PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, VARIANT_FIRSTCOL_FIX,
                    VARIANT_WTA_MIN_D, MvsvError, set_option, synchronize)
@@ -35,5 +36,6 @@ __all__ = [
     "sharpness", "undistort_maps", "remap_fixed", "undistort_pair",
     "detection_view", "View", "VIEW_SUBIMAGE_GRID", "VIEW_OBSTACLE_GRID", "VIEW_FOUND_TILES", "VIEW_FOUND_POINTS",
     "prepare_gray", "prepare_size", "GRAY_Q14", "GRAY_Q15", "MATCHER_SGBM", "MATCHER_BM",
+    "MVSV_HOST_MAP", "MVSV_HOST_RECTIFIED", "MVSV_HOST_DISPLAY", "MVSV_HOST_VIEW", "MVSV_HOST_ALL",
 ]
 __version__ = "1.0.0"

@@ -43,6 +43,11 @@ GRAY_Q14 = 0
 GRAY_Q15 = 1
 MATCHER_SGBM = 0
 MATCHER_BM = 1
+MVSV_HOST_MAP = 1
+MVSV_HOST_RECTIFIED = 2
+MVSV_HOST_DISPLAY = 4
+MVSV_HOST_VIEW = 8
+MVSV_HOST_ALL = 15
 
 NUM_STAGES = 9
 
@@ -219,6 +224,16 @@ def _declare(lib, strict=True):
         "mvsv_stream_enable_bgr": ([P, I, I, I, I], I),
         "mvsv_stream_disable_bgr": ([P], I),
         "mvsv_stream_push_bgr": ([P, P, Z, P, Z], I),
+        "mvsv_stream_push_device": ([P, I, P, Z, Z, P, Z, Z, P], I),
+        "mvsv_stream_push_raw_device": ([P, I, P, Z, Z, P, Z, Z, P], I),
+        "mvsv_stream_push_bgr_device": ([P, I, P, Z, Z, P, Z, Z, P], I),
+        "mvsv_stream_set_host_outputs": ([P, I], I),
+        "mvsv_stream_pop_device": ([P, P, Z, P, P], I),
+        "mvsv_stream_front_map_device": ([P, ctypes.POINTER(P), P], I),
+        "mvsv_stream_front_rectified_device": ([P, ctypes.POINTER(P), ctypes.POINTER(P)], I),
+        "mvsv_stream_front_display_device": ([P, ctypes.POINTER(P), P], I),
+        "mvsv_stream_front_view_device": ([P, ctypes.POINTER(P), P], I),
+        "mvsv_stream_fence": ([P, P], I),
         "mvsv_reproject_device": ([P, I, P, Z, Z, I, I, P, P, Z, Z], I),
         "mvsv_calc_coordinate": ([ctypes.c_float] * 3 + [P, P], None),
         "mvsv_calc_coordinates": ([ctypes.c_int, P, P, P], None),

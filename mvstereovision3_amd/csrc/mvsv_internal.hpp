@@ -277,6 +277,12 @@ int resize_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sf
 int prepare_size(int sw, int sh, int halve, int* dw, int* dh);
 int prepare_gray_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t ss, size_t sfs, int sw, int sh, int halve,
                         int variant, uint8_t* dst, size_t ds, size_t dfs);
+// The frame stream's device push (mvsv_prepare.hip): rows of row_bytes bytes of both
+// sides of n frames (strides in bytes) into dL / dR, which share ds / dfs; one launch
+// on `stream`.  The pointers must be readable / writable by the device.
+int stream_copy_device(mvsv_ctx* ctx, hipStream_t stream, int n, const uint8_t* L, size_t ls, size_t lfs,
+                       const uint8_t* R, size_t rs, size_t rfs, uint8_t* dL, uint8_t* dR, size_t ds, size_t dfs,
+                       int row_bytes, int rows);
 int reproject_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
                      const float* Q, float* out, size_t os, size_t ofs);
 int mean_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W,

@@ -13,6 +13,10 @@
 // makes four output pixels from 24 (halving) or 12 (conversion alone) contiguous
 // source bytes of a row, read as dwords where the source's base and strides are
 // multiples of 4 and the four pixels are whole; bytes otherwise.  No LDS.
+//
+// Also here: stream_copy_kernel, which puts the frames of a device push
+// (mvsv_stream_push_device) into the stream's slots, with the same dword / byte
+// split by alignment.  DESIGN.md §4m.
 #include "mvsv_device.hpp"
 #include "mvsv_internal.hpp"
 
@@ -117,7 +121,62 @@ __global__ __launch_bounds__(256) void bgr_gray_kernel(const uint8_t* __restrict
     }
 }
 
+// The frame stream's device push (mvsv_stream_push_device): rows of row_bytes bytes
+// of both sides of n frames, from the caller's buffers into consecutive slots.
+// blockIdx.z = 2 * frame + side; a block is 64 units of 4 rows.  A wide side moves
+// a dword per lane (consecutive lanes, consecutive dwords) and the row's last
+// row_bytes % 4 bytes one by one; any other side moves a byte per lane.  wide is
+// the same for every lane of a block: source and destination base, row stride and
+// frame stride are all multiples of 4.  Nothing outside [row, row + row_bytes) is
+// read or written.
+struct CopySide {
+    const uint8_t* src;
+    size_t ss, sfs;
+    uint8_t* dst;
+    int wide;
+};
+
+__global__ __launch_bounds__(256) void stream_copy_kernel(CopySide left, CopySide right, size_t ds, size_t dfs,
+                                                          int row_bytes, int rows)
+{
+    const CopySide& s = (blockIdx.z & 1) ? right : left;
+    const size_t f = blockIdx.z >> 1;
+    const uint8_t* __restrict__ S = s.src + f * s.sfs;
+    uint8_t* __restrict__ D = s.dst + f * dfs;
+    const int u = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int x = s.wide ? 4 * u : u;
+    if (x >= row_bytes) return;
+    for (int y = blockIdx.y * 4 + (threadIdx.x >> 6); y < rows; y += gridDim.y * 4) {
+        const uint8_t* p = S + (size_t)y * s.ss + x;
+        uint8_t* q = D + (size_t)y * ds + x;
+        if (!s.wide) {
+            *q = *p;
+        } else if (x + 4 <= row_bytes) {
+            *reinterpret_cast<uint32_t*>(q) = *reinterpret_cast<const uint32_t*>(p);
+        } else {
+            for (int k = 0; x + k < row_bytes; k++) q[k] = p[k];
+        }
+    }
+}
+
 }  // namespace
+
+int stream_copy_device(mvsv_ctx* ctx, hipStream_t stream, int n, const uint8_t* L, size_t ls, size_t lfs,
+                       const uint8_t* R, size_t rs, size_t rfs, uint8_t* dL, uint8_t* dR, size_t ds, size_t dfs,
+                       int row_bytes, int rows)
+{
+    if (n < 1 || row_bytes < 1 || rows < 1 || ls < (size_t)row_bytes || rs < (size_t)row_bytes ||
+        ds < (size_t)row_bytes)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "stream copy: empty frame or stride smaller than the row");
+    if (n == 1) lfs = rfs = dfs = 0;  // unused, and no reason to leave the dword path
+    const size_t dst_bits = ds | dfs;
+    CopySide left{L, ls, lfs, dL, (((uintptr_t)L | ls | lfs | (uintptr_t)dL | dst_bits) & 3) == 0};
+    CopySide right{R, rs, rfs, dR, (((uintptr_t)R | rs | rfs | (uintptr_t)dR | dst_bits) & 3) == 0};
+    const int units = left.wide && right.wide ? (row_bytes + 3) / 4 : row_bytes;
+    dim3 grid((units + 63) / 64, std::min((rows + 3) / 4, 65535), 2 * n);
+    hipLaunchKernelGGL(stream_copy_kernel, grid, dim3(256), 0, stream, left, right, ds, dfs, row_bytes, rows);
+    return check_hip(ctx, hipGetLastError(), "stream copy");
+}
 
 int prepare_size(int sw, int sh, int halve, int* dw, int* dh)
 {

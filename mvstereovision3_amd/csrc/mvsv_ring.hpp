@@ -6,6 +6,8 @@
 // enqueued (tail <= launched <= head, head - tail <= depth).  Pushed frames are
 // launched as runs of consecutive slots; a run never wraps past the ring's end,
 // so its slots are one contiguous [frame][H][W] block of the device arrays.
+// Also here, for the same reason: where the frames of a batched device push go
+// (ring_push_segments) and which source pointers such a push accepts (ring_source_ok).
 #pragma once
 
 #include <algorithm>
@@ -34,5 +36,45 @@ inline bool ring_launch_after_push(long head, long launched, int batch, long dep
 }
 
 inline bool ring_full(long head, long tail, long depth) { return head - tail >= depth; }
+
+// The slots that n consecutive pushes starting at frame `head` fill, as at most
+// two pieces of consecutive slots (the second starts at slot 0 after the ring's
+// end).  Returns the number of pieces; 0 unless 1 <= n <= depth.  That the slots
+// are free (n <= depth - pending) is the caller's check.
+inline int ring_push_segments(long head, int n, long depth, RingRun out[2])
+{
+    if (n < 1 || n > depth) return 0;
+    const long i0 = head % depth;
+    const int first = (int)std::min<long>(n, depth - i0);
+    out[0] = RingRun{i0, first};
+    if (first == n) return 1;
+    out[1] = RingRun{0, n - first};
+    return 2;
+}
+
+// Where the source of a device push may live (mvsv_stream_push_device): what
+// hipPointerGetAttributes reports, restated without HIP types.
+enum PtrKind {
+    kPtrUnregistered = 0,  // pageable host memory the runtime does not know
+    kPtrHost = 1,          // pinned / registered host memory
+    kPtrDevice = 2,
+    kPtrManaged = 3,
+    kPtrOther = 4,  // arrays and whatever else the runtime may name
+};
+
+// query_ok: the attribute query succeeded.  ptr_device: the device the
+// allocation belongs to.  device_ptr: the query reported a device-side address.
+// Accepted: memory of the stream's device, and host memory that its kernels can
+// read (pinned with a device address, or managed).
+inline bool ring_source_ok(bool query_ok, PtrKind kind, int ptr_device, int stream_device, bool device_ptr)
+{
+    if (!query_ok) return false;
+    switch (kind) {
+    case kPtrDevice: return ptr_device == stream_device;
+    case kPtrHost: return device_ptr;
+    case kPtrManaged: return true;
+    default: return false;
+    }
+}
 
 }  // namespace mvsv

@@ -38,6 +38,12 @@
 // With mvsv_stream_enable_bgr, a stream of rectified pairs also takes interleaved
 // BGR pairs (mvsv_stream_push_bgr): uploaded once as BGR, halved and converted to
 // grey into the slot's dL / dR ahead of the matcher (disparityTest.cpp:201-211).
+// With mvsv_stream_push_device (and its raw / BGR forms), frames come from device
+// memory: one copy kernel per contiguous piece of the ring puts them into the
+// slots, ordered against the producer's stream by events; set_host_outputs drops
+// the per-frame downloads nobody reads, pop_device and front_*_device hand the
+// results out on the device, and fence orders the stream behind a zero-copy
+// reader.
 // The host copies of a frame (caller rows -> pinned slot on push, pinned map ->
 // caller rows on pop) are split over a small pool of copy threads that the
 // stream owns (MVSV_STREAM_COPY_THREADS, default 4 including the caller), so a
@@ -174,6 +180,8 @@ struct mvsv_stream {
         int16_t* dOut = nullptr;
         float* dMeans = nullptr;
         hipEvent_t uploaded = nullptr, computed = nullptr, done = nullptr;
+        hipEvent_t released = nullptr;  // pop_device's copy of dOut on the consumer's stream
+        bool release_pending = false;   // the slot's next launch waits for `released`
         int status = MVSV_OK;
         int run_len = 0;     // > 0: this slot starts a frame-batch launch of run_len slots
         bool gave_up = false;  // the launch of this frame gave up a strip wait
@@ -189,6 +197,10 @@ struct mvsv_stream {
     long head = 0, tail = 0;      // pushed / popped frame counters
     long launched = 0;            // frames whose compute is enqueued
     int batch = 1;
+    int host_mask = MVSV_HOST_ALL;     // the per-frame D2H copies that are enqueued (set_host_outputs)
+    hipEvent_t producer_ev = nullptr;  // push_device: what the producer had queued
+    hipEvent_t fence_ev = nullptr;     // mvsv_stream_fence
+    bool fenced = false;
     CopyPool* pool = nullptr;     // host copies of push / pop (nullptr: caller's thread only)
     // raw stream (mvsv_stream_create_raw): pushed frames are raw camera pairs,
     // rectified (cropped, resized) into the slots' dL / dR ahead of their SGBM
@@ -350,9 +362,11 @@ static void stream_free(mvsv_stream* st)
         if (s.hMeans) (void)hipHostFree(s.hMeans);
         if (s.hRectL) (void)hipHostFree(s.hRectL);
         if (s.hRectR) (void)hipHostFree(s.hRectR);
-        for (hipEvent_t e : {s.uploaded, s.computed, s.done})
+        for (hipEvent_t e : {s.uploaded, s.computed, s.done, s.released})
             if (e) (void)hipEventDestroy(e);
     }
+    for (hipEvent_t e : {st->producer_ev, st->fence_ev})
+        if (e) (void)hipEventDestroy(e);
     if (st->dL_all) (void)hipFree(st->dL_all);
     if (st->dR_all) (void)hipFree(st->dR_all);
     if (st->dOut_all) (void)hipFree(st->dOut_all);
@@ -461,7 +475,9 @@ static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p,
     }
     const size_t crop_px = (size_t)st->cropW * st->cropH;
     bool ok = hipStreamCreateWithFlags(&st->up, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&st->down, hipStreamNonBlocking) == hipSuccess;
+              hipStreamCreateWithFlags(&st->down, hipStreamNonBlocking) == hipSuccess &&
+              hipEventCreateWithFlags(&st->producer_ev, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&st->fence_ev, hipEventDisableTiming) == hipSuccess;
     st->slots.resize(depth);
     if (raw) {
         ok = ok && hipMalloc((void**)&st->dRaw_all, 2 * in_px * depth) == hipSuccess && upload_maps(st, raw->rect);
@@ -490,7 +506,8 @@ static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p,
              hipHostMalloc((void**)&s.hMeans, 81 * sizeof(float), hipHostMallocDefault) == hipSuccess &&
              hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&s.computed, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
+             hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&s.released, hipEventDisableTiming) == hipSuccess;
     }
     ok = ok && alloc_report(ctx, depth, &st->rep, &st->rep_dev) == MVSV_OK;
     if (ok) stream_pool(st, std::max(px, in_px) * 2);
@@ -634,6 +651,13 @@ static int stream_launch(mvsv_stream* st)
         // the upload stream is in order: the last slot's upload covers the run
         if ((rc = check_hip(ctx, hipStreamWaitEvent(ctx->stream, last.uploaded, 0), "stream wait")))
             return rc;
+        // a slot whose map pop_device is still copying on the consumer's stream
+        for (int k = 0; k < n; k++) {
+            auto& s = st->slots[i0 + k];
+            if (!s.release_pending) continue;
+            if ((rc = check_hip(ctx, hipStreamWaitEvent(ctx->stream, s.released, 0), "stream wait"))) return rc;
+            s.release_pending = false;
+        }
         // slot i0 was popped (or never used): nothing reads rep[i0] any more
         __atomic_store_n(&st->rep[i0], 0, __ATOMIC_RELEASE);
         first.run_len = n;
@@ -708,14 +732,15 @@ static int stream_launch(mvsv_stream* st)
             auto& s = st->slots[i0 + k];
             s.status = status;
             mvsv_ctx* c = st->ctx;
-            if ((rc = check_hip(c, hipMemcpyAsync(s.hOut, s.dOut, px * 2, hipMemcpyDeviceToHost, st->down),
+            if ((st->host_mask & MVSV_HOST_MAP) &&
+                (rc = check_hip(c, hipMemcpyAsync(s.hOut, s.dOut, px * 2, hipMemcpyDeviceToHost, st->down),
                                 "stream D2H")))
                 return rc;
             if (st->grid &&
                 (rc = check_hip(c, hipMemcpyAsync(s.hMeans, s.dMeans, 81 * sizeof(float),
                                                   hipMemcpyDeviceToHost, st->down), "stream D2H")))
                 return rc;
-            if (st->keep &&
+            if (st->keep && (st->host_mask & MVSV_HOST_RECTIFIED) &&
                 ((rc = check_hip(c, hipMemcpyAsync(s.hRectL, s.dL, px, hipMemcpyDeviceToHost, st->down),
                                  "stream D2H")) ||
                  (rc = check_hip(c, hipMemcpyAsync(s.hRectR, s.dR, px, hipMemcpyDeviceToHost, st->down),
@@ -736,16 +761,18 @@ static int stream_launch(mvsv_stream* st)
             }
             if (st->disp) {
                 const long i = i0 + k;
-                if ((rc = check_hip(c, hipMemcpyAsync(st->disp_map(i), st->dDisp + (size_t)i * st->disp_px, st->disp_px,
-                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")) ||
+                if (((st->host_mask & MVSV_HOST_DISPLAY) &&
+                     (rc = check_hip(c, hipMemcpyAsync(st->disp_map(i), st->dDisp + (size_t)i * st->disp_px, st->disp_px,
+                                                       hipMemcpyDeviceToHost, st->down), "stream D2H"))) ||
                     (rc = check_hip(c, hipMemcpyAsync(st->disp_minmax(i), st->dDispMM + 2 * i, 2 * sizeof(int16_t),
                                                       hipMemcpyDeviceToHost, st->down), "stream D2H")))
                     return rc;
             }
             if (st->view) {
                 const long i = i0 + k;
-                if ((rc = check_hip(c, hipMemcpyAsync(st->view_img(i), st->dView + (size_t)i * st->view_bytes,
-                                                      st->view_bytes, hipMemcpyDeviceToHost, st->down), "stream D2H")) ||
+                if (((st->host_mask & MVSV_HOST_VIEW) &&
+                     (rc = check_hip(c, hipMemcpyAsync(st->view_img(i), st->dView + (size_t)i * st->view_bytes,
+                                                       st->view_bytes, hipMemcpyDeviceToHost, st->down), "stream D2H"))) ||
                     (rc = check_hip(c, hipMemcpyAsync(st->view_minmax(i), st->dViewMM + 2 * i, 2 * sizeof(int16_t),
                                                       hipMemcpyDeviceToHost, st->down), "stream D2H")))
                     return rc;
@@ -814,6 +841,8 @@ int mvsv_stream_set_inflight(mvsv_stream* st, int n)
         if ((rc = mvsv_create(&c, ctx->device))) return set_error(ctx, rc, "stream lane context creation failed");
         copy_options(c, ctx);
         st->lanes.push_back(c);
+        if (st->fenced && (rc = check_hip(ctx, hipStreamWaitEvent(c->stream, st->fence_ev, 0), "stream wait")))
+            return rc;
     }
     while ((int)st->lanes.size() > n) {  // mvsv_destroy waits for the lane's work
         mvsv_destroy(st->lanes.back());
@@ -1050,6 +1079,11 @@ int mvsv_stream_pop_pair(mvsv_stream* st, int16_t* out, size_t os, float* means,
         return set_error(st->ctx, MVSV_E_INVALID_ARG, "the stream was not created with keep_rectified");
     if ((rl && rls < (size_t)st->W) || (rr && rrs < (size_t)st->W))
         return set_error(st->ctx, MVSV_E_INVALID_ARG, "stride smaller than width");
+    if (out && !(st->host_mask & MVSV_HOST_MAP))
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the host map is switched off (mvsv_stream_set_host_outputs)");
+    if ((rl || rr) && !(st->host_mask & MVSV_HOST_RECTIFIED))
+        return set_error(st->ctx, MVSV_E_INVALID_ARG,
+                         "the host rectified pair is switched off (mvsv_stream_set_host_outputs)");
     DeviceGuard dev_guard(st->ctx->device);
     mvsv_stream::Slot* sp = nullptr;
     int rc = stream_pop_slot(st, &sp);
@@ -1081,6 +1115,8 @@ int mvsv_stream_pop_view(mvsv_stream* st, const int16_t** map, float* means)
 {
     if (!st || !map) return MVSV_E_INVALID_ARG;
     *map = nullptr;
+    if (!(st->host_mask & MVSV_HOST_MAP))
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the host map is switched off (mvsv_stream_set_host_outputs)");
     DeviceGuard dev_guard(st->ctx->device);
     mvsv_stream::Slot* sp = nullptr;
     int rc = stream_pop_slot(st, &sp);
@@ -1242,8 +1278,11 @@ static int front_slot(mvsv_stream* st, bool enabled, const char* not_enabled, lo
     return MVSV_OK;
 }
 
-static int display_front(mvsv_stream* st, long* idx)
+static int display_front(mvsv_stream* st, long* idx, bool host = true)
 {
+    if (host && st->disp && !(st->host_mask & MVSV_HOST_DISPLAY))
+        return set_error(st->ctx, MVSV_E_INVALID_ARG,
+                         "the host display map is switched off (mvsv_stream_set_host_outputs)");
     return front_slot(st, st->disp, "the display is not enabled on this stream", idx);
 }
 
@@ -1486,8 +1525,10 @@ int mvsv_stream_enable_view(mvsv_stream* st, const mvsv_rect* roi, const mvsv_vi
     return MVSV_OK;
 }
 
-static int view_front(mvsv_stream* st, long* idx)
+static int view_front(mvsv_stream* st, long* idx, bool host = true)
 {
+    if (host && st->view && !(st->host_mask & MVSV_HOST_VIEW))
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the host view is switched off (mvsv_stream_set_host_outputs)");
     return front_slot(st, st->view, "the view is not enabled on this stream", idx);
 }
 
@@ -1516,6 +1557,218 @@ int mvsv_stream_front_view_view(mvsv_stream* st, const uint8_t** view, int16_t* 
     if ((rc = view_front(st, &idx))) return rc;
     *view = st->view_img(idx);
     if (minmax) std::memcpy(minmax, st->view_minmax(idx), 2 * sizeof(int16_t));
+    return MVSV_OK;
+}
+
+// ---- device ends of the stream ----
+
+// Both ends of a source span may be read by the stream's device.
+static bool source_ok(const mvsv_stream* st, const uint8_t* p, size_t span)
+{
+    for (const uint8_t* q : {p, p + span - 1}) {
+        hipPointerAttribute_t a{};
+        const bool ok = hipPointerGetAttributes(&a, q) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        PtrKind kind = kPtrOther;
+        switch (a.type) {
+        case hipMemoryTypeUnregistered: kind = kPtrUnregistered; break;
+        case hipMemoryTypeHost: kind = kPtrHost; break;
+        case hipMemoryTypeDevice: kind = kPtrDevice; break;
+        case hipMemoryTypeManaged: kind = kPtrManaged; break;
+        default: break;
+        }
+        if (!ring_source_ok(ok, kind, a.device, st->ctx->device, a.devicePointer != nullptr)) return false;
+    }
+    return true;
+}
+
+enum PushKind { kPushRectified, kPushRaw, kPushBgr };
+
+// n frames from device-readable memory into the next n slots: one copy launch per
+// contiguous ring segment on the upload stream, ordered against the producer's
+// stream by events in both directions; then the bookkeeping of n single pushes.
+static int stream_push_device(mvsv_stream* st, PushKind kind, int n, const uint8_t* L, size_t ls, size_t lfs,
+                              const uint8_t* R, size_t rs, size_t rfs, void* producer)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (kind == kPushRaw && !st->raw)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "stream of rectified pairs: push them with mvsv_stream_push_device");
+    if (kind != kPushRaw && st->raw)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "raw stream: push raw pairs with mvsv_stream_push_raw_device");
+    if (kind == kPushBgr && !st->bgr)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "colour input is not enabled on this stream");
+    const int rows = kind == kPushRaw ? st->rawH : kind == kPushBgr ? st->bgrH : st->H;
+    const size_t row = kind == kPushRaw ? (size_t)st->rawW : kind == kPushBgr ? 3 * (size_t)st->bgrW : (size_t)st->W;
+    if (!L || !R || ls < row || rs < row)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "null frame or stride smaller than the row");
+    const long depth = (long)st->slots.size();
+    if (n < 1 || n > depth - (st->head - st->tail))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "device push: 1 .. depth - pending frames expected");
+    if (n > 1 && (lfs < (size_t)(rows - 1) * ls + row || rfs < (size_t)(rows - 1) * rs + row))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "frame stride smaller than a frame");
+    DeviceGuard dev_guard(ctx->device);
+    if (!source_ok(st, L, (size_t)(n - 1) * lfs + (size_t)(rows - 1) * ls + row) ||
+        !source_ok(st, R, (size_t)(n - 1) * rfs + (size_t)(rows - 1) * rs + row))
+        return set_error(ctx, MVSV_E_INVALID_ARG,
+                         "device push: memory of the stream's device or device-accessible host memory expected");
+    hipStream_t prod = (hipStream_t)producer;
+    int rc;
+    if ((rc = check_hip(ctx, hipEventRecord(st->producer_ev, prod), "stream event")) ||
+        (rc = check_hip(ctx, hipStreamWaitEvent(st->up, st->producer_ev, 0), "stream wait")))
+        return rc;
+    RingRun seg[2];
+    const int nseg = ring_push_segments(st->head, n, depth, seg);
+    // the slots' previous frames were popped, so everything that read or wrote them is complete
+    int done = 0;
+    for (int g = 0; g < nseg; g++) {
+        auto& first = st->slots[seg[g].i0];
+        uint8_t *dl, *dr;
+        size_t ds, dfs;
+        if (kind == kPushRaw) {
+            dl = first.dRaw, dr = first.dRaw + row * rows, ds = row, dfs = 2 * row * rows;
+        } else if (kind == kPushBgr) {
+            dl = first.dBgr, dr = first.dBgr + st->bgrRow * rows, ds = st->bgrRow, dfs = 2 * st->bgrRow * rows;
+        } else {
+            dl = first.dL, dr = first.dR, ds = row, dfs = row * rows;
+        }
+        if ((rc = stream_copy_device(ctx, st->up, seg[g].n, L + done * lfs, ls, lfs, R + done * rfs, rs, rfs, dl, dr,
+                                     ds, dfs, (int)row, rows)))
+            return rc;
+        done += seg[g].n;
+    }
+    // n single pushes: a launch waits for the `uploaded` event of its last slot, which is
+    // the frame that completes a group, the ring's last slot or the call's last frame
+    hipEvent_t last = nullptr;
+    for (int k = 0; k < n; k++) {
+        auto& s = st->slots[st->head % depth];
+        if (kind != kPushRaw) s.is_bgr = kind == kPushBgr;
+        st->head++;
+        const bool launch = ring_launch_after_push(st->head, st->launched, st->batch, depth);
+        if (launch || k == n - 1) {
+            if ((rc = check_hip(ctx, hipEventRecord(s.uploaded, st->up), "stream event"))) return rc;
+            last = s.uploaded;
+        }
+        if (launch && (rc = stream_launch(st))) return rc;
+    }
+    // what the producer enqueues from now on may overwrite or free the source
+    return check_hip(ctx, hipStreamWaitEvent(prod, last, 0), "stream wait");
+}
+
+int mvsv_stream_push_device(mvsv_stream* st, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
+                            size_t rs, size_t rfs, void* producer_stream)
+{
+    return stream_push_device(st, kPushRectified, n, L, ls, lfs, R, rs, rfs, producer_stream);
+}
+
+int mvsv_stream_push_raw_device(mvsv_stream* st, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
+                                size_t rs, size_t rfs, void* producer_stream)
+{
+    return stream_push_device(st, kPushRaw, n, L, ls, lfs, R, rs, rfs, producer_stream);
+}
+
+int mvsv_stream_push_bgr_device(mvsv_stream* st, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
+                                size_t rs, size_t rfs, void* producer_stream)
+{
+    return stream_push_device(st, kPushBgr, n, L, ls, lfs, R, rs, rfs, producer_stream);
+}
+
+int mvsv_stream_set_host_outputs(mvsv_stream* st, int mask)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (mask & ~MVSV_HOST_ALL) return set_error(st->ctx, MVSV_E_INVALID_ARG, "unknown host output bit");
+    if (st->head != st->tail)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the host outputs change only while no frame is pending");
+    st->host_mask = mask;
+    return MVSV_OK;
+}
+
+int mvsv_stream_pop_device(mvsv_stream* st, int16_t* out, size_t os, float* means, void* consumer_stream)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (!out || os < (size_t)st->W) return set_error(ctx, MVSV_E_INVALID_ARG, "null map or stride smaller than width");
+    DeviceGuard dev_guard(ctx->device);
+    mvsv_stream::Slot* sp = nullptr;
+    int rc = stream_pop_slot(st, &sp);
+    if (rc) return rc;
+    // the frame is complete: the consumer's stream needs no wait.  The slot's next
+    // launch waits for this copy before it overwrites the map.
+    hipStream_t cons = (hipStream_t)consumer_stream;
+    if ((rc = check_hip(ctx, hipMemcpy2DAsync(out, os * 2, sp->dOut, (size_t)st->W * 2, (size_t)st->W * 2, st->H,
+                                              hipMemcpyDeviceToDevice, cons), "stream D2D")) ||
+        (rc = check_hip(ctx, hipEventRecord(sp->released, cons), "stream event")))
+        return rc;
+    sp->release_pending = true;
+    stream_means(st, *sp, means);
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_map_device(mvsv_stream* st, const int16_t** map_dev, float* means)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (!map_dev) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null map pointer");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = front_slot(st, true, "", &idx))) return rc;
+    *map_dev = st->slots[idx].dOut;
+    stream_means(st, st->slots[idx], means);
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_rectified_device(mvsv_stream* st, const uint8_t** left_dev, const uint8_t** right_dev)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (!left_dev || !right_dev) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null pair pointer");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = front_slot(st, st->keep, "the stream was not created with keep_rectified", &idx))) return rc;
+    *left_dev = st->slots[idx].dL;
+    *right_dev = st->slots[idx].dR;
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_display_device(mvsv_stream* st, const uint8_t** map_dev, int16_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (!map_dev) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null map pointer");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = display_front(st, &idx, false))) return rc;
+    *map_dev = st->dDisp + (size_t)idx * st->disp_px;
+    if (minmax) std::memcpy(minmax, st->disp_minmax(idx), 2 * sizeof(int16_t));
+    return MVSV_OK;
+}
+
+int mvsv_stream_front_view_device(mvsv_stream* st, const uint8_t** bgr_dev, int16_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (!bgr_dev) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null view pointer");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    int rc;
+    if ((rc = view_front(st, &idx, false))) return rc;
+    *bgr_dev = st->dView + (size_t)idx * st->view_bytes;
+    if (minmax) std::memcpy(minmax, st->view_minmax(idx), 2 * sizeof(int16_t));
+    return MVSV_OK;
+}
+
+int mvsv_stream_fence(mvsv_stream* st, void* hip_stream)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    DeviceGuard dev_guard(ctx->device);
+    int rc;
+    if ((rc = check_hip(ctx, hipEventRecord(st->fence_ev, (hipStream_t)hip_stream), "stream event")) ||
+        (rc = check_hip(ctx, hipStreamWaitEvent(st->up, st->fence_ev, 0), "stream wait")))
+        return rc;
+    // frames that are pushed but not launched yet run on the lanes
+    for (mvsv_ctx* c : st->lanes)
+        if ((rc = check_hip(ctx, hipStreamWaitEvent(c->stream, st->fence_ev, 0), "stream wait"))) return rc;
+    st->fenced = true;
     return MVSV_OK;
 }
 

@@ -389,11 +389,11 @@ class SamplepointDetection:
 
 
 class _DeviceSpan:
-    """float32 device memory owned by someone else, for torch.as_tensor (no copy)."""
+    """Device memory owned by someone else (float32 by default), for torch.as_tensor (no copy)."""
 
-    def __init__(self, ptr, shape, owner):
+    def __init__(self, ptr, shape, owner, typestr="<f4"):
         self._owner = owner
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(ptr), False),
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
                                          "version": 2, "strides": None}
 
 
@@ -410,6 +410,14 @@ class DisparityStream:
     matcher: a StereoSGBM or a StereoBM (mvsv_stream_create_bm), here and in
     set_params, which may switch between the two; anything else raises.
     enable_bgr / push_bgr: colour pairs, halved and converted on the device.
+    Device ends: push / push_raw / push_bgr also take torch uint8 tensors on the
+    stream's device, one frame or N frames with a leading axis, ordered against
+    torch's current stream by events (no synchronisation; the source may be
+    overwritten or freed on that stream right after the call).
+    pop(copy_map="device"), front_map(device=True), front_display(copy="device"),
+    front_view(copy="device") and front_rectified() hand the results out on the
+    device; host_outputs(...) switches the per-frame downloads off; fence() is for
+    zero-copy readers.
     """
 
     @staticmethod
@@ -559,6 +567,8 @@ class DisparityStream:
         shape = getattr(self, "_bgr_shape", None)
         if shape is None:
             raise MvsvError(_lib.MVSV_E_INVALID_ARG, "push_bgr: enable_bgr first (a stream of rectified pairs)")
+        if self._on_device(left) or self._on_device(right):
+            return self._push_device(lib().mvsv_stream_push_bgr_device, left, right, shape, "push_bgr")
         L = np.asarray(left)
         R = np.asarray(right)
         if L.shape != shape or R.shape != shape or L.dtype != np.uint8 or R.dtype != np.uint8:
@@ -578,8 +588,89 @@ class DisparityStream:
             raise MvsvError(_lib.MVSV_E_INVALID_ARG, "stream is closed")
         return self._h
 
+    @staticmethod
+    def _on_device(x):
+        """A torch tensor in device memory (numpy arrays and CPU tensors take the host path)."""
+        return getattr(x, "is_cuda", False) is True
+
+    def _push_device(self, fn, left, right, shape, what):
+        """One frame (`shape`) or N frames (N, *shape) from torch device tensors
+        (mvsv_stream_push*_device), ordered against torch's current stream."""
+        import torch
+        bad = MvsvError(_lib.MVSV_E_INVALID_ARG,
+                        f"{what}: a pair of uint8 tensors of shape {shape} or (N, *{shape}) on the stream's device expected")
+        if not (self._on_device(left) and self._on_device(right)):
+            raise bad
+        dev = torch.device("cuda", self._ctx.device)
+        nd = len(shape)
+        inner = (3, 1) if nd == 3 else (1,)
+        pair = []
+        for t in (left, right):
+            if t.device != dev or t.dtype != torch.uint8 or t.dim() not in (nd, nd + 1) \
+                    or tuple(t.shape[-nd:]) != tuple(shape) or t.shape != left.shape:
+                raise bad
+            if tuple(t.stride()[-len(inner):]) != inner:
+                t = t.contiguous()
+            pair.append(t)
+        L, R = pair
+        n = L.shape[0] if L.dim() == nd + 1 else 1
+        fs = (lambda t: t.stride(0)) if L.dim() == nd + 1 else (lambda t: 0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(fn(self._h, n, L.data_ptr(), L.stride(-nd), fs(L), R.data_ptr(), R.stride(-nd), fs(R), stream),
+              self._ctx.handle)
+
+    def host_outputs(self, map=True, rectified=True, display=True, view=True):
+        """Which per-frame products are also downloaded to the host (default: all;
+        mvsv_stream_set_host_outputs).  Only while no frame is pending.  The host
+        getters of a product that is switched off raise; the device getters work."""
+        mask = (_lib.MVSV_HOST_MAP if map else 0) | (_lib.MVSV_HOST_RECTIFIED if rectified else 0) | \
+               (_lib.MVSV_HOST_DISPLAY if display else 0) | (_lib.MVSV_HOST_VIEW if view else 0)
+        check(lib().mvsv_stream_set_host_outputs(self._live(), mask), self._ctx.handle)
+
+    def fence(self):
+        """Everything the stream enqueues from now on waits for what is queued on
+        torch's current stream now (mvsv_stream_fence): call it after the last read of
+        a zero-copy tensor whose frame is popped while that read may still run."""
+        import torch
+        stream = torch.cuda.current_stream(torch.device("cuda", self._ctx.device)).cuda_stream
+        check(lib().mvsv_stream_fence(self._live(), stream), self._ctx.handle)
+
+    def _span(self, ptr, shape, typestr):
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        return torch.as_tensor(_DeviceSpan(ptr.value, shape, self, typestr), device=dev)
+
+    def front_map(self, device=True):
+        """(map, means) of the oldest pending frame, which stays pending: the int16
+        map as a zero-copy device tensor viewing the stream's ring, read-only by
+        contract and valid until the frame is popped (mvsv_stream_front_map_device)."""
+        self._live()
+        if not device:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "front_map: device=True expected (pop returns the host map)")
+        ptr = ctypes.c_void_p()
+        means = np.empty(81, np.float32) if self._grid else None
+        check(lib().mvsv_stream_front_map_device(self._h, ctypes.byref(ptr),
+                                                 means.ctypes.data if means is not None else None),
+              self._ctx.handle)
+        return self._span(ptr, (self.height, self.width), "<i2"), means
+
+    def front_rectified(self):
+        """(left, right) of the oldest pending frame of a keep_rectified stream, which
+        stays pending: the rectified pair as zero-copy uint8 device tensors, read-only
+        by contract and valid until the frame is popped."""
+        self._live()
+        pl, pr = ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().mvsv_stream_front_rectified_device(self._h, ctypes.byref(pl), ctypes.byref(pr)),
+              self._ctx.handle)
+        shape = (self.height, self.width)
+        return self._span(pl, shape, "|u1"), self._span(pr, shape, "|u1")
+
     def push(self, left, right):
         self._live()
+        if self._on_device(left) or self._on_device(right):
+            if self._raw_shape is not None:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "push: a raw stream takes push_raw")
+            return self._push_device(lib().mvsv_stream_push_device, left, right, (self.height, self.width), "push")
         L = np.asarray(left)
         R = np.asarray(right)
         if L.shape != (self.height, self.width) or R.shape != L.shape or L.dtype != np.uint8 \
@@ -595,10 +686,12 @@ class DisparityStream:
     def push_raw(self, left, right):
         """Push a raw camera pair (a stream made by DisparityStream.raw)."""
         self._live()
-        L = np.asarray(left)
-        R = np.asarray(right)
         if self._raw_shape is None:
             raise MvsvError(_lib.MVSV_E_INVALID_ARG, "push_raw: a stream of rectified pairs takes push")
+        if self._on_device(left) or self._on_device(right):
+            return self._push_device(lib().mvsv_stream_push_raw_device, left, right, self._raw_shape, "push_raw")
+        L = np.asarray(left)
+        R = np.asarray(right)
         if L.shape != self._raw_shape or R.shape != L.shape or L.dtype != np.uint8 or R.dtype != np.uint8:
             raise MvsvError(_lib.MVSV_E_INVALID_ARG, "push_raw: uint8 pair of the raw frame's size expected")
         if L.strides[1] != 1:
@@ -613,8 +706,20 @@ class DisparityStream:
         copy_map="view" returns a read-only view of the map in the stream's pinned
         host slot (no host copy), valid until the next push.  rectified=True (a raw
         stream with keep_rectified) returns (map, means, (left, right)) with the
-        frame's rectified pair."""
+        frame's rectified pair.  copy_map="device": the map as a fresh int16 tensor on
+        the stream's device, filled on torch's current stream (mvsv_stream_pop_device)."""
         self._live()
+        if isinstance(copy_map, str) and copy_map == "device":
+            import torch
+            if rectified:
+                raise MvsvError(_lib.MVSV_E_INVALID_ARG, "pop(copy_map='device'): front_rectified() hands out the pair")
+            dev = torch.device("cuda", self._ctx.device)
+            out = torch.empty((self.height, self.width), dtype=torch.int16, device=dev)
+            means = np.empty(81, np.float32) if self._grid else None
+            check(lib().mvsv_stream_pop_device(self._h, out.data_ptr(), self.width,
+                                               means.ctypes.data if means is not None else None,
+                                               torch.cuda.current_stream(dev).cuda_stream), self._ctx.handle)
+            return out, means
         if rectified:
             if not self._keep or copy_map == "view":
                 raise MvsvError(_lib.MVSV_E_INVALID_ARG,
@@ -728,10 +833,17 @@ class DisparityStream:
         """(map, (smin, smax)) of the oldest pending frame, which stays pending (pop
         it afterwards): the uint8 display map of the enabled roi and the min / max
         it was normalised with.  copy="view": a read-only view of the map in the
-        stream's pinned host slot, valid until the next push."""
+        stream's pinned host slot, valid until the next push.  copy="device": a
+        zero-copy device tensor viewing the stream's ring, read-only by contract and
+        valid until the frame is popped."""
         self._live()
         shape = getattr(self, "_disp_shape", None) or (0, 0)
         mm = np.zeros(2, np.int16)
+        if copy == "device":
+            ptr = ctypes.c_void_p()
+            check(lib().mvsv_stream_front_display_device(self._h, ctypes.byref(ptr), mm.ctypes.data),
+                  self._ctx.handle)
+            return self._span(ptr, shape, "|u1"), (int(mm[0]), int(mm[1]))
         if copy == "view":
             ptr = ctypes.c_void_p()
             check(lib().mvsv_stream_front_display_view(self._h, ctypes.byref(ptr), mm.ctypes.data),
@@ -788,10 +900,16 @@ class DisparityStream:
         """(image, (smin, smax)) of the oldest pending frame, which stays pending (pop
         it afterwards): the uint8 BGR detection view (h, w, 3) of the enabled roi and
         the min / max it was normalised with.  copy="view": a read-only view of the
-        image in the stream's pinned host slot, valid until the next push."""
+        image in the stream's pinned host slot, valid until the next push.
+        copy="device": a zero-copy device tensor viewing the stream's ring, read-only
+        by contract and valid until the frame is popped."""
         self._live()
         shape = getattr(self, "_view_shape", None) or (0, 0, 3)
         mm = np.zeros(2, np.int16)
+        if copy == "device":
+            ptr = ctypes.c_void_p()
+            check(lib().mvsv_stream_front_view_device(self._h, ctypes.byref(ptr), mm.ctypes.data), self._ctx.handle)
+            return self._span(ptr, shape, "|u1"), (int(mm[0]), int(mm[1]))
         if copy == "view":
             ptr = ctypes.c_void_p()
             check(lib().mvsv_stream_front_view_view(self._h, ctypes.byref(ptr), mm.ctypes.data), self._ctx.handle)

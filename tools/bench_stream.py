@@ -14,9 +14,13 @@ trgt/disparityTest.cpp:268 runs beside SGBM): StereoBM::create(64, 9), or the va
 of tests/golden/configs/bm.yml.  --bgr: the frames are pushed as 2W x 2H colour
 pairs (mvsv_stream_push_bgr), halved and converted on the device (:201-211); the
 device-resident figure then includes prepare_gray of the batch.
+--device-frames: the device ends of the stream: the frames are
+resident torch tensors pushed `batch` at a time as (N, H, W), the host map, display
+and view outputs are off, and every map is read in place through
+front_map(device=True) before pop(copy_map=False); the means still come to the host.
 
     python tools/bench_stream.py [--frames 300] [--depth 24] [--batch 8] [--inflight 2]
-                                 [--matcher sgbm|bm|bm-yml] [--bgr]
+                                 [--matcher sgbm|bm|bm-yml] [--bgr] [--device-frames]
 """
 import argparse
 import json
@@ -29,7 +33,7 @@ sys.path.insert(0, ROOT)
 
 
 def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=2, pop="view",
-                   host_probe="full", device_steps=10, matcher="sgbm", bgr=False):
+                   host_probe="full", device_steps=10, matcher="sgbm", bgr=False, device_frames=False):
     """The config-5 stream (liveDisparity matcher + MeanDisparityDetection post-pass
     on every frame, host frames in / maps and means out) -> one result dict."""
     import numpy as np
@@ -64,13 +68,21 @@ def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=
     if bgr:
         st.enable_bgr((2 * H, 2 * W))
     push = st.push_bgr if bgr else st.push
+    if device_frames:
+        # resident frames, a whole number of groups of `batch`
+        nres = -(-8 // batch) * batch
+        res = tuple(torch.from_numpy(np.stack([uniq[j % 8][k] for j in range(nres)])).cuda() for k in (0, 1))
+        st.host_outputs(map=False, display=False, view=False)
     found = 0
     host = {"push": 0.0, "pop": 0.0, "post": 0.0}
 
     def consume():
         nonlocal found
         t = time.perf_counter()
-        if host_probe == "no-copy":
+        if device_frames:
+            d, means = st.front_map(device=True)  # zero copy: valid until the pop
+            st.pop(copy_map=False)
+        elif host_probe == "no-copy":
             st.pop(copy_map=False)
         else:
             d, means = st.pop(copy_map="view" if pop == "view" else True)
@@ -82,24 +94,34 @@ def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=
         host["pop"] += t2 - t
         host["post"] += time.perf_counter() - t2
 
-    for i in range(depth):  # warm-up
-        push(*uniq[i % 8])
-    while st.pending():
-        consume()
+    def feed(count):
+        """`count` frames: one by one from the host, or `batch` at a time from the device."""
+        i = 0
+        while i < count:
+            n = min(batch, count - i) if device_frames else 1
+            while st.pending() > depth - n:
+                consume()
+            t = time.perf_counter()
+            if device_frames:
+                o = i % nres
+                push(res[0][o:o + n], res[1][o:o + n])
+            else:
+                push(*uniq[i % 8])
+            host["push"] += time.perf_counter() - t
+            i += n
+        while st.pending():
+            consume()
+
+    feed(depth)  # warm-up
     host = dict.fromkeys(host, 0.0)
     t0 = time.perf_counter()
-    for i in range(frames):
-        if st.pending() == depth:
-            consume()
-        t = time.perf_counter()
-        push(*uniq[i % 8])
-        host["push"] += time.perf_counter() - t
-    while st.pending():
-        consume()
+    feed(frames)
     wall = time.perf_counter() - t0
     st.close()
 
     # device-resident rate of the same matcher + the mean grid (8-frame batch in HBM)
+    if device_frames:
+        del res
     dev = torch.device("cuda", 0)
     Lt = torch.from_numpy(np.stack([u[0] for u in uniq])).to(dev)
     Rt = torch.from_numpy(np.stack([u[1] for u in uniq])).to(dev)
@@ -124,7 +146,8 @@ def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=
         "workload": f"config5_stream_{W}x{H}_d{D}_mode_sgbm" if matcher == "sgbm" and not bgr else
                     f"stream_{W}x{H}_d{D}_{matcher}{'_bgr' if bgr else ''}",
         "frames": frames, "depth": depth, "batch": batch, "inflight": inflight,
-        "host_probe": host_probe, "pop": pop,
+        "host_probe": host_probe, "pop": "front_map(device)" if device_frames else pop,
+        "device_frames": bool(device_frames),
         "stream_fps": round(frames / wall, 2),
         "stream_mpix_s": round(frames * W * H / wall / 1e6, 2),
         "stream_ms_per_frame": round(wall / frames * 1e3, 3),
@@ -132,7 +155,9 @@ def stream_measure(mvsv, W=1280, H=960, frames=300, depth=24, batch=8, inflight=
         "device_resident_ms_per_frame": round(dwall / (8 * device_steps) * 1e3, 3),
         "obstacle_tiles_found": found,
         "host_ms_per_frame": {k: round(v / frames * 1e3, 3) for k, v in host.items()},
-        "note": "stream = host frames in, int16 map + 81 means out (PCIe incl.); "
+        "stream_over_device_resident": round((frames / wall) / (8 * device_steps / dwall), 3),
+        "note": ("stream = resident device frames in (batches of N), int16 map read in place + 81 means out; "
+                 if device_frames else "stream = host frames in, int16 map + 81 means out (PCIe incl.); ") +
                 "post-pass = MeanDisparityDetection build(MEAN_VALUE) + detectObstacles",
     }
 
@@ -153,12 +178,15 @@ def main():
                     help="the stream's matcher: config 5's SGBM, StereoBM(64, 9), or StereoBM with bm.yml's values")
     ap.add_argument("--bgr", action="store_true",
                     help="push 2W x 2H colour pairs; the device halves and converts them (mvsv_stream_push_bgr)")
+    ap.add_argument("--device-frames", action="store_true",
+                    help="resident torch frames pushed `batch` at a time, host map / display / view outputs off, "
+                         "maps read through front_map(device=True)")
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=960)
     a = ap.parse_args()
     import mvstereovision3_amd as mvsv
     print(json.dumps(stream_measure(mvsv, a.width, a.height, a.frames, a.depth, a.batch, a.inflight, a.pop,
-                                    a.host_probe, matcher=a.matcher, bgr=a.bgr)))
+                                    a.host_probe, matcher=a.matcher, bgr=a.bgr, device_frames=a.device_frames)))
 
 
 if __name__ == "__main__":
