@@ -83,6 +83,9 @@
  *   mvsv_stream_push*_device /        the same loops for a producer and a consumer on the GPU:
  *   _pop_device / _front_*_device /   frames from device memory, results read where they lie (no
  *   _set_host_outputs / _fence        counterpart in the reference, whose images live in cv::Mat)
+ *   mvsv_tm(_device) / _tm_validate   Disparity::tm          src/disparity.cpp:25-58,
+ *                                     decl inc/disparity.h:32 (cv::matchTemplate
+ *                                     CV_TM_CCORR_NORMED along the row, per pixel)
  *
  * Conventions
  *   - Plain C types only; no exceptions cross this boundary.
@@ -896,6 +899,33 @@ MVSV_API int mvsv_prepare_gray_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, 
                                       size_t dst_stride, size_t dst_frame_stride);
 MVSV_API int mvsv_prepare_gray(mvsv_ctx* ctx, const uint8_t* bgr, size_t stride, int src_width, int src_height,
                                int halve, int variant, uint8_t* dst, size_t dst_stride);
+
+/* ---- Disparity::tm: normalised cross-correlation row search (src/disparity.cpp:25-58) ----
+ * For every pixel (i, j), i < height - k and j < width - k (both exclusive, the
+ * reference's loop bounds), the k x k template left[i.., j..] is matched against the
+ * windows right[i.., j + x ..], x = 0 .. width - j - k - 1 (the search strip ends at
+ * column width - 2 and runs to the right), by cv::matchTemplate(CV_TM_CCORR_NORMED):
+ * score = N / sqrt(sum T^2 * sum S^2), N = sum T * S, and 0 where the denominator is 0.
+ * The first x with the largest score (cv::minMaxLoc's scan order) is stored; every
+ * other pixel of the map is 0.  Scores are compared exactly: x beats the best b so far
+ * iff N_x^2 * sum S_b^2 > N_b^2 * sum S_x^2 in 128-bit integers (strict: the earliest x
+ * keeps a tie; a window of zeros counts as N = 0, sum S^2 = 1), never in floating
+ * point alone -- cv::matchTemplate's arithmetic without the rounding of its float DFT.
+ * mvsv_tm_validate: 1 <= k <= 31, k < min(width, height), sides <= 65535; context-free.
+ * mvsv_tm: host images, synchronous; dst is 8 bit: x truncated (output.at<char>), so
+ *   x >= 256 wraps.
+ * mvsv_tm_device: n frames, device pointers, strides in bytes (ROI views where a stride
+ *   exceeds the row), asynchronous on the context's stream.  elem_bytes 1: the wrapped
+ *   byte; elem_bytes 2 (new): x as uint16, dst and its strides even.  Rows >= height - k
+ *   and columns >= width - k are written as 0; no byte outside [row, row + width *
+ *   elem_bytes) of a destination row is written, none outside [row, row + width) read. */
+MVSV_API int mvsv_tm_validate(int k, int width, int height);
+MVSV_API int mvsv_tm(mvsv_ctx* ctx, const uint8_t* left, size_t left_stride, const uint8_t* right,
+                     size_t right_stride, int width, int height, int k, uint8_t* dst, size_t dst_stride);
+MVSV_API int mvsv_tm_device(mvsv_ctx* ctx, int n, const uint8_t* left, size_t left_stride,
+                            size_t left_frame_stride, const uint8_t* right, size_t right_stride,
+                            size_t right_frame_stride, int width, int height, int k, void* dst,
+                            size_t dst_stride, size_t dst_frame_stride, int elem_bytes);
 
 /* cv::initUndistortRectifyMap(K, dist, R, P, size, CV_32FC1): K 3x3, dist =
  * (k1, k2, p1, p2[, k3[, k4, k5, k6]]) with ndist in {0, 4, 5, 8}, R 3x3, P 3x3 or

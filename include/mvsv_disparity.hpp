@@ -5,6 +5,7 @@
 //   Disparity::sgbmParameters              inc/disparity.h:17-27
 //   Disparity::sgbm(Stereopair const&, cv::Mat&, cv::Ptr<cv::StereoSGBM>)   src/disparity.cpp:6-10
 //   Disparity::bm  (Stereopair const&, cv::Mat&, cv::Ptr<cv::StereoBM>)     src/disparity.cpp:18-22
+//   Disparity::tm  (Stereopair const&, cv::Mat&, unsigned int kernelSize)   src/disparity.cpp:25-58
 //   Disparity::loadSGBMParameters(std::string, cv::Ptr<cv::StereoSGBM>&, sgbmParameters&)
 //                                                                          src/disparity.cpp:60-108
 // This header keeps those names, argument meaning and error behaviour without
@@ -264,6 +265,25 @@ template <class Pair>
 inline void bm(Pair const& inputImages, mvsv::Mat& output, mvsv::Ptr<mvsv::StereoBM> dispCompute)
 {
     dispCompute->compute(inputImages.mLeft, inputImages.mRight, output);
+}
+
+// src/disparity.cpp:25-58 — the template-matching matcher: output (re)allocated CV_8U,
+// the arg-max shift of cv::matchTemplate(CV_TM_CCORR_NORMED) along the row, truncated to
+// 8 bits, for the pixels i < rows - kernelSize, j < cols - kernelSize; 0 elsewhere.
+// kernelSize outside 1 .. 31 or not below both sides throws (the reference's unsigned
+// loop bounds wrap there).
+template <class Pair>
+inline void tm(Pair const& inputImages, mvsv::Mat& output, unsigned int kernelSize)
+{
+    const mvsv::Mat& l = inputImages.mLeft;
+    const mvsv::Mat& r = inputImages.mRight;
+    mvsv::check_pair(l, r);
+    if (kernelSize > 31u || mvsv_tm_validate((int)kernelSize, l.cols, l.rows) != MVSV_OK)
+        throw mvsv::Error(MVSV_E_INVALID_ARG, "tm: kernelSize must be within 1 .. 31 and below both image sides");
+    output.create(l.rows, l.cols, mvsv::MAT_8UC1);
+    mvsv_ctx* c = mvsv::thread_context();
+    mvsv::check(mvsv_tm(c, l.data, l.step, r.data, r.step, l.cols, l.rows, (int)kernelSize, output.data, output.step),
+                c);
 }
 
 // src/disparity.cpp:60-108 — eight setters + mode from configs/sgbm.yml; P1/P2 untouched

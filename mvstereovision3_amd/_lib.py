@@ -217,6 +217,9 @@ def _declare(lib, strict=True):
         "mvsv_prepare_size": ([I, I, I, ctypes.POINTER(I), ctypes.POINTER(I)], I),
         "mvsv_prepare_gray_device": ([P, I, P, Z, Z, I, I, I, I, P, Z, Z], I),
         "mvsv_prepare_gray": ([P, P, Z, I, I, I, I, P, Z], I),
+        "mvsv_tm_validate": ([I, I, I], I),
+        "mvsv_tm": ([P, P, Z, P, Z, I, I, I, P, Z], I),
+        "mvsv_tm_device": ([P, I, P, Z, Z, P, Z, Z, I, I, I, P, Z, Z, I], I),
         "mvsv_stream_create_bm": ([P, I, I, P, I, P, ctypes.POINTER(P)], I),
         "mvsv_stream_create_raw_bm": ([P, P, P, I, P, ctypes.POINTER(P)], I),
         "mvsv_stream_set_bm_params": ([P, P], I),

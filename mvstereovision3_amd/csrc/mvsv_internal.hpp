@@ -283,6 +283,11 @@ int prepare_gray_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t ss, siz
 int stream_copy_device(mvsv_ctx* ctx, hipStream_t stream, int n, const uint8_t* L, size_t ls, size_t lfs,
                        const uint8_t* R, size_t rs, size_t rfs, uint8_t* dL, uint8_t* dR, size_t ds, size_t dfs,
                        int row_bytes, int rows);
+// Disparity::tm (mvsv_tm.hip): the accepted kernel sizes, and n frames on ctx->stream;
+// elem_bytes 1 stores the shift's low byte, 2 the shift as uint16 (strides in bytes)
+int tm_validate(int k, int W, int H, std::string* why);
+int tm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R, size_t rs, size_t rfs,
+              int W, int H, int k, void* dst, size_t ds, size_t dfs, int elem_bytes);
 int reproject_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
                      const float* Q, float* out, size_t os, size_t ofs);
 int mean_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W,

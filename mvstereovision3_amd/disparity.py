@@ -229,6 +229,11 @@ class Disparity:
         return dispCompute.compute(inputImages.mLeft, inputImages.mRight, output)
 
     @staticmethod
+    def tm(inputImages: Stereopair, output, kernelSize: int):
+        """src/disparity.cpp:25-58; returns the (re)allocated 8-bit map."""
+        return tm(inputImages.mLeft, inputImages.mRight, kernelSize)
+
+    @staticmethod
     def loadSGBMParameters(filename: str, disparityObj: StereoSGBM,
                            para: sgbmParameters) -> bool:
         """src/disparity.cpp:60-108: reads configs/sgbm.yml, applies 8 setters + mode.
@@ -258,6 +263,77 @@ class Disparity:
             log.error("Unable to load BM parameters from %s", filename)
             return False
         return True
+
+
+def tm_validate(kernel_size: int, width: int, height: int) -> bool:
+    """mvsv_tm_validate: 1 <= kernel_size <= 31 and kernel_size < min(width, height)."""
+    return lib().mvsv_tm_validate(int(kernel_size), int(width), int(height)) == 0
+
+
+def tm(left, right, kernel_size: int, wide: bool = False):
+    """Disparity::tm (src/disparity.cpp:25-58): for every pixel (i, j) with
+    i < H - k and j < W - k, cv::matchTemplate(CV_TM_CCORR_NORMED) of the k x k
+    template of ``left`` along the row of ``right`` (to the right, up to column
+    W - 2); the first shift with the largest score is stored, 0 elsewhere.
+    Scores are compared in exact integers (include/mvsv.h).
+
+    numpy uint8 (H, W) arrays give a numpy uint8 map through the host entry.
+    torch uint8 device tensors (H, W) or (N, H, W) run on the current torch
+    stream and give a device tensor: uint8 (the shift's low byte, as the
+    reference's ``output.at<char>`` stores it) or, with ``wide``, the shift
+    itself as uint16."""
+    what = "tm"
+    k = int(kernel_size)
+    if _is_torch(left) != _is_torch(right):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: left and right must both be numpy or both torch")
+    if _is_torch(left):
+        import torch
+        if left.dtype != torch.uint8 or right.dtype != torch.uint8:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be uint8")
+        if left.shape != right.shape or left.dim() not in (2, 3):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be (H,W) or (N,H,W), equal")
+        if not left.is_cuda or not right.is_cuda or left.device != right.device:
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: device tensors on one GPU expected")
+        batched = left.dim() == 3
+        Lt = left if batched else left.unsqueeze(0)
+        Rt = right if batched else right.unsqueeze(0)
+        if Lt.stride(2) != 1:
+            Lt = Lt.contiguous()
+        if Rt.stride(2) != 1:
+            Rt = Rt.contiguous()
+        n, H, W = Lt.shape
+        if not tm_validate(k, W, H):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: kernel size {k} not within 1..31 and below min(W, H)")
+        eb = 2 if wide else 1
+        out = torch.empty((n, H, W), dtype=torch.uint16 if wide else torch.uint8, device=left.device)
+        ctx = context(left.device.index or 0)
+        stream = torch.cuda.current_stream(left.device).cuda_stream
+        check(lib().mvsv_set_stream(ctx.handle, ctypes.c_void_p(stream)), ctx.handle)
+        check(lib().mvsv_tm_device(ctx.handle, n, Lt.data_ptr(), Lt.stride(1), Lt.stride(0), Rt.data_ptr(),
+                                   Rt.stride(1), Rt.stride(0), W, H, k, out.data_ptr(), W * eb, H * W * eb, eb),
+              ctx.handle)
+        return out if batched else out[0]
+    L = np.asarray(left)
+    R = np.asarray(right)
+    if L.ndim != 2 or R.ndim != 2 or L.dtype != np.uint8 or R.dtype != np.uint8:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be 2-D CV_8UC1 (uint8)")
+    if L.shape != R.shape:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: left and right sizes differ")
+    if wide:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: the 16-bit map is for device tensors (the host entry is 8 bit)")
+    H, W = L.shape
+    if not tm_validate(k, W, H):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: kernel size {k} not within 1..31 and below min(W, H)")
+    if L.strides[1] != 1:
+        L = np.ascontiguousarray(L)
+    if R.strides[1] != 1:
+        R = np.ascontiguousarray(R)
+    out = np.empty((H, W), np.uint8)
+    ctx = context(0)
+    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    check(lib().mvsv_tm(ctx.handle, L.ctypes.data, L.strides[0], R.ctypes.data, R.strides[0], W, H, k,
+                        out.ctypes.data, out.strides[0]), ctx.handle)
+    return out
 
 
 def synth_pair(seed: int, width: int, height: int, min_disparity: int, num_disparities: int):
