@@ -728,7 +728,7 @@ int bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, con
     const int win = 2 * e.wsz2 + 1;
     // disparities on the lanes (bm_match2_kernel) for blockSize <= 21 and
     // numDisparities <= 128; the 16x16-tile kernel otherwise
-    if (ctx->bm2 && e.wsz2 >= 2 && e.wsz2 <= 10 && e.ndisp <= 128) {
+    if (ctx->opt.bm2 && e.wsz2 >= 2 && e.wsz2 <= 10 && e.ndisp <= 128) {
         const int NR = e.ndisp > 64 ? 2 : 1;
         const int BC = kBm2Waves / NR * kBm2Cols;
         const int gx = (e.ncol + BC - 1) / BC, nrows = e.ymax - e.ymin;
@@ -759,7 +759,7 @@ int bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, con
         // window, ~win / 4 + 1 rows), with a penalty for fewer than four
         // resident blocks per CU (the kernel hides LDS latency with waves);
         // fitted to configs 1 / 2 at batch 1 and 8 (tools/bm_time.py sweep)
-        int TY = ctx->bm_ty;
+        int TY = ctx->opt.bm_ty;
         if (TY <= 0) {
             double best = 1e30;
             for (int ty = 4; ty <= 64; ty += 4) {

@@ -1123,7 +1123,7 @@ bool bsgm_eligible(const mvsv_ctx* ctx, const SgbmEff& e, int n, int H)
 {
     const long bs = 2L * e.SW2 + 1;
     const bool no_wrap = (long)e.P2 + bs * bs * (2L * e.ftzero + 63) + e.P2 <= 32767;
-    return ctx->bitslice && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && no_wrap &&
+    return ctx->opt.bitslice && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && no_wrap &&
            e.W1 > 0 && (size_t)n * H * bs::padq(e.W1) * 16 < ((size_t)1 << 31);
 }
 
@@ -1154,7 +1154,7 @@ static int launch_bs_strips(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const
     if ((++ctx->tri_epoch & 0xffffu) == 0) ++ctx->tri_epoch;
     const unsigned epoch = ctx->tri_epoch;
     const dim3 grid(nstrips * npass * n);
-    const bool tickets = ctx->strip_tickets != 0;
+    const bool tickets = ctx->opt.strip_tickets != 0;
     // MVSV_BS_STATS: per-strip spans and hand-off spin time on stderr
     // (diagnostics only: the buffer is cleared on the context stream, and any
     // failure turns the statistics off instead of touching a null buffer)
@@ -1184,7 +1184,7 @@ static int launch_bs_strips(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const
         return rc;
     hipLaunchKernelGGL((bsgm_strip_kernel<NG, 2, 5>), grid, dim3(Cfg::kThreads), lds, ctx->stream, Bv, Av,
                        aplane, dummy, H, e.W1, npass, (unsigned long long*)ctx->bs_bnd.ptr, epoch, n,
-                       (int*)ctx->status.ptr, ctx->spin_limit, ctx->report_target,
+                       (int*)ctx->status.ptr, ctx->opt.spin_limit, ctx->report_target,
                        tickets ? (long long)ctx->tri_tickets : -1ll, stats, 0);
     rc = check_hip(ctx, hipGetLastError(), "bit-sliced strip kernel");
     if (rc == MVSV_OK && tickets) ctx->tri_tickets += grid.x;
@@ -1288,13 +1288,13 @@ int bsgm_paths(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const int16
         // few and memory-bound): bench 2970 vs 2850 Mpix/s with the lines after
         // the strips on the context stream (MVSV_BS_SERIAL=1, same box, with
         // one-block-per-CU 2-group strips and the grouped planes)
-        const bool side = !ctx->bs_serial;
+        const bool side = !ctx->opt.bs_serial;
         if (side && ((rc = check_hip(ctx, hipEventRecord(ctx->ev_fork, s), "fork")) ||
                      (rc = check_hip(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0), "fork wait"))))
             return rc;
         hipStream_t ls = side ? ctx->aux : s;
         // fused: only L->R here, R->L runs with the WTA (bsgm_rlwta_kernel)
-        const bool fuse = ctx->bs_fuse != 0;
+        const bool fuse = ctx->opt.bs_fuse != 0;
         auto lines = [&]() -> int {
             StageTimer tl(ctx, kStageLines, ls);
             hipLaunchKernelGGL((bsgm_lines4_kernel<2, 5>), dim3((H + 15) / 16, n, fuse ? 1 : 2), dim3(64), 0, ls,
@@ -1309,7 +1309,7 @@ int bsgm_paths(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const int16
             // the other batch in flight (bench 3114-3120 -> 3164-3169 Mpix/s,
             // same box, r06n; one batch alone: strips 1.14 -> 1.15 ms); 4 groups
             // leave no room for the line waves beside them (lines 0.55 -> 2.0 ms)
-            const int ng = ctx->bs_groups ? ctx->bs_groups : (e.fullDP ? 3 : 2);
+            const int ng = ctx->opt.bs_groups ? ctx->opt.bs_groups : (e.fullDP ? 3 : 2);
             uint32_t* dummy = Dv + 2 * dplane;
             rc = ng == 1   ? launch_bs_strips<1>(ctx, n, H, e, Bv, Av, aplane, dummy)
                  : ng == 3 ? launch_bs_strips<3>(ctx, n, H, e, Bv, Av, aplane, dummy)
@@ -1324,7 +1324,7 @@ int bsgm_paths(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const int16
             return rc;
     }
     StageTimer tm(ctx, kStageFinal);
-    if (ctx->bs_fuse) {
+    if (ctx->opt.bs_fuse) {
         // per-pixel records in the (unused) R->L plane's space
         uint32_t* rec = Dv + dplane;
         const int lane_rule = !(e.variant & MVSV_VARIANT_WTA_MIN_D);

@@ -838,13 +838,13 @@ int launch_cost(mvsv_ctx* ctx, int n, int W, int H, const SgbmEff& e, int TY,
     *pinned_hh = false;
     hipStream_t s = ctx->stream;
     int rc;
-    if (ctx->cost2 && e.SH2 <= 7 && e.SW2 == e.SH2) {
+    if (ctx->opt.cost2 && e.SH2 <= 7 && e.SW2 == e.SH2) {
         const Cost2Layout l2 = cost2_layout(e.D, e.SW2, TY);
         const int items = 2 * l2.NX + e.D - 1;
         const bool two = items > kCost2Threads;
         // numDisparities 128 / 256: the pair count is a compile-time
         // constant (unrolled pixel-cost loop, immediate LDS offsets)
-        const int ppc = !ctx->cost_fixed_pp ? 0 : l2.PP == 64 ? 64 : (l2.PP == 128 ? 128 : 0);
+        const int ppc = !ctx->opt.cost_fixed_pp ? 0 : l2.PP == 64 ? 64 : (l2.PP == 128 ? 128 : 0);
         const size_t lbytes = cost2_total_bytes(l2, 2 * e.SH2 + 1, two ? 2 : 1, ppc);
         if (l2.CL >= 1 && items <= kCost2Threads * 2 && lbytes <= 160 * 1024) {
             dim3 grid2((e.W1 + l2.TX - 1) / l2.TX, (H + TY - 1) / TY, n);
@@ -860,7 +860,7 @@ int launch_cost(mvsv_ctx* ctx, int n, int W, int H, const SgbmEff& e, int TY,
             {
                 StageTimer tm(ctx, kStageCost);
                 hipLaunchKernelGGL(kern, grid2, dim3(kCost2Threads), lbytes, s, pre, W, H, e, TY,
-                                   Cv, *Bv ? nullptr : *Rv, Mv, *Bv, ctx->cost_xcd ? 1 : 0);
+                                   Cv, *Bv ? nullptr : *Rv, Mv, *Bv, ctx->opt.cost_xcd ? 1 : 0);
             }
             *pinned_hh = e.fullDP != 0;  // MODE_HH fix-up rows/column written by the kernel
             return check_hip(ctx, hipGetLastError(), "sgbm cost kernel");
@@ -889,10 +889,10 @@ int launch_cost(mvsv_ctx* ctx, int n, int W, int H, const SgbmEff& e, int TY,
 
 bool cost2_runs(const mvsv_ctx* ctx, const SgbmEff& e)
 {
-    if (!ctx->cost2 || e.SH2 > 7 || e.SW2 != e.SH2) return false;
+    if (!ctx->opt.cost2 || e.SH2 > 7 || e.SW2 != e.SH2) return false;
     const Cost2Layout l2 = cost2_layout(e.D, e.SW2, 120);  // (the layout does not depend on the tile height)
     const int items = 2 * l2.NX + e.D - 1;
-    const int ppc = !ctx->cost_fixed_pp ? 0 : l2.PP == 64 ? 64 : (l2.PP == 128 ? 128 : 0);
+    const int ppc = !ctx->opt.cost_fixed_pp ? 0 : l2.PP == 64 ? 64 : (l2.PP == 128 ? 128 : 0);
     const size_t lbytes = cost2_total_bytes(l2, 2 * e.SH2 + 1, items > kCost2Threads ? 2 : 1, ppc);
     return l2.CL >= 1 && items <= kCost2Threads * 2 && lbytes <= 160 * 1024;
 }

@@ -353,37 +353,37 @@ int mvsv_create(mvsv_ctx** out, int hip_device)
     c->report_target = c->report_dev;
     c->stream = c->own;
     if (const char* v = std::getenv("MVSV_STRIP_SPIN_LIMIT"))
-        c->spin_limit = (unsigned)std::strtoul(v, nullptr, 0);
+        c->opt.spin_limit = (unsigned)std::strtoul(v, nullptr, 0);
     // kernel-variant switches for A/B measurement and for testing the
     // general-shape kernels on shapes the specialised ones also cover
     if (const char* v = std::getenv("MVSV_KERNELS")) {
-        if (std::strstr(v, "cost-lds")) c->cost2 = 0;
-        if (std::strstr(v, "path-wave")) c->path16 = 0;
-        if (std::strstr(v, "path-lines")) c->tri = 0;
-        if (std::strstr(v, "bm-tile")) c->bm2 = 0;
-        if (std::strstr(v, "cost-generic")) c->cost_fixed_pp = 0;
+        if (std::strstr(v, "cost-lds")) c->opt.cost2 = 0;
+        if (std::strstr(v, "path-wave")) c->opt.path16 = 0;
+        if (std::strstr(v, "path-lines")) c->opt.tri = 0;
+        if (std::strstr(v, "bm-tile")) c->opt.bm2 = 0;
+        if (std::strstr(v, "cost-generic")) c->opt.cost_fixed_pp = 0;
     }
-    if (const char* v = std::getenv("MVSV_COST_TY")) c->cost_ty = std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("MVSV_PATH_SCHEDULE")) c->path_sched = std::max(0, std::min(2, std::atoi(v)));
-    if (const char* v = std::getenv("MVSV_STRIP_WAVES")) c->strip_waves = std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("MVSV_TRI32")) c->tri32 = std::atoi(v) != 0;
-    if (const char* v = std::getenv("MVSV_FINAL_SPLIT")) c->final_split = std::atoi(v) != 0;
-    if (const char* v = std::getenv("MVSV_COST_RESIDUAL")) c->cost_res = std::atoi(v) != 0;
-    if (const char* v = std::getenv("MVSV_BM_TY")) c->bm_ty = std::max(0, std::min(128, std::atoi(v)));
+    if (const char* v = std::getenv("MVSV_COST_TY")) c->opt.cost_ty = std::max(0, std::atoi(v));
+    if (const char* v = std::getenv("MVSV_PATH_SCHEDULE")) c->opt.path_sched = std::max(0, std::min(2, std::atoi(v)));
+    if (const char* v = std::getenv("MVSV_STRIP_WAVES")) c->opt.strip_waves = std::max(0, std::atoi(v));
+    if (const char* v = std::getenv("MVSV_TRI32")) c->opt.tri32 = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MVSV_FINAL_SPLIT")) c->opt.final_split = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MVSV_COST_RESIDUAL")) c->opt.cost_res = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MVSV_BM_TY")) c->opt.bm_ty = std::max(0, std::min(128, std::atoi(v)));
     if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, hip_device) != hipSuccess) {
         (void)hipGetLastError();
         c->cus = 256;
     }
-    if (const char* v = std::getenv("MVSV_STRIP_ORDER")) c->strip_tickets = std::strcmp(v, "blockidx") != 0;
-    if (const char* v = std::getenv("MVSV_LINES_AUX")) c->lines_aux = std::max(-1, std::min(2, std::atoi(v)));
-    if (const char* v = std::getenv("MVSV_BITSLICE")) c->bitslice = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MVSV_STRIP_ORDER")) c->opt.strip_tickets = std::strcmp(v, "blockidx") != 0;
+    if (const char* v = std::getenv("MVSV_LINES_AUX")) c->opt.lines_aux = std::max(-1, std::min(2, std::atoi(v)));
+    if (const char* v = std::getenv("MVSV_BITSLICE")) c->opt.bitslice = std::atoi(v) != 0;
     if (const char* v = std::getenv("MVSV_GRAPHS")) c->graphs = std::atoi(v) != 0;
-    if (const char* v = std::getenv("MVSV_BS_SERIAL")) c->bs_serial = std::atoi(v) != 0;
-    if (const char* v = std::getenv("MVSV_COST_XCD")) c->cost_xcd = std::atoi(v) != 0;
-    if (const char* v = std::getenv("MVSV_BS_FUSE")) c->bs_fuse = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MVSV_BS_SERIAL")) c->opt.bs_serial = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MVSV_COST_XCD")) c->opt.cost_xcd = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MVSV_BS_FUSE")) c->opt.bs_fuse = std::atoi(v) != 0;
     if (const char* v = std::getenv("MVSV_BS_GROUPS")) {
         const int g = std::atoi(v);
-        c->bs_groups = (g >= 1 && g <= 5) ? g : 0;
+        c->opt.bs_groups = (g >= 1 && g <= 5) ? g : 0;
     }
     *out = c;
     return MVSV_OK;
@@ -518,31 +518,31 @@ int mvsv_set_option(mvsv_ctx* ctx, int option, long long value)
     case MVSV_OPT_STRIP_SPIN_LIMIT:
         if (value < 0 || value > 0xffffffffLL)
             return set_error(ctx, MVSV_E_INVALID_ARG, "spin limit must be 0..2^32-1");
-        ctx->spin_limit = (unsigned)value;
+        ctx->opt.spin_limit = (unsigned)value;
         return MVSV_OK;
     case MVSV_OPT_BM_TILE_ROWS:
         if (value < 0 || value > 128) return set_error(ctx, MVSV_E_INVALID_ARG, "BM tile rows must be 0..128");
-        ctx->bm_ty = (int)value;
+        ctx->opt.bm_ty = (int)value;
         return MVSV_OK;
     case MVSV_OPT_PATH_SCHEDULE:
         if (value < 0 || value > 2) return set_error(ctx, MVSV_E_INVALID_ARG, "path schedule must be 0..2");
-        ctx->path_sched = (int)value;
+        ctx->opt.path_sched = (int)value;
         return MVSV_OK;
     case MVSV_OPT_STRIP_WAVES:
         if (value < 0 || value > 64) return set_error(ctx, MVSV_E_INVALID_ARG, "strip waves must be 0..64");
-        ctx->strip_waves = (int)value;
+        ctx->opt.strip_waves = (int)value;
         return MVSV_OK;
     case MVSV_OPT_STRIP_TICKETS:
         if (value < 0 || value > 1) return set_error(ctx, MVSV_E_INVALID_ARG, "strip tickets must be 0 or 1");
-        ctx->strip_tickets = (int)value;
+        ctx->opt.strip_tickets = (int)value;
         return MVSV_OK;
     case MVSV_OPT_COST_RESIDUAL:
         if (value < 0 || value > 1) return set_error(ctx, MVSV_E_INVALID_ARG, "cost residual must be 0 or 1");
-        ctx->cost_res = (int)value;
+        ctx->opt.cost_res = (int)value;
         return MVSV_OK;
     case MVSV_OPT_BITSLICE:
         if (value < 0 || value > 1) return set_error(ctx, MVSV_E_INVALID_ARG, "bitslice must be 0 or 1");
-        ctx->bitslice = (int)value;
+        ctx->opt.bitslice = (int)value;
         return MVSV_OK;
     default:
         return set_error(ctx, MVSV_E_INVALID_ARG, "unknown option");

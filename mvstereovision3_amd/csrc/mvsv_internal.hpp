@@ -81,6 +81,34 @@ struct DeviceGuard {
 // instead of a hang.  mvsv_set_option(MVSV_OPT_STRIP_SPIN_LIMIT) overrides it.
 constexpr unsigned kStripSpinLimitDefault = 1u << 20;
 
+// The launch-shape options of a context (MVSV_* environment at creation,
+// mvsv_set_option): which kernels run and how their launches are cut.  A frame
+// stream's own lane contexts take the caller context's as a whole.
+struct KernelOptions {
+    // strip blocks draw their strip as a ticket (status[2]) unless strip_tickets
+    // is 0 (blockIdx order, MVSV_STRIP_ORDER=blockidx)
+    int strip_tickets = 1;
+    unsigned spin_limit = kStripSpinLimitDefault;
+    int path16 = 1;  // 16-lanes-per-scanline path kernels where D allows
+    int cost2 = 1;   // register-ring cost kernel where blockSize <= 15
+    int cost_fixed_pp = 1;  // fixed-pair-count cost kernels for D = 128 / 256 (MVSV_KERNELS=cost-generic: off)
+    int cost_ty = 0;  // cost-volume tile height (0 = by image height); MVSV_COST_TY for A/B runs
+    int tri = 1;     // sheared-strip kernels: three directions per sweep
+    int path_sched = 0;   // 16-lane path schedule: 0 = by launch size, 1 = strips, 2 = directions side by side
+    int tri32 = 1;        // D = 256 narrow strips on 32 lanes per column (MVSV_TRI32)
+    int final_split = 1;  // side by side on byte / u16 planes: R->L as a chain set + per-pixel WTA (MVSV_FINAL_SPLIT)
+    int strip_waves = 0;  // compute waves per strip (0 = by launch size; 4 or the wide count forces)
+    int cost_res = 1;     // direction passes read the cost residual plane where exact (MVSV_OPT_COST_RESIDUAL)
+    int lines_aux = -1;  // L->R line kernel beside the strip kernel: -1 = small launches only, 0 / 1 / 2 force
+    int bitslice = 1;    // bit-sliced MODE_HH paths where they apply (MVSV_OPT_BITSLICE, env MVSV_BITSLICE)
+    int bs_groups = 0;   // column groups (3 direction waves each) per bit-sliced strip: 1-5 (MVSV_BS_GROUPS), 0 = by mode
+    int cost_xcd = 1;    // cost kernel: whole row bands per XCD (MVSV_COST_XCD=0: blockIdx order, A/B)
+    int bs_fuse = 1;     // bit-sliced batches: R->L lines fused with the WTA (MVSV_BS_FUSE=0: separate, A/B)
+    int bs_serial = 0;   // 1: bit-sliced line kernel after the strips on the context stream (MVSV_BS_SERIAL, A/B)
+    int bm2 = 1;     // StereoBM: disparities-on-lanes match kernel where blockSize <= 21, D <= 128
+    int bm_ty = 0;   // its tile height (0 = chosen per launch); MVSV_BM_TY for A/B runs
+};
+
 }  // namespace mvsv
 
 struct mvsv_ctx {
@@ -95,12 +123,10 @@ struct mvsv_ctx {
     // boundary granules (tri_bnd is re-zeroed whenever they wrap), all 32 bits
     // go into status[0] when that launch gives up a wait (no per-call reset)
     unsigned tri_epoch = 0;
-    // strip blocks draw their strip as a ticket (status[2]) unless strip_tickets
-    // is 0 (blockIdx order, MVSV_STRIP_ORDER=blockidx); tri_tickets = the first
-    // ticket of the next launch (the counter is zeroed with the status word)
-    int strip_tickets = 1;
+    // the first ticket of the next strip launch (opt.strip_tickets; the counter is
+    // zeroed with the status word)
     unsigned tri_tickets = 0;
-    unsigned spin_limit = mvsv::kStripSpinLimitDefault;
+    mvsv::KernelOptions opt;
     // given-up strip waits are reported into host-mapped ints: `report` is the
     // context's sticky word (device calls; read and cleared by the next call,
     // mvsv_synchronize and the host-pointer calls), report_target is where the
@@ -116,25 +142,6 @@ struct mvsv_ctx {
     bool last_valid = false;
     hipStream_t aux = nullptr;  // second stream for concurrent direction passes
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int path16 = 1;  // 16-lanes-per-scanline path kernels where D allows
-    int cost2 = 1;   // register-ring cost kernel where blockSize <= 15
-    int cost_fixed_pp = 1;  // fixed-pair-count cost kernels for D = 128 / 256 (MVSV_KERNELS=cost-generic: off)
-    int cost_ty = 0;  // cost-volume tile height (0 = by image height); MVSV_COST_TY for A/B runs
-    int tri = 1;     // sheared-strip kernels: three directions per sweep
-    int path_sched = 0;   // 16-lane path schedule: 0 = by launch size, 1 = strips, 2 = directions side by side
-    int tri32 = 1;
-    int final_split = 1;  // side by side on byte / u16 planes: R->L as a chain set + per-pixel WTA (MVSV_FINAL_SPLIT)
-    int tri_xseg = 0;     // A/B: one strip chain's neighbours on one XCD (MVSV_TRI_XSEG)        // D = 256 narrow strips on 32 lanes per column (MVSV_TRI32)
-    int strip_waves = 0;  // compute waves per strip (0 = by launch size; 4 or the wide count forces)
-    int cost_res = 1;     // direction passes read the cost residual plane where exact (MVSV_OPT_COST_RESIDUAL)
-    int lines_aux = -1;  // L->R line kernel beside the strip kernel: -1 = small launches only, 0 / 1 / 2 force
-    int bitslice = 1;    // bit-sliced MODE_HH paths where they apply (MVSV_OPT_BITSLICE, env MVSV_BITSLICE)
-    int bs_groups = 0;   // column groups (3 direction waves each) per bit-sliced strip: 1-5 (MVSV_BS_GROUPS), 0 = by mode
-    int cost_xcd = 1;    // cost kernel: whole row bands per XCD (MVSV_COST_XCD=0: blockIdx order, A/B)
-    int bs_fuse = 1;     // bit-sliced batches: R->L lines fused with the WTA (MVSV_BS_FUSE=0: separate, A/B)
-    int bs_serial = 0;   // 1: bit-sliced line kernel after the strips on the context stream (MVSV_BS_SERIAL, A/B)
-    int bm2 = 1;     // StereoBM: disparities-on-lanes match kernel where blockSize <= 21, D <= 128
-    int bm_ty = 0;   // its tile height (0 = chosen per launch); MVSV_BM_TY for A/B runs
     int cus = 256;   // compute units of the device (launch-shape choices)
     // HIP graphs (round 6): a small SGBM launch (no strip chain, whose launches
     // carry per-launch epochs) repeated with the same arguments is captured once

@@ -7,10 +7,13 @@
 // launched as runs of consecutive slots; a run never wraps past the ring's end,
 // so its slots are one contiguous [frame][H][W] block of the device arrays.
 // Also here, for the same reason: where the frames of a batched device push go
-// (ring_push_segments) and which source pointers such a push accepts (ring_source_ok).
+// (ring_push_segments), which source pointers such a push accepts (ring_source_ok),
+// the layout of a stage's pinned slot (ring_slot_block) and the geometry of a push
+// of each kind (ring_push_geom).
 #pragma once
 
 #include <algorithm>
+#include <cstddef>
 
 namespace mvsv {
 
@@ -75,6 +78,60 @@ inline bool ring_source_ok(bool query_ok, PtrKind kind, int ptr_device, int stre
     case kPtrManaged: return true;
     default: return false;
     }
+}
+
+// One slot of a stage's pinned host block: three parts one after the other, the
+// second aligned to mid_align (a power of two), the slot padded to 16 bytes.
+// An image stage keeps (image | int16 min, max | nothing), mid_align 2; the sample
+// points keep (float values | int count | hit records), mid_align 4.
+struct SlotBlock {
+    size_t mid = 0, tail = 0;  // offsets of the second and the third part
+    size_t bytes = 0;          // from one slot to the next
+};
+
+inline SlotBlock ring_slot_block(size_t first_bytes, size_t mid_align, size_t mid_bytes, size_t tail_bytes)
+{
+    SlotBlock b;
+    b.mid = (first_bytes + mid_align - 1) & ~(mid_align - 1);
+    b.tail = b.mid + mid_bytes;
+    b.bytes = (b.tail + tail_bytes + 15) & ~(size_t)15;
+    return b;
+}
+
+// What a push copies and where it lands in a slot's staging and device buffers,
+// which share one layout: `rows` rows of `row` bytes per image, `stride` bytes
+// apart.  right != 0: the pair is one buffer, the right image `right` bytes after
+// the left; right == 0: two buffers (the matcher's own input arrays).  `frame`:
+// bytes from one slot's device buffer(s) to the next slot's.
+enum PushKind { kPushRectified, kPushRaw, kPushBgr };
+
+struct PushGeom {
+    int rows;
+    size_t row, stride, right, frame;
+};
+
+// W x H: the stream's (rectified) size; rawW x rawH: a raw stream's camera frame;
+// bgrW x bgrH: the colour frame, its staged rows padded to 4 bytes (packed loads).
+inline PushGeom ring_push_geom(PushKind kind, int W, int H, int rawW, int rawH, int bgrW, int bgrH)
+{
+    PushGeom g{};
+    if (kind == kPushRaw) {
+        g.rows = rawH;
+        g.row = g.stride = (size_t)rawW;
+        g.right = g.stride * g.rows;
+        g.frame = 2 * g.right;
+    } else if (kind == kPushBgr) {
+        g.rows = bgrH;
+        g.row = 3 * (size_t)bgrW;
+        g.stride = (g.row + 3) & ~(size_t)3;
+        g.right = g.stride * g.rows;
+        g.frame = 2 * g.right;
+    } else {
+        g.rows = H;
+        g.row = g.stride = (size_t)W;
+        g.frame = g.stride * g.rows;
+    }
+    return g;
 }
 
 }  // namespace mvsv

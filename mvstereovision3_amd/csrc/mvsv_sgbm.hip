@@ -2180,7 +2180,7 @@ void launch_final16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const 
 // the chain-free WTA saves); MODE_HH D 64 1.01 either way
 static bool wta_split(const mvsv_ctx* ctx, const SgbmEff& e)
 {
-    return ctx->final_split && e.P2 > 15 && e.D <= 32;
+    return ctx->opt.final_split && e.P2 > 15 && e.D <= 32;
 }
 
 static bool sgbm_no_wrap(const SgbmEff& e)
@@ -2195,27 +2195,27 @@ static bool sgbm_no_wrap(const SgbmEff& e)
 // D <= 128 (one cost kernel wave segment holds a pixel's D costs).
 static bool use_residual(const mvsv_ctx* ctx, const SgbmEff& e, int sched)
 {
-    return ctx->cost_res && (sched == 1 || sched == 2) && sgbm_no_wrap(e) && 3 * e.P2 <= 15 &&
+    return ctx->opt.cost_res && (sched == 1 || sched == 2) && sgbm_no_wrap(e) && 3 * e.P2 <= 15 &&
            (e.D == 32 || e.D == 64 || e.D == 128);
 }
 
 static bool use_strips(const mvsv_ctx* ctx, const SgbmEff& e, int H)
 {
-    return ctx->tri && (size_t)H * e.W1 * e.D < ((size_t)1 << 31);
+    return ctx->opt.tri && (size_t)H * e.W1 * e.D < ((size_t)1 << 31);
 }
 
 // Path schedule of the 16-lane kernels (D = 32 / 64 / 128 / 256):
 // 2 = all line directions side by side (sgbm_pathdirs16_kernel, one 4-bit plane
 // per direction, P2 <= 15) -- the latency shape for launches too small to fill
 // the chip with strips (one camera frame); 1 = sheared strips (batches).
-// ctx->path_sched: 0 = by launch size, 1 / 2 force (tests, A/B).
+// ctx->opt.path_sched: 0 = by launch size, 1 / 2 force (tests, A/B).
 static int path_schedule(const mvsv_ctx* ctx, const SgbmEff& e, int H, int n)
 {
-    if (e.D == 16 && ctx->path16 && ctx->path_sched != 1) return 2;  // launch_paths_d16
-    if (!ctx->path16 || !(e.D == 32 || e.D == 64 || e.D == 128 || e.D == 256)) return 0;
-    const bool dirs_ok = e.P2 <= 15 || ctx->path_sched == 2;  // nibble planes; wider planes when forced
-    if (ctx->path_sched == 2) return 2;
-    if (ctx->path_sched == 0 && bsgm_eligible(ctx, e, n, H) && e.SH2 <= 7 && e.SW2 == e.SH2) {
+    if (e.D == 16 && ctx->opt.path16 && ctx->opt.path_sched != 1) return 2;  // launch_paths_d16
+    if (!ctx->opt.path16 || !(e.D == 32 || e.D == 64 || e.D == 128 || e.D == 256)) return 0;
+    const bool dirs_ok = e.P2 <= 15 || ctx->opt.path_sched == 2;  // nibble planes; wider planes when forced
+    if (ctx->opt.path_sched == 2) return 2;
+    if (ctx->opt.path_sched == 0 && bsgm_eligible(ctx, e, n, H) && e.SH2 <= 7 && e.SW2 == e.SH2) {
         // bit-sliced regime (round 6): the side-by-side chains' work grows with
         // the direction-pixels, the strips' time with the chain length; measured
         // (8 frames, MI355X r06e): 640x480 5 paths 0.90 side vs 1.11 ms strips,
@@ -2225,7 +2225,7 @@ static int path_schedule(const mvsv_ctx* ctx, const SgbmEff& e, int H, int n)
         if (dirpix <= 12000000LL) return 2;
         return use_strips(ctx, e, H) ? 1 : 0;
     }
-    if (ctx->path_sched == 0 && dirs_ok) {
+    if (ctx->opt.path_sched == 0 && dirs_ok) {
         const int wide = e.D > 128 ? 7 : 15;
         const long long blocks = (long long)(e.fullDP ? 2 : 1) * n * ((e.W1 + H - 1 + 4 * wide - 1) / (4 * wide));
         // measured: one 640x480 or 1280x960 frame and two 640x480 frames gain
@@ -2233,7 +2233,7 @@ static int path_schedule(const mvsv_ctx* ctx, const SgbmEff& e, int H, int n)
         // lose (1.87 -> 1.95 ms: seven planes into the final kernel)
         if (2 * blocks <= ctx->cus) return 2;
     }
-    if (ctx->path_sched == 0 && e.P2 > 15) {
+    if (ctx->opt.path_sched == 0 && e.P2 > 15) {
         // byte / u16 planes (liveDisparity's create(0, 64, 9, 648, 2592)): side by
         // side while the planes stay small -- their bytes against the strip
         // chain's latency.  Measured (1280x960, MI355X r06 s2a / d16a): MODE_SGBM
@@ -2297,7 +2297,7 @@ int launch_tri_wv(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const void* Cv,
     // (stream lanes, batches in flight), so blockIdx order would rest on
     // in-order dispatch; tickets never do.  MVSV_OPT_STRIP_TICKETS = 0 keeps
     // blockIdx order for A/B runs.
-    const bool tickets = ctx->strip_tickets != 0;
+    const bool tickets = ctx->opt.strip_tickets != 0;
     if (TL::kBytes > 65536 &&
         (rc = check_hip(ctx, hipFuncSetAttribute((const void*)sgbm_tri_kernel<NP, WV, LPC, AccT, NW, RES>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)TL::kBytes),
@@ -2306,7 +2306,7 @@ int launch_tri_wv(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const void* Cv,
     hipLaunchKernelGGL((sgbm_tri_kernel<NP, WV, LPC, AccT, NW, RES>), grid, dim3(TriCfg<NP, WV, LPC>::kThreads), TL::kBytes,
                        ctx->stream, Cv, Av, plane, (AccT*)ctx->dummy.ptr, H, e.W1, e.D, npass, e.P1,
                        e.P2, (unsigned long long*)ctx->tri_bnd.ptr, epoch, n, nstrips,
-                       (int*)ctx->status.ptr, ctx->spin_limit, ctx->report_target, stats, trace_h,
+                       (int*)ctx->status.ptr, ctx->opt.spin_limit, ctx->report_target, stats, trace_h,
                        tickets ? (long long)ctx->tri_tickets : -1ll);
     rc = check_hip(ctx, hipGetLastError(), "sgbm sheared-strip path kernel");
     if (rc == MVSV_OK && tickets) ctx->tri_tickets += grid.x;  // one ticket per block (u32 wrap is harmless)
@@ -2365,7 +2365,7 @@ int launch_tri_lpc(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const void* Cv
 {
     constexpr int wide = tri_wide_waves<NP, LPC>(), narrow = tri_narrow_waves<NP, LPC>();
     constexpr int cpw = 64 / LPC;
-    int wv = ctx->strip_waves;
+    int wv = ctx->opt.strip_waves;
     if (wv != wide && wv != narrow) {
         const long long blocks = (long long)npass * n * ((e.W1 + H - 1 + cpw * wide - 1) / (cpw * wide));
         wv = blocks < ctx->cus ? narrow : wide;
@@ -2383,7 +2383,7 @@ int launch_tri(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const void* Cv, Ac
         // 32 lanes per column (MVSV_TRI32 = 0: the 16-lane narrow strips)
         constexpr int wide = tri_wide_waves<NP, 16>();
         const long long blocks = (long long)npass * n * ((e.W1 + H - 1 + 4 * wide - 1) / (4 * wide));
-        if (ctx->tri32 && ctx->strip_waves == 0 && blocks < ctx->cus)
+        if (ctx->opt.tri32 && ctx->opt.strip_waves == 0 && blocks < ctx->cus)
             return launch_tri_wv<NP / 2, tri_narrow_waves<NP / 2, 32>(), 32, AccT, NW, RES>(ctx, n, H, e, Cv, Av,
                                                                                            plane, npass);
     }
@@ -2432,14 +2432,14 @@ int launch_paths_tri(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16
         // blocks, 132 narrow D = 128 MODE_HH blocks).  Two config-5 frames (D 256,
         // 248 narrow blocks) had the lines beside them at 2.68 ms instead of
         // 0.66 for one frame (r04g c5_frame.jsonl): every CU held a strip.
-        int aux_mode = ctx->lines_aux;
+        int aux_mode = ctx->opt.lines_aux;
         if (aux_mode < 0) {
             constexpr int wide = tri_wide_waves<NP>(), narrow = tri_narrow_waves<NP>();
             auto nblocks = [&](int wv) {
                 return (long long)npass * n * ((e.W1 + H - 1 + 4 * wv - 1) / (4 * wv));
             };
-            const int wv = ctx->strip_waves == wide || ctx->strip_waves == narrow
-                               ? ctx->strip_waves
+            const int wv = ctx->opt.strip_waves == wide || ctx->opt.strip_waves == narrow
+                               ? ctx->opt.strip_waves
                                : (nblocks(wide) < ctx->cus ? narrow : wide);
             // Round 6: byte / u16 planes at D <= 64 run the lines beside the
             // strips in batches too (liveDisparity default, 1280x960 x 4 / x 8:
@@ -2677,8 +2677,8 @@ int sgbm_plan(const mvsv_ctx* ctx, const SgbmEff& e, int n, int H)
 {
     if (e.minX1 >= e.maxX1) return 0;
     const int sched = path_schedule(ctx, e, H, n);
-    const bool bs = bsgm_eligible(ctx, e, n, H) && (sched == 1 || sched == 2) && ctx->path16 && ctx->tri &&
-                    ctx->cost_fixed_pp && e.SH2 <= 7 && e.SW2 == e.SH2 && cost2_runs(ctx, e);
+    const bool bs = bsgm_eligible(ctx, e, n, H) && (sched == 1 || sched == 2) && ctx->opt.path16 && ctx->opt.tri &&
+                    ctx->opt.cost_fixed_pp && e.SH2 <= 7 && e.SW2 == e.SH2 && cost2_runs(ctx, e);
     int plan = (bs ? MVSV_PLAN_BITSLICE : 0) | (sched == 2 ? MVSV_PLAN_SIDE : 0) | (sched == 1 ? MVSV_PLAN_STRIPS : 0);
     if (!bs && use_residual(ctx, e, sched) && cost2_runs(ctx, e)) plan |= MVSV_PLAN_RESIDUAL;
     return plan;
@@ -2714,8 +2714,8 @@ int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, c
     // (frame batches: the bit-sliced strips; launches too small to fill the
     // GPU with strips -- one camera frame, schedule 2 -- the bit-sliced
     // directions side by side, each on its own chains: bsgm_paths)
-    const bool bs = bsgm_eligible(ctx, e, n, H) && (sched == 1 || sched == 2) && ctx->path16 && ctx->tri &&
-                    ctx->cost2 && ctx->cost_fixed_pp && e.SH2 <= 7 && e.SW2 == e.SH2;
+    const bool bs = bsgm_eligible(ctx, e, n, H) && (sched == 1 || sched == 2) && ctx->opt.path16 && ctx->opt.tri &&
+                    ctx->opt.cost2 && ctx->opt.cost_fixed_pp && e.SH2 <= 7 && e.SW2 == e.SH2;
     uint32_t* Bv = nullptr;
     const int nplanes = sched == 2 ? (e.fullDP ? 7 : 4) + (wta_split(ctx, e) ? 1 : 0)
                                    : sched == 1 ? (e.fullDP ? 3 : 2) : 1;
@@ -2756,8 +2756,8 @@ int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, c
     // Taller tiles re-read fewer halo rows (2*SH2 per tile); shorter ones give
     // small batches enough blocks (>= 2 per CU) to fill the chip.
     int TY = 16;
-    if (ctx->cost_ty > 0) {
-        TY = ctx->cost_ty;
+    if (ctx->opt.cost_ty > 0) {
+        TY = ctx->opt.cost_ty;
     } else if (H >= 256) {
         const int TX = cost2_layout(e.D, e.SW2, 120).TX;
         const long tiles_x = (e.W1 + TX - 1) / TX;
@@ -2802,7 +2802,7 @@ int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, c
     }
 
     const int np = (e.D + 127) / 128;
-    const bool wide = ctx->path16 && (e.D == 32 || e.D == 64 || e.D == 128 || e.D == 256);
+    const bool wide = ctx->opt.path16 && (e.D == 32 || e.D == 64 || e.D == 128 || e.D == 256);
     if (Bv) {
         rc = bsgm_paths(ctx, n, H, W, e, Cv, Bv, Mv, raw, sched == 2);
     } else if (e.D == 16 && sched == 2) {

@@ -55,12 +55,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
 
 #include "mvsv_internal.hpp"
 #include "mvsv_ring.hpp"
+#include "mvsv_stream_mem.hpp"
 
 using namespace mvsv;
 
@@ -155,6 +157,97 @@ static void copy_rows(uint8_t* dst, size_t ds, const uint8_t* src, size_t ss, si
     for (int y = y0; y < y1; y++) std::memcpy(dst + (size_t)y * ds, src + (size_t)y * ss, W);
 }
 
+// The optional stages of a stream: plain structs that own their buffers, so
+// `stage = {}` switches one off and frees it.  stream_launch walks them in a fixed
+// order: mean grid, sample points, display, view (reads the two before it), cloud,
+// sharpness.
+
+// SamplepointDetection's lattice over roi of every frame
+// (mvsv_stream_enable_samplepoints): values, hit count and hit records per slot, on
+// the device and in one pinned host block
+struct Samplepoints {
+    bool on = false;
+    mvsv_rect roi{};
+    int radius = 0, max_hits = 0, npts = 0;
+    float Q[16] = {}, first = 0, second = 0;
+    DevArray<float> dVal;             // [depth][npts]
+    DevArray<int> dCnt;               // [depth]
+    DevArray<mvsv_sample_hit> dHits;  // [depth][max_hits]
+    PinnedArray<uint8_t> host;        // [depth] x (values, count, hits), lay.bytes each
+    SlotBlock lay;
+    float* values(long i) const { return (float*)(host + (size_t)i * lay.bytes); }
+    int* count(long i) const { return (int*)(host + (size_t)i * lay.bytes + lay.mid); }
+    mvsv_sample_hit* hits(long i) const { return (mvsv_sample_hit*)(host + (size_t)i * lay.bytes + lay.tail); }
+    float* dev_values(long i) const { return dVal ? dVal + (size_t)i * npts : nullptr; }
+    mvsv_sample_hit* dev_hits(long i) const { return dHits + (size_t)i * max_hits; }
+};
+
+// A dense image of roi of every frame and the (smin, smax) it was scaled by, per
+// slot, on the device and in one pinned host block: the 8-bit display map
+// (mvsv_stream_enable_display) and the BGR detection view (mvsv_stream_enable_view)
+struct ImageStage {
+    bool on = false;
+    mvsv_rect roi{};
+    size_t bytes = 0, row_bytes = 0;  // of a frame's image, of one of its rows
+    DevArray<uint8_t> dImg;           // [depth][bytes]
+    DevArray<int16_t> dMM;            // [depth][2]
+    PinnedArray<uint8_t> host;        // [depth] x (image, min, max), lay.bytes each
+    SlotBlock lay;
+    int width() const { return roi.x1 - roi.x0; }
+    int height() const { return roi.y1 - roi.y0; }
+    uint8_t* image(long i) const { return host + (size_t)i * lay.bytes; }
+    int16_t* minmax(long i) const { return (int16_t*)(image(i) + lay.mid); }
+    uint8_t* dev_image(long i) const { return dImg + (size_t)i * bytes; }
+    int16_t* dev_minmax(long i) const { return dMM + 2 * i; }
+};
+
+// What tells the display from the view at the entry points: the bit of
+// mvsv_stream_set_host_outputs that keeps its image on the device, and its messages.
+struct ImageTexts {
+    int host_bit;
+    const char *not_enabled, *host_off, *stride, *null_out;
+};
+static const ImageTexts kDisplayTexts = {
+    MVSV_HOST_DISPLAY, "the display is not enabled on this stream",
+    "the host display map is switched off (mvsv_stream_set_host_outputs)",
+    "display stride smaller than the ROI's width", "null map pointer"};
+static const ImageTexts kViewTexts = {
+    MVSV_HOST_VIEW, "the view is not enabled on this stream",
+    "the host view is switched off (mvsv_stream_set_host_outputs)",
+    "view stride smaller than three times the ROI's width", "null view pointer"};
+
+// the point cloud of roi of every frame (mvsv_stream_enable_cloud): the records
+// stay in a device ring, (count, min, max) per slot come to the host
+struct Cloud {
+    bool on = false;
+    mvsv_rect roi{};
+    float Q[16] = {};
+    int max_points = 0;
+    DevArray<mvsv_cloud_point> dRec;  // [depth][max_points]
+    DevArray<int> dHdr;               // [depth][3] (count, min, max)
+    PinnedArray<int> hHdr;            // [depth][3]
+    Stream copy;                      // front_cloud's copies: not behind the later frames' downloads
+    mvsv_cloud_point* dev_records(long i) const { return dRec + (size_t)i * max_points; }
+};
+
+// the focus measure of every pushed pair (mvsv_stream_enable_sharpness): S4 of
+// roi[0] of the left and roi[1] of the right pushed image per slot
+struct Sharpness {
+    bool on = false;
+    mvsv_rect roi[2] = {};
+    DevArray<int64_t> dSum;     // [depth][2]
+    PinnedArray<int64_t> hSum;  // [depth][2]
+};
+
+// colour frames (mvsv_stream_enable_bgr): a pushed BGR pair is staged per slot and
+// prepared into the slot's dL / dR on the lane's stream
+struct Bgr {
+    bool on = false;
+    int W = 0, H = 0, halve = 0, variant = 0;
+    DevArray<uint8_t> dev;      // [depth] pairs in kPushBgr's geometry
+    PinnedArray<uint8_t> host;  // the same, staged
+};
+
 struct mvsv_stream {
     mvsv_ctx* ctx = nullptr;
     std::vector<mvsv_ctx*> lanes;  // [0] = ctx; the rest are owned by the stream
@@ -167,183 +260,68 @@ struct mvsv_stream {
     BmEff bm_eff{};
     bool grid = false;
     mvsv_rect roi{};
-    hipStream_t up = nullptr, down = nullptr;
+    Stream up, down;
     struct Slot {
-        uint8_t *hL = nullptr, *hR = nullptr;  // pinned
-        uint8_t *hRectL = nullptr, *hRectR = nullptr;  // pinned, keep_rectified streams
-        uint8_t* dRaw = nullptr;                       // [2][rawH][rawW], raw streams
-        uint8_t *hBgr = nullptr, *dBgr = nullptr;      // [2][bgrH][bgrRow], pinned / device, with enable_bgr
-        bool is_bgr = false;                           // the pending frame was pushed as BGR
-        int16_t* hOut = nullptr;
-        float* hMeans = nullptr;
+        PinnedArray<uint8_t> hL, hR;          // the pushed pair
+        PinnedArray<uint8_t> hRectL, hRectR;  // keep_rectified streams
+        PinnedArray<int16_t> hOut;
+        PinnedArray<float> hMeans;
+        // the slot's part of the stream's device arrays
+        uint8_t* dRaw = nullptr;  // [2][rawH][rawW], raw streams
         uint8_t *dL = nullptr, *dR = nullptr;
         int16_t* dOut = nullptr;
         float* dMeans = nullptr;
-        hipEvent_t uploaded = nullptr, computed = nullptr, done = nullptr;
-        hipEvent_t released = nullptr;  // pop_device's copy of dOut on the consumer's stream
-        bool release_pending = false;   // the slot's next launch waits for `released`
+        bool is_bgr = false;  // the pending frame was pushed as BGR (written by every push)
+        Event uploaded, computed, done;
+        Event released;                // pop_device's copy of dOut on the consumer's stream
+        bool release_pending = false;  // the slot's next launch waits for `released`
         int status = MVSV_OK;
-        int run_len = 0;     // > 0: this slot starts a frame-batch launch of run_len slots
+        int run_len = 0;       // > 0: this slot starts a frame-batch launch of run_len slots
         bool gave_up = false;  // the launch of this frame gave up a strip wait
     };
     std::vector<Slot> slots;
-    uint8_t *dL_all = nullptr, *dR_all = nullptr;  // [depth][H][W]
-    int16_t* dOut_all = nullptr;
-    float* dMeans_all = nullptr;  // [depth][81]
+    DevArray<uint8_t> dL_all, dR_all;  // [depth][H][W]
+    DevArray<int16_t> dOut_all;
+    DevArray<float> dMeans_all;  // [depth][81]
     // per-slot report words (host-mapped): a launch starting at slot i reports
     // a given-up strip wait into rep[i], read when slot i is popped
-    int* rep = nullptr;
+    PinnedArray<int> rep;
     int* rep_dev = nullptr;
-    long head = 0, tail = 0;      // pushed / popped frame counters
-    long launched = 0;            // frames whose compute is enqueued
+    long head = 0, tail = 0;  // pushed / popped frame counters
+    long launched = 0;        // frames whose compute is enqueued
     int batch = 1;
-    int host_mask = MVSV_HOST_ALL;     // the per-frame D2H copies that are enqueued (set_host_outputs)
-    hipEvent_t producer_ev = nullptr;  // push_device: what the producer had queued
-    hipEvent_t fence_ev = nullptr;     // mvsv_stream_fence
+    int host_mask = MVSV_HOST_ALL;  // the per-frame D2H copies that are enqueued (set_host_outputs)
+    Event producer_ev;              // push_device: what the producer had queued
+    Event fence_ev;                 // mvsv_stream_fence
     bool fenced = false;
-    CopyPool* pool = nullptr;     // host copies of push / pop (nullptr: caller's thread only)
+    std::unique_ptr<CopyPool> pool;  // host copies of push / pop (null: caller's thread only)
     // raw stream (mvsv_stream_create_raw): pushed frames are raw camera pairs,
     // rectified (cropped, resized) into the slots' dL / dR ahead of their SGBM
     bool raw = false;
-    int rawW = 0, rawH = 0;       // the camera frame; a slot's hL / hR hold one each
-    int cropW = 0, cropH = 0;     // the display ROI's size
-    double factor = 0;            // 0: the crop is the frame; else cv::resize of the crop
-    bool keep = false;            // the rectified pair comes back to the host too
-    uint8_t* dRaw_all = nullptr;  // [depth][2][rawH][rawW]
-    int16_t* dMapXY = nullptr;    // [2][cropH][mapStride] (sx, sy), ROI only
-    uint16_t* dMapFrac = nullptr; // [2][cropH][mapStride] ay * 32 + ax
-    size_t mapStride = 0;         // entries per map row: cropW rounded up to 4, padding zero
-    uint8_t *dCropL = nullptr, *dCropR = nullptr;  // [depth][cropH][cropW] each, with a factor
-    // SamplepointDetection's lattice over sp_roi of every frame
-    // (mvsv_stream_enable_samplepoints): values, hit count and hit records per
-    // slot, on the device and in one pinned host block
-    bool sp = false;
-    mvsv_rect sp_roi{};
-    int sp_radius = 0, sp_max = 0, sp_npts = 0;
-    float sp_Q[16] = {}, sp_first = 0, sp_second = 0;
-    float* dSpVal = nullptr;            // [depth][sp_npts]
-    int* dSpCnt = nullptr;              // [depth]
-    mvsv_sample_hit* dSpHits = nullptr; // [depth][sp_max]
-    uint8_t* hSp = nullptr;             // pinned: [depth] x (values, count, hits), sp_slot_bytes each
-    size_t sp_slot_bytes = 0;
-    float* sp_values(long i) const { return (float*)(hSp + (size_t)i * sp_slot_bytes); }
-    int* sp_count(long i) const { return (int*)(sp_values(i) + sp_npts); }
-    mvsv_sample_hit* sp_hits(long i) const { return (mvsv_sample_hit*)(sp_count(i) + 1); }
-    // the display map of disp_roi of every frame (mvsv_stream_enable_display): a
-    // dense u8 map and (smin, smax) per slot, on the device and in one pinned host block
-    bool disp = false;
-    mvsv_rect disp_roi{};
+    int rawW = 0, rawH = 0;        // the camera frame; a slot's hL / hR hold one each
+    int cropW = 0, cropH = 0;      // the display ROI's size
+    double factor = 0;             // 0: the crop is the frame; else cv::resize of the crop
+    bool keep = false;             // the rectified pair comes back to the host too
+    DevArray<uint8_t> dRaw_all;    // [depth][2][rawH][rawW]
+    DevArray<int16_t> dMapXY;      // [2][cropH][mapStride] (sx, sy), ROI only
+    DevArray<uint16_t> dMapFrac;   // [2][cropH][mapStride] ay * 32 + ax
+    size_t mapStride = 0;          // entries per map row: cropW rounded up to 4, padding zero
+    DevArray<uint8_t> dCropL, dCropR;  // [depth][cropH][cropW] each, with a factor
+    Samplepoints sp;
+    ImageStage disp;
     double disp_alpha = 0, disp_beta = 255;
-    uint8_t* dDisp = nullptr;    // [depth][rh][rw]
-    int16_t* dDispMM = nullptr;  // [depth][2]
-    uint8_t* hDisp = nullptr;    // pinned: [depth] x (map, min, max), disp_slot_bytes each
-    size_t disp_px = 0, disp_slot_bytes = 0;
-    uint8_t* disp_map(long i) const { return hDisp + (size_t)i * disp_slot_bytes; }
-    int16_t* disp_minmax(long i) const { return (int16_t*)(disp_map(i) + ((disp_px + 1) & ~(size_t)1)); }
-    // the detection view of view_roi of every frame (mvsv_stream_enable_view): a
-    // dense BGR image and (smin, smax) per slot, on the device and in one pinned
-    // host block; view_spec's pointers are set per launch
-    bool view = false;
-    mvsv_rect view_roi{};
-    mvsv_view_spec view_spec{};
-    uint8_t* dView = nullptr;    // [depth][rh][rw][3]
-    int16_t* dViewMM = nullptr;  // [depth][2]
-    uint8_t* hView = nullptr;    // pinned: [depth] x (image, min, max), view_slot_bytes each
-    size_t view_bytes = 0, view_slot_bytes = 0;
-    uint8_t* view_img(long i) const { return hView + (size_t)i * view_slot_bytes; }
-    int16_t* view_minmax(long i) const { return (int16_t*)(view_img(i) + ((view_bytes + 1) & ~(size_t)1)); }
-    // the point cloud of cloud_roi of every frame (mvsv_stream_enable_cloud): the
-    // records stay in a device ring, (count, min, max) per slot come to the host
-    bool cloud = false;
-    mvsv_rect cloud_roi{};
-    float cloud_Q[16] = {};
-    int cloud_max = 0;
-    mvsv_cloud_point* dCloud = nullptr;  // [depth][cloud_max]
-    int* dCloudHdr = nullptr;            // [depth][3] (count, min, max)
-    int* hCloudHdr = nullptr;            // pinned, [depth][3]
-    hipStream_t cloud_copy = nullptr;    // front_cloud's copies: not behind the later frames' downloads
-    // the focus measure of every pushed pair (mvsv_stream_enable_sharpness): S4 of
-    // sharp_roi[0] of the left and sharp_roi[1] of the right pushed image per slot
-    bool sharp = false;
-    mvsv_rect sharp_roi[2] = {};
-    int64_t* dSharp = nullptr;  // [depth][2]
-    int64_t* hSharp = nullptr;  // pinned, [depth][2]
-    // colour frames (mvsv_stream_enable_bgr): a pushed BGR pair is staged per slot and
-    // prepared into the slot's dL / dR on the lane's stream
-    bool bgr = false;
-    int bgrW = 0, bgrH = 0, bgr_halve = 0, bgr_variant = 0;
-    size_t bgrRow = 0;            // bytes per staged row: 3 * bgrW rounded up to 4 (packed loads)
-    uint8_t* dBgr_all = nullptr;  // [depth][2][bgrH][bgrRow]
-};
+    ImageStage view;
+    mvsv_view_spec view_spec{};  // its means / values pointers are set per launch
+    Cloud cloud;
+    Sharpness sharp;
+    Bgr bgr;
 
-static void bgr_free(mvsv_stream* st)
-{
-    for (auto& s : st->slots) {
-        if (s.hBgr) (void)hipHostFree(s.hBgr);
-        s.hBgr = s.dBgr = nullptr;
-        s.is_bgr = false;
+    ~mvsv_stream()
+    {
+        for (size_t i = 1; i < lanes.size(); i++) mvsv_destroy(lanes[i]);
     }
-    if (st->dBgr_all) (void)hipFree(st->dBgr_all);
-    st->dBgr_all = nullptr;
-    st->bgr = false;
-}
-
-static void sharpness_free(mvsv_stream* st)
-{
-    if (st->dSharp) (void)hipFree(st->dSharp);
-    if (st->hSharp) (void)hipHostFree(st->hSharp);
-    st->dSharp = nullptr;
-    st->hSharp = nullptr;
-    st->sharp = false;
-}
-
-static void cloud_free(mvsv_stream* st)
-{
-    if (st->dCloud) (void)hipFree(st->dCloud);
-    if (st->dCloudHdr) (void)hipFree(st->dCloudHdr);
-    if (st->hCloudHdr) (void)hipHostFree(st->hCloudHdr);
-    if (st->cloud_copy) (void)hipStreamDestroy(st->cloud_copy);
-    st->cloud_copy = nullptr;
-    st->dCloud = nullptr;
-    st->dCloudHdr = nullptr;
-    st->hCloudHdr = nullptr;
-    st->cloud = false;
-}
-
-static void display_free(mvsv_stream* st)
-{
-    if (st->dDisp) (void)hipFree(st->dDisp);
-    if (st->dDispMM) (void)hipFree(st->dDispMM);
-    if (st->hDisp) (void)hipHostFree(st->hDisp);
-    st->dDisp = nullptr;
-    st->dDispMM = nullptr;
-    st->hDisp = nullptr;
-    st->disp = false;
-}
-
-static void view_free(mvsv_stream* st)
-{
-    if (st->dView) (void)hipFree(st->dView);
-    if (st->dViewMM) (void)hipFree(st->dViewMM);
-    if (st->hView) (void)hipHostFree(st->hView);
-    st->dView = nullptr;
-    st->dViewMM = nullptr;
-    st->hView = nullptr;
-    st->view = false;
-}
-
-static void samplepoints_free(mvsv_stream* st)
-{
-    if (st->dSpVal) (void)hipFree(st->dSpVal);
-    if (st->dSpCnt) (void)hipFree(st->dSpCnt);
-    if (st->dSpHits) (void)hipFree(st->dSpHits);
-    if (st->hSp) (void)hipHostFree(st->hSp);
-    st->dSpVal = nullptr;
-    st->dSpCnt = nullptr;
-    st->dSpHits = nullptr;
-    st->hSp = nullptr;
-    st->sp = false;
-}
+    PushGeom push_geom(PushKind kind) const { return ring_push_geom(kind, W, H, rawW, rawH, bgr.W, bgr.H); }
+};
 
 // what mvsv_stream_create_raw adds to a stream's creation
 struct RawSetup {
@@ -351,43 +329,6 @@ struct RawSetup {
     int cropW, cropH;
     bool resized;
 };
-
-static void stream_free(mvsv_stream* st)
-{
-    for (size_t i = 1; i < st->lanes.size(); i++) mvsv_destroy(st->lanes[i]);
-    for (auto& s : st->slots) {
-        if (s.hL) (void)hipHostFree(s.hL);
-        if (s.hR) (void)hipHostFree(s.hR);
-        if (s.hOut) (void)hipHostFree(s.hOut);
-        if (s.hMeans) (void)hipHostFree(s.hMeans);
-        if (s.hRectL) (void)hipHostFree(s.hRectL);
-        if (s.hRectR) (void)hipHostFree(s.hRectR);
-        for (hipEvent_t e : {s.uploaded, s.computed, s.done, s.released})
-            if (e) (void)hipEventDestroy(e);
-    }
-    for (hipEvent_t e : {st->producer_ev, st->fence_ev})
-        if (e) (void)hipEventDestroy(e);
-    if (st->dL_all) (void)hipFree(st->dL_all);
-    if (st->dR_all) (void)hipFree(st->dR_all);
-    if (st->dOut_all) (void)hipFree(st->dOut_all);
-    if (st->dMeans_all) (void)hipFree(st->dMeans_all);
-    if (st->dRaw_all) (void)hipFree(st->dRaw_all);
-    if (st->dMapXY) (void)hipFree(st->dMapXY);
-    if (st->dMapFrac) (void)hipFree(st->dMapFrac);
-    if (st->dCropL) (void)hipFree(st->dCropL);
-    if (st->dCropR) (void)hipFree(st->dCropR);
-    samplepoints_free(st);
-    display_free(st);
-    view_free(st);
-    cloud_free(st);
-    sharpness_free(st);
-    bgr_free(st);
-    if (st->rep) (void)hipHostFree(st->rep);
-    if (st->up) (void)hipStreamDestroy(st->up);
-    if (st->down) (void)hipStreamDestroy(st->down);
-    delete st->pool;
-    delete st;
-}
 
 // The display ROI of both map pairs in cv::convertMaps' form, on the device.
 static bool upload_maps(mvsv_stream* st, const mvsv_rectification* r)
@@ -409,8 +350,7 @@ static bool upload_maps(mvsv_stream* st, const mvsv_rectification* r)
                               xy.data() + k * side * 2, ms, frac.data() + k * side, ms) != MVSV_OK)
             return false;
     }
-    return hipMalloc((void**)&st->dMapXY, xy.size() * sizeof(int16_t)) == hipSuccess &&
-           hipMalloc((void**)&st->dMapFrac, frac.size() * sizeof(uint16_t)) == hipSuccess &&
+    return st->dMapXY.alloc(xy.size()) && st->dMapFrac.alloc(frac.size()) &&
            hipMemcpy(st->dMapXY, xy.data(), xy.size() * sizeof(int16_t), hipMemcpyHostToDevice) == hipSuccess &&
            hipMemcpy(st->dMapFrac, frac.data(), frac.size() * sizeof(uint16_t), hipMemcpyHostToDevice) ==
                hipSuccess;
@@ -424,9 +364,8 @@ static void stream_pool(mvsv_stream* st, size_t frame_bytes)
     if (const char* v = std::getenv("MVSV_STREAM_COPY_THREADS")) threads = std::max(1, std::min(16, std::atoi(v)));
     if (threads > 1) {
         try {
-            st->pool = new CopyPool(threads);
-        } catch (...) {
-            st->pool = nullptr;  // copies on the caller's thread
+            st->pool.reset(new CopyPool(threads));
+        } catch (...) {  // copies on the caller's thread
         }
     }
 }
@@ -445,7 +384,7 @@ static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p,
                      grid_roi->x1 - grid_roi->x0 < 9 || grid_roi->y1 - grid_roi->y0 < 9))
         return set_error(ctx, MVSV_E_INVALID_ARG, "grid ROI outside the image or smaller than 9x9");
     DeviceGuard dev_guard(ctx->device);
-    mvsv_stream* st = new (std::nothrow) mvsv_stream();
+    std::unique_ptr<mvsv_stream> st(new (std::nothrow) mvsv_stream());
     if (!st) return MVSV_E_OOM;
     st->ctx = ctx;
     st->lanes.push_back(ctx);
@@ -474,21 +413,14 @@ static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p,
         in_px = (size_t)st->rawW * st->rawH;
     }
     const size_t crop_px = (size_t)st->cropW * st->cropH;
-    bool ok = hipStreamCreateWithFlags(&st->up, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&st->down, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&st->producer_ev, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&st->fence_ev, hipEventDisableTiming) == hipSuccess;
+    bool ok = st->up.create() && st->down.create() && st->producer_ev.create() && st->fence_ev.create();
     st->slots.resize(depth);
     if (raw) {
-        ok = ok && hipMalloc((void**)&st->dRaw_all, 2 * in_px * depth) == hipSuccess && upload_maps(st, raw->rect);
-        if (raw->resized)
-            ok = ok && hipMalloc((void**)&st->dCropL, crop_px * depth) == hipSuccess &&
-                 hipMalloc((void**)&st->dCropR, crop_px * depth) == hipSuccess;
+        ok = ok && st->dRaw_all.alloc(2 * in_px * depth) && upload_maps(st.get(), raw->rect);
+        if (raw->resized) ok = ok && st->dCropL.alloc(crop_px * depth) && st->dCropR.alloc(crop_px * depth);
     }
-    ok = ok && hipMalloc((void**)&st->dL_all, px * depth) == hipSuccess &&
-         hipMalloc((void**)&st->dR_all, px * depth) == hipSuccess &&
-         hipMalloc((void**)&st->dOut_all, px * 2 * depth) == hipSuccess &&
-         hipMalloc((void**)&st->dMeans_all, 81 * sizeof(float) * depth) == hipSuccess;
+    ok = ok && st->dL_all.alloc(px * depth) && st->dR_all.alloc(px * depth) && st->dOut_all.alloc(px * depth) &&
+         st->dMeans_all.alloc((size_t)81 * depth);
     for (size_t i = 0; i < st->slots.size(); i++) {
         auto& s = st->slots[i];
         if (!ok) break;
@@ -497,26 +429,20 @@ static int stream_create(mvsv_ctx* ctx, int W, int H, const mvsv_sgbm_params* p,
         s.dOut = st->dOut_all + i * px;
         s.dMeans = st->dMeans_all + i * 81;
         if (raw) s.dRaw = st->dRaw_all + i * 2 * in_px;
-        if (st->keep)
-            ok = hipHostMalloc((void**)&s.hRectL, px, hipHostMallocDefault) == hipSuccess &&
-                 hipHostMalloc((void**)&s.hRectR, px, hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipHostMalloc((void**)&s.hL, in_px, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void**)&s.hR, in_px, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void**)&s.hOut, px * 2, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc((void**)&s.hMeans, 81 * sizeof(float), hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&s.computed, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&s.released, hipEventDisableTiming) == hipSuccess;
+        if (st->keep) ok = s.hRectL.alloc(px) && s.hRectR.alloc(px);
+        ok = ok && s.hL.alloc(in_px) && s.hR.alloc(in_px) && s.hOut.alloc(px) && s.hMeans.alloc(81) &&
+             s.uploaded.create() && s.computed.create() && s.done.create() && s.released.create();
     }
-    ok = ok && alloc_report(ctx, depth, &st->rep, &st->rep_dev) == MVSV_OK;
-    if (ok) stream_pool(st, std::max(px, in_px) * 2);
+    int* rep = nullptr;
+    ok = ok && alloc_report(ctx, depth, &rep, &st->rep_dev) == MVSV_OK;
+    st->rep = PinnedArray<int>(rep);
+    if (ok) stream_pool(st.get(), std::max(px, in_px) * 2);
     if (!ok) {
         (void)hipGetLastError();
-        stream_free(st);
+        st.reset();
         return set_error(ctx, MVSV_E_OOM, "stream slot allocation failed");
     }
-    *out = st;
+    *out = st.release();
     return MVSV_OK;
 }
 
@@ -613,7 +539,9 @@ static int stream_rectify(mvsv_stream* st, mvsv_ctx* ctx, long i0, int n)
 // dL / dR on the lane's stream, one launch per side and stretch of such slots.
 static int stream_prepare(mvsv_stream* st, mvsv_ctx* ctx, long i0, int n)
 {
-    const size_t px = (size_t)st->W * st->H, side = (size_t)st->bgrH * st->bgrRow;
+    const size_t px = (size_t)st->W * st->H;
+    const PushGeom g = st->push_geom(kPushBgr);
+    const Bgr& b = st->bgr;
     for (int k = 0; k < n;) {
         if (!st->slots[i0 + k].is_bgr) {
             k++;
@@ -622,11 +550,12 @@ static int stream_prepare(mvsv_stream* st, mvsv_ctx* ctx, long i0, int n)
         int m = 1;
         while (k + m < n && st->slots[i0 + k + m].is_bgr) m++;
         auto& s = st->slots[i0 + k];
+        const uint8_t* pair = b.dev + (size_t)(i0 + k) * g.frame;
         int rc;
-        if ((rc = prepare_gray_device(ctx, m, s.dBgr, st->bgrRow, 2 * side, st->bgrW, st->bgrH, st->bgr_halve,
-                                      st->bgr_variant, s.dL, st->W, px)) ||
-            (rc = prepare_gray_device(ctx, m, s.dBgr + side, st->bgrRow, 2 * side, st->bgrW, st->bgrH, st->bgr_halve,
-                                      st->bgr_variant, s.dR, st->W, px)))
+        if ((rc = prepare_gray_device(ctx, m, pair, g.stride, g.frame, b.W, b.H, b.halve, b.variant, s.dL, st->W,
+                                      px)) ||
+            (rc = prepare_gray_device(ctx, m, pair + g.right, g.stride, g.frame, b.W, b.H, b.halve, b.variant, s.dR,
+                                      st->W, px)))
             return rc;
         k += m;
     }
@@ -663,62 +592,59 @@ static int stream_launch(mvsv_stream* st)
         first.run_len = n;
         int* prev_target = ctx->report_target;
         ctx->report_target = st->rep_dev + i0;
-        int status = st->raw ? stream_rectify(st, ctx, i0, n) : st->bgr ? stream_prepare(st, ctx, i0, n) : MVSV_OK;
+        int status = st->raw ? stream_rectify(st, ctx, i0, n) : st->bgr.on ? stream_prepare(st, ctx, i0, n) : MVSV_OK;
         if (status == MVSV_OK)
             status = st->matcher == MVSV_MATCHER_BM
                          ? bm_device(ctx, n, first.dL, W, px, first.dR, W, px, W, H, st->bm_eff, first.dOut, W, px)
                          : sgbm_device(ctx, n, first.dL, W, px, first.dR, W, px, W, H, st->eff, first.dOut, W, px);
         ctx->report_target = prev_target;
+        // the run's maps at a stage's ROI
+        auto at = [&](const mvsv_rect& q) { return first.dOut + (size_t)q.y0 * W + q.x0; };
         if (status == MVSV_OK && st->grid) {
             const mvsv_rect& q = st->roi;
-            status = mean_grid_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, q.x1 - q.x0,
-                                      q.y1 - q.y0, first.dMeans);
+            status = mean_grid_device(ctx, n, at(q), W, px, q.x1 - q.x0, q.y1 - q.y0, first.dMeans);
         }
-        if (status == MVSV_OK && st->sp && st->sp_npts > 0) {
-            const mvsv_rect& q = st->sp_roi;
+        const Samplepoints& sp = st->sp;
+        if (status == MVSV_OK && sp.on && sp.npts > 0) {
+            const mvsv_rect& q = sp.roi;
             const int rw = q.x1 - q.x0, rh = q.y1 - q.y0;
-            float* vals = st->dSpVal + (size_t)i0 * st->sp_npts;
-            status = sample_grid_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, rw, rh, st->sp_radius,
-                                        vals);
+            status = sample_grid_device(ctx, n, at(q), W, px, rw, rh, sp.radius, sp.dev_values(i0));
             if (status == MVSV_OK)
-                status = sample_detect_device(ctx, n, vals, rw, rh, st->sp_Q, st->sp_first, st->sp_second,
-                                              st->sp_max, st->dSpCnt + i0, st->dSpHits + (size_t)i0 * st->sp_max);
+                status = sample_detect_device(ctx, n, sp.dev_values(i0), rw, rh, sp.Q, sp.first, sp.second, sp.max_hits,
+                                              sp.dCnt + i0, sp.dev_hits(i0));
         }
-        if (status == MVSV_OK && st->disp) {
-            const mvsv_rect& q = st->disp_roi;
-            const int rw = q.x1 - q.x0, rh = q.y1 - q.y0;
-            status = normalize_minmax_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, rw, rh,
-                                             st->disp_alpha, st->disp_beta, st->dDisp + (size_t)i0 * st->disp_px, rw,
-                                             st->disp_px, st->dDispMM + 2 * i0);
+        if (status == MVSV_OK && st->disp.on) {
+            const ImageStage& g = st->disp;
+            status = normalize_minmax_device(ctx, n, at(g.roi), W, px, g.width(), g.height(), st->disp_alpha,
+                                             st->disp_beta, g.dev_image(i0), g.row_bytes, g.bytes, g.dev_minmax(i0));
         }
-        if (status == MVSV_OK && st->view) {  // after the mean grid and the lattice: it reads both
-            const mvsv_rect& q = st->view_roi;
-            const int rw = q.x1 - q.x0, rh = q.y1 - q.y0;
+        if (status == MVSV_OK && st->view.on) {  // after the mean grid and the lattice: it reads both
+            const ImageStage& g = st->view;
             mvsv_view_spec spec = st->view_spec;
             spec.means = first.dMeans;
-            spec.values = st->dSpVal ? st->dSpVal + (size_t)i0 * st->sp_npts : nullptr;
-            spec.point_first = st->sp_first;
-            spec.point_second = st->sp_second;
-            status = view_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, rw, rh, spec,
-                                 st->dView + (size_t)i0 * st->view_bytes, 3 * (size_t)rw, st->view_bytes,
-                                 st->dViewMM + 2 * i0);
+            spec.values = sp.dev_values(i0);
+            spec.point_first = sp.first;
+            spec.point_second = sp.second;
+            status = view_device(ctx, n, at(g.roi), W, px, g.width(), g.height(), spec, g.dev_image(i0), g.row_bytes,
+                                 g.bytes, g.dev_minmax(i0));
         }
-        if (status == MVSV_OK && st->cloud) {
-            const mvsv_rect& q = st->cloud_roi;
-            status = point_cloud_device(ctx, n, first.dOut + (size_t)q.y0 * W + q.x0, W, px, q.x1 - q.x0, q.y1 - q.y0,
-                                        st->cloud_Q, st->dCloud + (size_t)i0 * st->cloud_max, st->cloud_max,
-                                        st->dCloudHdr + 3 * i0, 3, st->dCloudHdr + 3 * i0 + 1, 3);
+        if (status == MVSV_OK && st->cloud.on) {
+            const Cloud& c = st->cloud;
+            const mvsv_rect& q = c.roi;
+            status = point_cloud_device(ctx, n, at(q), W, px, q.x1 - q.x0, q.y1 - q.y0, c.Q, c.dev_records(i0),
+                                        c.max_points, c.dHdr + 3 * i0, 3, c.dHdr + 3 * i0 + 1, 3);
         }
-        if (status == MVSV_OK && st->sharp) {
+        if (status == MVSV_OK && st->sharp.on) {
             // the pushed pair: a raw slot holds it as [2][rawH][rawW]
             const int iw = st->raw ? st->rawW : W, ih = st->raw ? st->rawH : H;
             const size_t ipx = (size_t)iw * ih;
             const uint8_t* pl = st->raw ? first.dRaw : first.dL;
             const uint8_t* pr = st->raw ? first.dRaw + ipx : first.dR;
             const size_t ifs = st->raw ? 2 * ipx : ipx;
-            status = sharpness_device(ctx, n, pl, iw, ifs, iw, ih, st->sharp_roi[0], st->dSharp + 2 * i0, 2);
+            int64_t* sums = st->sharp.dSum + 2 * i0;
+            status = sharpness_device(ctx, n, pl, iw, ifs, iw, ih, st->sharp.roi[0], sums, 2);
             if (status == MVSV_OK)
-                status = sharpness_device(ctx, n, pr, iw, ifs, iw, ih, st->sharp_roi[1], st->dSharp + 2 * i0 + 1, 2);
+                status = sharpness_device(ctx, n, pr, iw, ifs, iw, ih, st->sharp.roi[1], sums + 1, 2);
         }
         if (status != MVSV_OK && ctx != st->ctx) st->ctx->err = ctx->err;  // reported by pop
         st->runs++;
@@ -728,64 +654,37 @@ static int stream_launch(mvsv_stream* st)
             if (ctx != st->ctx) st->ctx->err = ctx->err;
             return rc;
         }
-        for (int k = 0; k < n; k++) {
-            auto& s = st->slots[i0 + k];
+        // what the host reads of every frame, in this order on the download stream
+        auto d2h = [&](void* dst, const void* src, size_t bytes) {
+            return check_hip(st->ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st->down), "stream D2H");
+        };
+        // an image stage: the image unless set_host_outputs keeps it on the device, and its (min, max)
+        auto d2h_image = [&](const ImageStage& g, int host_bit, long i) {
+            int e = MVSV_OK;
+            if (!g.on) return e;
+            if ((st->host_mask & host_bit) && (e = d2h(g.image(i), g.dev_image(i), g.bytes))) return e;
+            return d2h(g.minmax(i), g.dev_minmax(i), 2 * sizeof(int16_t));
+        };
+        for (long i = i0; i < i0 + n; i++) {
+            auto& s = st->slots[i];
             s.status = status;
-            mvsv_ctx* c = st->ctx;
-            if ((st->host_mask & MVSV_HOST_MAP) &&
-                (rc = check_hip(c, hipMemcpyAsync(s.hOut, s.dOut, px * 2, hipMemcpyDeviceToHost, st->down),
-                                "stream D2H")))
-                return rc;
-            if (st->grid &&
-                (rc = check_hip(c, hipMemcpyAsync(s.hMeans, s.dMeans, 81 * sizeof(float),
-                                                  hipMemcpyDeviceToHost, st->down), "stream D2H")))
-                return rc;
+            if ((st->host_mask & MVSV_HOST_MAP) && (rc = d2h(s.hOut, s.dOut, px * 2))) return rc;
+            if (st->grid && (rc = d2h(s.hMeans, s.dMeans, 81 * sizeof(float)))) return rc;
             if (st->keep && (st->host_mask & MVSV_HOST_RECTIFIED) &&
-                ((rc = check_hip(c, hipMemcpyAsync(s.hRectL, s.dL, px, hipMemcpyDeviceToHost, st->down),
-                                 "stream D2H")) ||
-                 (rc = check_hip(c, hipMemcpyAsync(s.hRectR, s.dR, px, hipMemcpyDeviceToHost, st->down),
-                                 "stream D2H"))))
+                ((rc = d2h(s.hRectL, s.dL, px)) || (rc = d2h(s.hRectR, s.dR, px))))
                 return rc;
-            if (st->sp && st->sp_npts > 0) {
-                // values, count and hit records are adjacent in the pinned slot
-                const long i = i0 + k;
-                if ((rc = check_hip(c, hipMemcpyAsync(st->sp_values(i), st->dSpVal + (size_t)i * st->sp_npts,
-                                                      (size_t)st->sp_npts * sizeof(float), hipMemcpyDeviceToHost,
-                                                      st->down), "stream D2H")) ||
-                    (rc = check_hip(c, hipMemcpyAsync(st->sp_count(i), st->dSpCnt + i, sizeof(int),
-                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")) ||
-                    (rc = check_hip(c, hipMemcpyAsync(st->sp_hits(i), st->dSpHits + (size_t)i * st->sp_max,
-                                                      (size_t)st->sp_max * sizeof(mvsv_sample_hit),
-                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")))
-                    return rc;
-            }
-            if (st->disp) {
-                const long i = i0 + k;
-                if (((st->host_mask & MVSV_HOST_DISPLAY) &&
-                     (rc = check_hip(c, hipMemcpyAsync(st->disp_map(i), st->dDisp + (size_t)i * st->disp_px, st->disp_px,
-                                                       hipMemcpyDeviceToHost, st->down), "stream D2H"))) ||
-                    (rc = check_hip(c, hipMemcpyAsync(st->disp_minmax(i), st->dDispMM + 2 * i, 2 * sizeof(int16_t),
-                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")))
-                    return rc;
-            }
-            if (st->view) {
-                const long i = i0 + k;
-                if (((st->host_mask & MVSV_HOST_VIEW) &&
-                     (rc = check_hip(c, hipMemcpyAsync(st->view_img(i), st->dView + (size_t)i * st->view_bytes,
-                                                       st->view_bytes, hipMemcpyDeviceToHost, st->down), "stream D2H"))) ||
-                    (rc = check_hip(c, hipMemcpyAsync(st->view_minmax(i), st->dViewMM + 2 * i, 2 * sizeof(int16_t),
-                                                      hipMemcpyDeviceToHost, st->down), "stream D2H")))
-                    return rc;
-            }
-            if (st->cloud &&  // the header only: the records wait on the device for front_cloud
-                (rc = check_hip(c, hipMemcpyAsync(st->hCloudHdr + 3 * (i0 + k), st->dCloudHdr + 3 * (i0 + k),
-                                                  3 * sizeof(int), hipMemcpyDeviceToHost, st->down), "stream D2H")))
+            if (sp.on && sp.npts > 0 &&  // values, count and hit records are adjacent in the pinned slot
+                ((rc = d2h(sp.values(i), sp.dev_values(i), (size_t)sp.npts * sizeof(float))) ||
+                 (rc = d2h(sp.count(i), sp.dCnt + i, sizeof(int))) ||
+                 (rc = d2h(sp.hits(i), sp.dev_hits(i), (size_t)sp.max_hits * sizeof(mvsv_sample_hit)))))
                 return rc;
-            if (st->sharp &&
-                (rc = check_hip(c, hipMemcpyAsync(st->hSharp + 2 * (i0 + k), st->dSharp + 2 * (i0 + k),
-                                                  2 * sizeof(int64_t), hipMemcpyDeviceToHost, st->down), "stream D2H")))
+            if ((rc = d2h_image(st->disp, MVSV_HOST_DISPLAY, i)) || (rc = d2h_image(st->view, MVSV_HOST_VIEW, i)))
                 return rc;
-            if ((rc = check_hip(c, hipEventRecord(s.done, st->down), "stream event"))) return rc;
+            // the cloud's header only: the records wait on the device for front_cloud
+            if (st->cloud.on && (rc = d2h(st->cloud.hHdr + 3 * i, st->cloud.dHdr + 3 * i, 3 * sizeof(int)))) return rc;
+            if (st->sharp.on && (rc = d2h(st->sharp.hSum + 2 * i, st->sharp.dSum + 2 * i, 2 * sizeof(int64_t))))
+                return rc;
+            if ((rc = check_hip(st->ctx, hipEventRecord(s.done, st->down), "stream event"))) return rc;
         }
         st->launched += n;
     }
@@ -804,29 +703,6 @@ int mvsv_stream_set_batch(mvsv_stream* st, int batch)
     return MVSV_OK;
 }
 
-// The stream's own lanes follow the caller context's kernel options.
-static void copy_options(mvsv_ctx* d, const mvsv_ctx* s)
-{
-    d->spin_limit = s->spin_limit;
-    d->path16 = s->path16;
-    d->cost2 = s->cost2;
-    d->cost_fixed_pp = s->cost_fixed_pp;
-    d->cost_ty = s->cost_ty;
-    d->tri = s->tri;
-    d->path_sched = s->path_sched;
-    d->strip_waves = s->strip_waves;
-    d->cost_res = s->cost_res;
-    d->lines_aux = s->lines_aux;
-    d->strip_tickets = s->strip_tickets;
-    d->bm2 = s->bm2;
-    d->bm_ty = s->bm_ty;
-    d->bitslice = s->bitslice;
-    d->bs_groups = s->bs_groups;
-    d->bs_serial = s->bs_serial;
-    d->cost_xcd = s->cost_xcd;
-    d->bs_fuse = s->bs_fuse;
-}
-
 int mvsv_stream_set_inflight(mvsv_stream* st, int n)
 {
     if (!st) return MVSV_E_INVALID_ARG;
@@ -839,7 +715,7 @@ int mvsv_stream_set_inflight(mvsv_stream* st, int n)
     while ((int)st->lanes.size() < n) {
         mvsv_ctx* c = nullptr;
         if ((rc = mvsv_create(&c, ctx->device))) return set_error(ctx, rc, "stream lane context creation failed");
-        copy_options(c, ctx);
+        c->opt = ctx->opt;  // the stream's own lanes follow the caller context's kernel options
         st->lanes.push_back(c);
         if (st->fenced && (rc = check_hip(ctx, hipStreamWaitEvent(c->stream, st->fence_ev, 0), "stream wait")))
             return rc;
@@ -884,154 +760,170 @@ int mvsv_stream_set_bm_params(mvsv_stream* st, const mvsv_bm_params* p)
 
 int mvsv_stream_pending(const mvsv_stream* st) { return st ? (int)(st->head - st->tail) : 0; }
 
-int mvsv_stream_push(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs)
+// ---- steps the entry points share ----
+
+// Stages and outputs change only while the ring is empty: nothing in flight uses
+// the buffers then.  subject: "the display changes", "sample points change", ...
+static int idle_check(mvsv_stream* st, const char* subject)
+{
+    if (st->head == st->tail) return MVSV_OK;
+    return set_error(st->ctx, MVSV_E_INVALID_ARG, std::string(subject) + " only while no frame is pending");
+}
+
+// *q = roi, or the whole iw x ih image without one; false unless it is inside the image and not empty
+static bool roi_or_whole(const mvsv_rect* roi, int iw, int ih, mvsv_rect* q)
+{
+    *q = roi ? *roi : mvsv_rect{0, 0, iw, ih};
+    return q->x0 >= 0 && q->y0 >= 0 && q->x1 <= iw && q->y1 <= ih && q->x1 > q->x0 && q->y1 > q->y0;
+}
+
+static bool same_rect(const mvsv_rect& a, const mvsv_rect& b)
+{
+    return a.x0 == b.x0 && a.y0 == b.y0 && a.x1 == b.x1 && a.y1 == b.y1;
+}
+
+template <class Stage>
+static int stage_disable(mvsv_stream* st, Stage mvsv_stream::*stage, const char* subject)
 {
     if (!st) return MVSV_E_INVALID_ARG;
-    mvsv_ctx* ctx = st->ctx;
-    if (st->raw) return set_error(ctx, MVSV_E_INVALID_ARG, "raw stream: push raw pairs with mvsv_stream_push_raw");
-    if (!L || !R || ls < (size_t)st->W || rs < (size_t)st->W)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "null frame or stride smaller than width");
-    if (ring_full(st->head, st->tail, (long)st->slots.size()))
-        return set_error(ctx, MVSV_E_INVALID_ARG, "stream full: pop a frame first");
-    DeviceGuard dev_guard(ctx->device);
-    auto& s = st->slots[st->head % st->slots.size()];
-    s.is_bgr = false;
-    const int W = st->W, H = st->H;
-    // the slot's previous frame was popped, so its copies are complete
-    auto copy_in = [&](int part, int parts) {
-        copy_rows(s.hL, W, L, ls, W, H, part, parts);
-        copy_rows(s.hR, W, R, rs, W, H, part, parts);
-    };
-    if (st->pool)
-        st->pool->run(copy_in);
-    else
-        copy_in(0, 1);
-    const size_t px = (size_t)W * H;
-    int rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(s.dL, s.hL, px, hipMemcpyHostToDevice, st->up), "stream H2D")) ||
-        (rc = check_hip(ctx, hipMemcpyAsync(s.dR, s.hR, px, hipMemcpyHostToDevice, st->up), "stream H2D")) ||
-        (rc = check_hip(ctx, hipEventRecord(s.uploaded, st->up), "stream event")))
-        return rc;
-    st->head++;
-    // a full group, or a group that would otherwise wrap past the ring's end
-    if (ring_launch_after_push(st->head, st->launched, st->batch, (long)st->slots.size()))
-        return stream_launch(st);
+    if (int rc = idle_check(st, subject)) return rc;
+    DeviceGuard dev_guard(st->ctx->device);
+    st->*stage = Stage{};
     return MVSV_OK;
 }
 
-int mvsv_stream_disable_bgr(mvsv_stream* st)
+// a stage's allocation failed: the stage is off again
+template <class Stage>
+static int stage_oom(mvsv_stream* st, Stage* stage, const char* msg)
 {
-    if (!st) return MVSV_E_INVALID_ARG;
-    if (st->head != st->tail)
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "colour input changes only while no frame is pending");
-    DeviceGuard dev_guard(st->ctx->device);
-    bgr_free(st);  // every frame was popped: nothing in flight uses the buffers
+    (void)hipGetLastError();
+    *stage = Stage{};
+    return set_error(st->ctx, MVSV_E_OOM, msg);
+}
+
+// fn(part, parts) over the copy pool, or on the caller's thread without one
+template <class Fn>
+static void run_copy(mvsv_stream* st, const Fn& fn)
+{
+    if (st->pool)
+        st->pool->run(fn);
+    else
+        fn(0, 1);
+}
+
+// ---- pushes ----
+
+// The stream takes frames of this kind: from the host (mvsv_stream_push, _raw, _bgr)
+// or, with device, from device memory (the same names + _device).
+static int push_kind_check(mvsv_stream* st, PushKind kind, bool device)
+{
+    const char* suffix = device ? "_device" : "";
+    if (kind == kPushRaw && !st->raw)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG,
+                         std::string("stream of rectified pairs: push them with mvsv_stream_push") + suffix);
+    if (kind != kPushRaw && st->raw)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG,
+                         std::string("raw stream: push raw pairs with mvsv_stream_push_raw") + suffix);
+    if (kind == kPushBgr && !st->bgr.on)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "colour input is not enabled on this stream");
     return MVSV_OK;
 }
+
+// Where a frame of this kind lands in slot i: pinned staging (host pushes) and device.
+struct PushEnds {
+    uint8_t *hl, *hr, *dl, *dr;
+};
+static PushEnds push_ends(mvsv_stream* st, PushKind kind, const PushGeom& g, long i)
+{
+    auto& s = st->slots[i];
+    if (kind == kPushRectified) return {s.hL, s.hR, s.dL, s.dR};
+    if (kind == kPushRaw) return {s.hL, s.hR, s.dRaw, s.dRaw + g.right};
+    uint8_t *h = st->bgr.host + (size_t)i * g.frame, *d = st->bgr.dev + (size_t)i * g.frame;
+    return {h, h + g.right, d, d + g.right};
+}
+
+// One frame from host memory: rows through the copy pool into the slot's pinned
+// staging, H2D on the upload stream, then the push's bookkeeping.
+static int stream_push_host(mvsv_stream* st, PushKind kind, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs)
+{
+    static const char* const bad_frame[] = {"null frame or stride smaller than width",
+                                            "null frame or stride smaller than the raw width",
+                                            "null frame or stride smaller than three times the width"};
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    int rc;
+    if ((rc = push_kind_check(st, kind, false))) return rc;
+    const PushGeom g = st->push_geom(kind);
+    if (!L || !R || ls < g.row || rs < g.row) return set_error(ctx, MVSV_E_INVALID_ARG, bad_frame[kind]);
+    const long depth = (long)st->slots.size();
+    if (ring_full(st->head, st->tail, depth))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "stream full: pop a frame first");
+    DeviceGuard dev_guard(ctx->device);
+    auto& s = st->slots[st->head % depth];
+    const PushEnds e = push_ends(st, kind, g, st->head % depth);
+    // the slot's previous frame was popped, so its copies and what read its device buffers are complete
+    run_copy(st, [&](int part, int parts) {
+        copy_rows(e.hl, g.stride, L, ls, g.row, g.rows, part, parts);
+        copy_rows(e.hr, g.stride, R, rs, g.row, g.rows, part, parts);
+    });
+    const size_t side = g.stride * g.rows;
+    const bool one = e.hr == e.hl + side && e.dr == e.dl + side;  // the pair is one block at both ends
+    auto h2d = [&](void* dst, const void* src, size_t bytes) {
+        return check_hip(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st->up), "stream H2D");
+    };
+    if ((rc = h2d(e.dl, e.hl, one ? 2 * side : side)) || (!one && (rc = h2d(e.dr, e.hr, side))) ||
+        (rc = check_hip(ctx, hipEventRecord(s.uploaded, st->up), "stream event")))
+        return rc;
+    if (kind != kPushRaw) s.is_bgr = kind == kPushBgr;
+    st->head++;
+    // a full group, or a group that would otherwise wrap past the ring's end
+    if (ring_launch_after_push(st->head, st->launched, st->batch, depth)) return stream_launch(st);
+    return MVSV_OK;
+}
+
+int mvsv_stream_push(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs)
+{
+    return stream_push_host(st, kPushRectified, L, ls, R, rs);
+}
+
+int mvsv_stream_push_raw(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs)
+{
+    return stream_push_host(st, kPushRaw, L, ls, R, rs);
+}
+
+int mvsv_stream_push_bgr(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs)
+{
+    return stream_push_host(st, kPushBgr, L, ls, R, rs);
+}
+
+int mvsv_stream_disable_bgr(mvsv_stream* st) { return stage_disable(st, &mvsv_stream::bgr, "colour input changes"); }
 
 int mvsv_stream_enable_bgr(mvsv_stream* st, int sw, int sh, int halve, int variant)
 {
     if (!st) return MVSV_E_INVALID_ARG;
     mvsv_ctx* ctx = st->ctx;
     if (st->raw) return set_error(ctx, MVSV_E_INVALID_ARG, "colour input is for streams of rectified pairs");
-    if (st->head != st->tail)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "colour input changes only while no frame is pending");
+    if (int rc = idle_check(st, "colour input changes")) return rc;
     int dw, dh;
     if (prepare_size(sw, sh, halve, &dw, &dh) || dw != st->W || dh != st->H)
         return set_error(ctx, MVSV_E_INVALID_ARG, "mvsv_prepare_size of the colour frame is not the stream's size");
     if (variant != MVSV_GRAY_Q14 && variant != MVSV_GRAY_Q15)
         return set_error(ctx, MVSV_E_INVALID_ARG, "unknown grey variant");
     DeviceGuard dev_guard(ctx->device);
-    bgr_free(st);
-    st->bgrW = sw;
-    st->bgrH = sh;
-    st->bgr_halve = halve;
-    st->bgr_variant = variant;
-    st->bgrRow = (3 * (size_t)sw + 3) & ~(size_t)3;
-    const size_t pair = 2 * (size_t)sh * st->bgrRow;
-    bool ok = hipMalloc((void**)&st->dBgr_all, pair * st->slots.size()) == hipSuccess;
-    for (size_t i = 0; ok && i < st->slots.size(); i++) {
-        st->slots[i].dBgr = st->dBgr_all + i * pair;
-        ok = hipHostMalloc((void**)&st->slots[i].hBgr, pair, hipHostMallocDefault) == hipSuccess;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        bgr_free(st);
-        return set_error(ctx, MVSV_E_OOM, "colour staging allocation failed");
-    }
+    Bgr& b = st->bgr;
+    b = {};
+    b.W = sw;
+    b.H = sh;
+    b.halve = halve;
+    b.variant = variant;
+    const size_t pair = st->push_geom(kPushBgr).frame;
+    if (!b.dev.alloc(pair * st->slots.size()) || !b.host.alloc(pair * st->slots.size()))
+        return stage_oom(st, &b, "colour staging allocation failed");
     stream_pool(st, pair);
-    st->bgr = true;
+    b.on = true;
     return MVSV_OK;
 }
 
-int mvsv_stream_push_bgr(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs)
-{
-    if (!st) return MVSV_E_INVALID_ARG;
-    mvsv_ctx* ctx = st->ctx;
-    if (st->raw) return set_error(ctx, MVSV_E_INVALID_ARG, "raw stream: push raw pairs with mvsv_stream_push_raw");
-    if (!st->bgr) return set_error(ctx, MVSV_E_INVALID_ARG, "colour input is not enabled on this stream");
-    const size_t row = 3 * (size_t)st->bgrW;
-    if (!L || !R || ls < row || rs < row)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "null frame or stride smaller than three times the width");
-    if (ring_full(st->head, st->tail, (long)st->slots.size()))
-        return set_error(ctx, MVSV_E_INVALID_ARG, "stream full: pop a frame first");
-    DeviceGuard dev_guard(ctx->device);
-    auto& s = st->slots[st->head % st->slots.size()];
-    const int H = st->bgrH;
-    const size_t side = (size_t)H * st->bgrRow;
-    // the slot's previous frame was popped, so its copies and its preparation are complete
-    auto copy_in = [&](int part, int parts) {
-        copy_rows(s.hBgr, st->bgrRow, L, ls, row, H, part, parts);
-        copy_rows(s.hBgr + side, st->bgrRow, R, rs, row, H, part, parts);
-    };
-    if (st->pool)
-        st->pool->run(copy_in);
-    else
-        copy_in(0, 1);
-    int rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(s.dBgr, s.hBgr, 2 * side, hipMemcpyHostToDevice, st->up), "stream H2D")) ||
-        (rc = check_hip(ctx, hipEventRecord(s.uploaded, st->up), "stream event")))
-        return rc;
-    s.is_bgr = true;
-    st->head++;
-    if (ring_launch_after_push(st->head, st->launched, st->batch, (long)st->slots.size()))
-        return stream_launch(st);
-    return MVSV_OK;
-}
-
-int mvsv_stream_push_raw(mvsv_stream* st, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs)
-{
-    if (!st) return MVSV_E_INVALID_ARG;
-    mvsv_ctx* ctx = st->ctx;
-    if (!st->raw)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "stream of rectified pairs: push them with mvsv_stream_push");
-    const int W = st->rawW, H = st->rawH;
-    if (!L || !R || ls < (size_t)W || rs < (size_t)W)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "null frame or stride smaller than the raw width");
-    if (ring_full(st->head, st->tail, (long)st->slots.size()))
-        return set_error(ctx, MVSV_E_INVALID_ARG, "stream full: pop a frame first");
-    DeviceGuard dev_guard(ctx->device);
-    auto& s = st->slots[st->head % st->slots.size()];
-    // the slot's previous frame was popped, so its copies and its rectification are complete
-    auto copy_in = [&](int part, int parts) {
-        copy_rows(s.hL, W, L, ls, W, H, part, parts);
-        copy_rows(s.hR, W, R, rs, W, H, part, parts);
-    };
-    if (st->pool)
-        st->pool->run(copy_in);
-    else
-        copy_in(0, 1);
-    const size_t px = (size_t)W * H;
-    int rc;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(s.dRaw, s.hL, px, hipMemcpyHostToDevice, st->up), "stream H2D")) ||
-        (rc = check_hip(ctx, hipMemcpyAsync(s.dRaw + px, s.hR, px, hipMemcpyHostToDevice, st->up), "stream H2D")) ||
-        (rc = check_hip(ctx, hipEventRecord(s.uploaded, st->up), "stream event")))
-        return rc;
-    st->head++;
-    if (ring_launch_after_push(st->head, st->launched, st->batch, (long)st->slots.size()))
-        return stream_launch(st);
-    return MVSV_OK;
-}
 
 // Wait for the oldest pending frame and release its slot: its status, and the
 // slot whose pinned map / means hold the result (valid until the slot's reuse).
@@ -1089,19 +981,14 @@ int mvsv_stream_pop_pair(mvsv_stream* st, int16_t* out, size_t os, float* means,
     int rc = stream_pop_slot(st, &sp);
     if (rc) return rc;
     const auto& s = *sp;
-    if (out || rl || rr) {
-        auto copy_out = [&](int part, int parts) {
+    if (out || rl || rr)
+        run_copy(st, [&](int part, int parts) {
             if (out)
-                copy_rows((uint8_t*)out, os * 2, (const uint8_t*)s.hOut, (size_t)st->W * 2, (size_t)st->W * 2,
+                copy_rows((uint8_t*)out, os * 2, (const uint8_t*)s.hOut.get(), (size_t)st->W * 2, (size_t)st->W * 2,
                           st->H, part, parts);
             if (rl) copy_rows(rl, rls, s.hRectL, (size_t)st->W, (size_t)st->W, st->H, part, parts);
             if (rr) copy_rows(rr, rrs, s.hRectR, (size_t)st->W, (size_t)st->W, st->H, part, parts);
-        };
-        if (st->pool)
-            st->pool->run(copy_out);
-        else
-            copy_out(0, 1);
-    }
+        });
     stream_means(st, s, means);
     return MVSV_OK;
 }
@@ -1126,20 +1013,54 @@ int mvsv_stream_pop_view(mvsv_stream* st, const int16_t** map, float* means)
     return MVSV_OK;
 }
 
+// ---- the oldest pending frame (front_*) ----
+
+// what is asked for is switched on, and a frame is pending
+static int front_check(mvsv_stream* st, bool enabled, const char* not_enabled)
+{
+    if (!enabled) return set_error(st->ctx, MVSV_E_INVALID_ARG, not_enabled);
+    if (st->head == st->tail) return set_error(st->ctx, MVSV_E_INVALID_ARG, "stream empty");
+    return MVSV_OK;
+}
+
+// Wait for the oldest pending frame and report its status; its slot index in *idx.
+// The frame stays pending.
+static int front_wait(mvsv_stream* st, long* idx)
+{
+    mvsv_ctx* ctx = st->ctx;
+    *idx = st->tail % (long)st->slots.size();
+    auto& s = st->slots[*idx];
+    int rc;
+    if (st->tail >= st->launched && (rc = stream_launch(st))) return rc;  // partial group
+    if ((rc = check_hip(ctx, hipEventSynchronize(s.done), "stream sync"))) return rc;
+    if (s.status) return s.status;
+    // the report word is left for pop to read and clear
+    if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[*idx], __ATOMIC_ACQUIRE) != 0))
+        return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
+    return MVSV_OK;
+}
+
+static int front_slot(mvsv_stream* st, bool enabled, const char* not_enabled, long* idx)
+{
+    if (int rc = front_check(st, enabled, not_enabled)) return rc;
+    return front_wait(st, idx);
+}
+
+// ---- sample points ----
+
 static bool view_uses_samplepoints(const mvsv_stream* st)
 {
-    return st->view && (st->view_spec.layers & MVSV_VIEW_FOUND_POINTS);
+    return st->view.on && (st->view_spec.layers & MVSV_VIEW_FOUND_POINTS);
 }
 
 int mvsv_stream_disable_samplepoints(mvsv_stream* st)
 {
     if (!st) return MVSV_E_INVALID_ARG;
-    if (st->head != st->tail)
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "sample points change only while no frame is pending");
+    if (int rc = idle_check(st, "sample points change")) return rc;
     if (view_uses_samplepoints(st))
         return set_error(st->ctx, MVSV_E_INVALID_ARG, "the view draws the found points: disable the view first");
     DeviceGuard dev_guard(st->ctx->device);
-    samplepoints_free(st);  // every frame was popped: nothing in flight uses the buffers
+    st->sp = {};
     return MVSV_OK;
 }
 
@@ -1149,13 +1070,11 @@ int mvsv_stream_enable_samplepoints(mvsv_stream* st, const mvsv_rect* roi, int r
     if (!st) return MVSV_E_INVALID_ARG;
     mvsv_ctx* ctx = st->ctx;
     if (!Q) return set_error(ctx, MVSV_E_INVALID_ARG, "null Q");
-    if (st->head != st->tail)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "sample points change only while no frame is pending");
-    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, st->W, st->H};
-    if (q.x0 < 0 || q.y0 < 0 || q.x1 > st->W || q.y1 > st->H || q.x1 <= q.x0 || q.y1 <= q.y0)
+    if (int rc = idle_check(st, "sample points change")) return rc;
+    mvsv_rect q;
+    if (!roi_or_whole(roi, st->W, st->H, &q))
         return set_error(ctx, MVSV_E_INVALID_ARG, "sample point ROI empty or outside the image");
-    if (view_uses_samplepoints(st) && !(q.x0 == st->view_roi.x0 && q.y0 == st->view_roi.y0 && q.x1 == st->view_roi.x1 &&
-                                        q.y1 == st->view_roi.y1))
+    if (view_uses_samplepoints(st) && !same_rect(q, st->view.roi))
         return set_error(ctx, MVSV_E_INVALID_ARG, "the view draws the found points of its own ROI: disable the view first");
     int sx, sy, nx, ny;
     sample_layout(q.x1 - q.x0, q.y1 - q.y0, &sx, &sy, &nx, &ny);
@@ -1163,70 +1082,105 @@ int mvsv_stream_enable_samplepoints(mvsv_stream* st, const mvsv_rect* roi, int r
     if (npts > 0 && (radius < 0 || radius >= std::min(sx, sy)))
         return set_error(ctx, MVSV_E_INVALID_ARG, "sample point radius must be 0 .. min(step_x, step_y) - 1");
     DeviceGuard dev_guard(ctx->device);
-    samplepoints_free(st);
-    st->sp_roi = q;
-    st->sp_radius = radius;
-    st->sp_npts = npts;
-    st->sp_max = max_hits <= 0 ? npts : std::min(max_hits, npts);
-    std::memcpy(st->sp_Q, Q, sizeof(st->sp_Q));
-    st->sp_first = first;
-    st->sp_second = second;
+    Samplepoints& sp = st->sp;
+    sp = {};
+    sp.roi = q;
+    sp.radius = radius;
+    sp.npts = npts;
+    sp.max_hits = max_hits <= 0 ? npts : std::min(max_hits, npts);
+    std::memcpy(sp.Q, Q, sizeof(sp.Q));
+    sp.first = first;
+    sp.second = second;
     const size_t depth = st->slots.size();
-    st->sp_slot_bytes = ((size_t)npts * sizeof(float) + sizeof(int) + (size_t)st->sp_max * sizeof(mvsv_sample_hit) + 15) &
-                        ~(size_t)15;
-    if (npts > 0) {
-        const bool ok = hipMalloc((void**)&st->dSpVal, depth * npts * sizeof(float)) == hipSuccess &&
-                        hipMalloc((void**)&st->dSpCnt, depth * sizeof(int)) == hipSuccess &&
-                        hipMalloc((void**)&st->dSpHits, depth * st->sp_max * sizeof(mvsv_sample_hit)) == hipSuccess &&
-                        hipHostMalloc((void**)&st->hSp, depth * st->sp_slot_bytes, hipHostMallocDefault) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            samplepoints_free(st);
-            return set_error(ctx, MVSV_E_OOM, "sample point buffer allocation failed");
-        }
-    }
-    st->sp = true;
+    sp.lay = ring_slot_block((size_t)npts * sizeof(float), alignof(int), sizeof(int),
+                             (size_t)sp.max_hits * sizeof(mvsv_sample_hit));
+    if (npts > 0 && !(sp.dVal.alloc(depth * npts) && sp.dCnt.alloc(depth) && sp.dHits.alloc(depth * sp.max_hits) &&
+                      sp.host.alloc(depth * sp.lay.bytes)))
+        return stage_oom(st, &sp, "sample point buffer allocation failed");
+    sp.on = true;
     return MVSV_OK;
 }
 
 int mvsv_stream_front_samples(mvsv_stream* st, float* values, int* count, mvsv_sample_hit* hits, int capacity)
 {
     if (!st) return MVSV_E_INVALID_ARG;
-    mvsv_ctx* ctx = st->ctx;
-    if (!st->sp) return set_error(ctx, MVSV_E_INVALID_ARG, "sample points are not enabled on this stream");
-    if (st->head == st->tail) return set_error(ctx, MVSV_E_INVALID_ARG, "stream empty");
-    if (hits && capacity < 0) return set_error(ctx, MVSV_E_INVALID_ARG, "negative capacity");
-    DeviceGuard dev_guard(ctx->device);
-    const long idx = st->tail % (long)st->slots.size();
-    auto& s = st->slots[idx];
+    const Samplepoints& sp = st->sp;
     int rc;
-    if (st->tail >= st->launched && (rc = stream_launch(st))) return rc;  // partial group
-    if ((rc = check_hip(ctx, hipEventSynchronize(s.done), "stream sync"))) return rc;
-    if (s.status) return s.status;
-    // the report word is left for pop to read and clear
-    if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[idx], __ATOMIC_ACQUIRE) != 0))
-        return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
-    if (st->sp_npts == 0) {
+    if ((rc = front_check(st, sp.on, "sample points are not enabled on this stream"))) return rc;
+    if (hits && capacity < 0) return set_error(st->ctx, MVSV_E_INVALID_ARG, "negative capacity");
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    if ((rc = front_wait(st, &idx))) return rc;
+    if (sp.npts == 0) {
         if (count) *count = 0;
         return MVSV_OK;
     }
-    const int total = *st->sp_count(idx);
-    if (values) std::memcpy(values, st->sp_values(idx), (size_t)st->sp_npts * sizeof(float));
+    const int total = *sp.count(idx);
+    if (values) std::memcpy(values, sp.values(idx), (size_t)sp.npts * sizeof(float));
     if (count) *count = total;
     if (hits)
-        std::memcpy(hits, st->sp_hits(idx),
-                    (size_t)std::min(std::min(total, st->sp_max), capacity) * sizeof(mvsv_sample_hit));
+        std::memcpy(hits, sp.hits(idx),
+                    (size_t)std::min(std::min(total, sp.max_hits), capacity) * sizeof(mvsv_sample_hit));
+    return MVSV_OK;
+}
+
+// ---- display and view ----
+
+// The rings of an image stage over q, bytes_per_px bytes a pixel; the stage is off before and on failure.
+static int image_alloc(mvsv_stream* st, ImageStage* g, const mvsv_rect& q, int bytes_per_px, const char* oom)
+{
+    *g = {};
+    g->roi = q;
+    g->row_bytes = (size_t)bytes_per_px * g->width();
+    g->bytes = g->row_bytes * g->height();
+    g->lay = ring_slot_block(g->bytes, alignof(int16_t), 2 * sizeof(int16_t), 0);
+    const size_t depth = st->slots.size();
+    if (!(g->dImg.alloc(depth * g->bytes) && g->dMM.alloc(depth * 2) && g->host.alloc(depth * g->lay.bytes)))
+        return stage_oom(st, g, oom);
+    g->on = true;
+    return MVSV_OK;
+}
+
+// The oldest pending frame of an image stage; host: what is read is the pinned image.
+static int image_front(mvsv_stream* st, const ImageStage& g, const ImageTexts& t, bool host, long* idx)
+{
+    if (host && g.on && !(st->host_mask & t.host_bit)) return set_error(st->ctx, MVSV_E_INVALID_ARG, t.host_off);
+    return front_slot(st, g.on, t.not_enabled, idx);
+}
+
+// front_display / front_view: the image copied into the caller's rows
+static int image_front_copy(mvsv_stream* st, ImageStage mvsv_stream::*stage, const ImageTexts& t, uint8_t* out,
+                            size_t out_stride, int16_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    const ImageStage& g = st->*stage;
+    if (g.on && out && out_stride < g.row_bytes) return set_error(st->ctx, MVSV_E_INVALID_ARG, t.stride);
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    if (int rc = image_front(st, g, t, true, &idx)) return rc;
+    if (out) copy_rows(out, out_stride, g.image(idx), g.row_bytes, g.row_bytes, g.height(), 0, 1);
+    if (minmax) std::memcpy(minmax, g.minmax(idx), 2 * sizeof(int16_t));
+    return MVSV_OK;
+}
+
+// front_*_view (host) / front_*_device: the image where it is, valid until the slot's reuse
+static int image_front_ptr(mvsv_stream* st, ImageStage mvsv_stream::*stage, const ImageTexts& t, bool host,
+                           const uint8_t** image, int16_t* minmax)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    if (!image) return set_error(st->ctx, MVSV_E_INVALID_ARG, t.null_out);
+    const ImageStage& g = st->*stage;
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    if (int rc = image_front(st, g, t, host, &idx)) return rc;
+    *image = host ? g.image(idx) : g.dev_image(idx);
+    if (minmax) std::memcpy(minmax, g.minmax(idx), 2 * sizeof(int16_t));
     return MVSV_OK;
 }
 
 int mvsv_stream_disable_display(mvsv_stream* st)
 {
-    if (!st) return MVSV_E_INVALID_ARG;
-    if (st->head != st->tail)
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the display changes only while no frame is pending");
-    DeviceGuard dev_guard(st->ctx->device);
-    display_free(st);  // every frame was popped: nothing in flight uses the buffers
-    return MVSV_OK;
+    return stage_disable(st, &mvsv_stream::disp, "the display changes");
 }
 
 int mvsv_stream_enable_display(mvsv_stream* st, const mvsv_rect* roi, double alpha, double beta)
@@ -1235,145 +1189,96 @@ int mvsv_stream_enable_display(mvsv_stream* st, const mvsv_rect* roi, double alp
     mvsv_ctx* ctx = st->ctx;
     if (!std::isfinite(alpha) || !std::isfinite(beta))
         return set_error(ctx, MVSV_E_INVALID_ARG, "display alpha / beta must be finite");
-    if (st->head != st->tail)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "the display changes only while no frame is pending");
-    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, st->W, st->H};
-    if (q.x0 < 0 || q.y0 < 0 || q.x1 > st->W || q.y1 > st->H || q.x1 <= q.x0 || q.y1 <= q.y0)
+    if (int rc = idle_check(st, "the display changes")) return rc;
+    mvsv_rect q;
+    if (!roi_or_whole(roi, st->W, st->H, &q))
         return set_error(ctx, MVSV_E_INVALID_ARG, "display ROI empty or outside the image");
     DeviceGuard dev_guard(ctx->device);
-    display_free(st);
-    st->disp_roi = q;
     st->disp_alpha = alpha;
     st->disp_beta = beta;
-    st->disp_px = (size_t)(q.x1 - q.x0) * (q.y1 - q.y0);
-    st->disp_slot_bytes = (((st->disp_px + 1) & ~(size_t)1) + 2 * sizeof(int16_t) + 15) & ~(size_t)15;
-    const size_t depth = st->slots.size();
-    const bool ok = hipMalloc((void**)&st->dDisp, depth * st->disp_px) == hipSuccess &&
-                    hipMalloc((void**)&st->dDispMM, depth * 2 * sizeof(int16_t)) == hipSuccess &&
-                    hipHostMalloc((void**)&st->hDisp, depth * st->disp_slot_bytes, hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        display_free(st);
-        return set_error(ctx, MVSV_E_OOM, "display buffer allocation failed");
-    }
-    st->disp = true;
-    return MVSV_OK;
-}
-
-// the oldest pending frame, complete: its slot index in *idx
-static int front_slot(mvsv_stream* st, bool enabled, const char* not_enabled, long* idx)
-{
-    mvsv_ctx* ctx = st->ctx;
-    if (!enabled) return set_error(ctx, MVSV_E_INVALID_ARG, not_enabled);
-    if (st->head == st->tail) return set_error(ctx, MVSV_E_INVALID_ARG, "stream empty");
-    *idx = st->tail % (long)st->slots.size();
-    auto& s = st->slots[*idx];
-    int rc;
-    if (st->tail >= st->launched && (rc = stream_launch(st))) return rc;  // partial group
-    if ((rc = check_hip(ctx, hipEventSynchronize(s.done), "stream sync"))) return rc;
-    if (s.status) return s.status;
-    // the report word is left for pop to read and clear
-    if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[*idx], __ATOMIC_ACQUIRE) != 0))
-        return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
-    return MVSV_OK;
-}
-
-static int display_front(mvsv_stream* st, long* idx, bool host = true)
-{
-    if (host && st->disp && !(st->host_mask & MVSV_HOST_DISPLAY))
-        return set_error(st->ctx, MVSV_E_INVALID_ARG,
-                         "the host display map is switched off (mvsv_stream_set_host_outputs)");
-    return front_slot(st, st->disp, "the display is not enabled on this stream", idx);
+    return image_alloc(st, &st->disp, q, 1, "display buffer allocation failed");
 }
 
 int mvsv_stream_front_display(mvsv_stream* st, uint8_t* out, size_t out_stride, int16_t* minmax)
 {
-    if (!st) return MVSV_E_INVALID_ARG;
-    const int rw = st->disp_roi.x1 - st->disp_roi.x0, rh = st->disp_roi.y1 - st->disp_roi.y0;
-    if (st->disp && out && out_stride < (size_t)rw)
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "display stride smaller than the ROI's width");
-    DeviceGuard dev_guard(st->ctx->device);
-    long idx;
-    int rc;
-    if ((rc = display_front(st, &idx))) return rc;
-    if (out) copy_rows(out, out_stride, st->disp_map(idx), (size_t)rw, (size_t)rw, rh, 0, 1);
-    if (minmax) std::memcpy(minmax, st->disp_minmax(idx), 2 * sizeof(int16_t));
-    return MVSV_OK;
+    return image_front_copy(st, &mvsv_stream::disp, kDisplayTexts, out, out_stride, minmax);
 }
 
 int mvsv_stream_front_display_view(mvsv_stream* st, const uint8_t** map, int16_t* minmax)
 {
-    if (!st) return MVSV_E_INVALID_ARG;
-    if (!map) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null map pointer");
-    DeviceGuard dev_guard(st->ctx->device);
-    long idx;
-    int rc;
-    if ((rc = display_front(st, &idx))) return rc;
-    *map = st->disp_map(idx);
-    if (minmax) std::memcpy(minmax, st->disp_minmax(idx), 2 * sizeof(int16_t));
-    return MVSV_OK;
+    return image_front_ptr(st, &mvsv_stream::disp, kDisplayTexts, true, map, minmax);
 }
+
+int mvsv_stream_disable_view(mvsv_stream* st) { return stage_disable(st, &mvsv_stream::view, "the view changes"); }
+
+int mvsv_stream_enable_view(mvsv_stream* st, const mvsv_rect* roi, const mvsv_view_spec* spec)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    mvsv_rect q;
+    if (!roi_or_whole(roi, st->W, st->H, &q))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "view ROI empty or outside the image");
+    if (const char* why = view_check(spec, q.x1 - q.x0, q.y1 - q.y0)) return set_error(ctx, MVSV_E_INVALID_ARG, why);
+    if (int rc = idle_check(st, "the view changes")) return rc;
+    if ((spec->layers & MVSV_VIEW_FOUND_TILES) && !(st->grid && same_rect(st->roi, q)))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "FOUND_TILES needs a stream created with a grid_roi equal to the view's ROI");
+    if ((spec->layers & MVSV_VIEW_FOUND_POINTS) && !(st->sp.on && same_rect(st->sp.roi, q)))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "FOUND_POINTS needs sample points enabled with the view's ROI");
+    DeviceGuard dev_guard(ctx->device);
+    st->view_spec = *spec;
+    return image_alloc(st, &st->view, q, 3, "view buffer allocation failed");
+}
+
+int mvsv_stream_front_view(mvsv_stream* st, uint8_t* out, size_t out_stride, int16_t* minmax)
+{
+    return image_front_copy(st, &mvsv_stream::view, kViewTexts, out, out_stride, minmax);
+}
+
+int mvsv_stream_front_view_view(mvsv_stream* st, const uint8_t** view, int16_t* minmax)
+{
+    return image_front_ptr(st, &mvsv_stream::view, kViewTexts, true, view, minmax);
+}
+
+// ---- sharpness ----
 
 int mvsv_stream_disable_sharpness(mvsv_stream* st)
 {
-    if (!st) return MVSV_E_INVALID_ARG;
-    if (st->head != st->tail)
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the sharpness changes only while no frame is pending");
-    DeviceGuard dev_guard(st->ctx->device);
-    sharpness_free(st);  // every frame was popped: nothing in flight uses the buffers
-    return MVSV_OK;
+    return stage_disable(st, &mvsv_stream::sharp, "the sharpness changes");
 }
 
 int mvsv_stream_enable_sharpness(mvsv_stream* st, const mvsv_rect* roi_left, const mvsv_rect* roi_right)
 {
     if (!st) return MVSV_E_INVALID_ARG;
     mvsv_ctx* ctx = st->ctx;
-    if (st->head != st->tail)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "the sharpness changes only while no frame is pending");
+    if (int rc = idle_check(st, "the sharpness changes")) return rc;
     // the pushed images' size
     const int iw = st->raw ? st->rawW : st->W, ih = st->raw ? st->rawH : st->H;
-    const mvsv_rect* rois[2] = {roi_left, roi_right};
     mvsv_rect q[2];
-    for (int i = 0; i < 2; i++) {
-        q[i] = rois[i] ? *rois[i] : mvsv_rect{0, 0, iw, ih};
-        if (q[i].x0 < 0 || q[i].y0 < 0 || q[i].x1 > iw || q[i].y1 > ih || q[i].x1 <= q[i].x0 || q[i].y1 <= q[i].y0)
-            return set_error(ctx, MVSV_E_INVALID_ARG, "sharpness ROI empty or outside the pushed image");
-    }
+    if (!roi_or_whole(roi_left, iw, ih, &q[0]) || !roi_or_whole(roi_right, iw, ih, &q[1]))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "sharpness ROI empty or outside the pushed image");
     DeviceGuard dev_guard(ctx->device);
-    sharpness_free(st);
-    st->sharp_roi[0] = q[0];
-    st->sharp_roi[1] = q[1];
-    const size_t bytes = st->slots.size() * 2 * sizeof(int64_t);
-    const bool ok = hipMalloc((void**)&st->dSharp, bytes) == hipSuccess &&
-                    hipHostMalloc((void**)&st->hSharp, bytes, hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        sharpness_free(st);
-        return set_error(ctx, MVSV_E_OOM, "sharpness buffer allocation failed");
-    }
-    st->sharp = true;
+    Sharpness& sh = st->sharp;
+    sh = {};
+    sh.roi[0] = q[0];
+    sh.roi[1] = q[1];
+    if (!(sh.dSum.alloc(2 * st->slots.size()) && sh.hSum.alloc(2 * st->slots.size())))
+        return stage_oom(st, &sh, "sharpness buffer allocation failed");
+    sh.on = true;
     return MVSV_OK;
 }
 
 int mvsv_stream_front_sharpness(mvsv_stream* st, double value[2], int64_t sum4[2])
 {
     if (!st) return MVSV_E_INVALID_ARG;
-    mvsv_ctx* ctx = st->ctx;
-    if (!st->sharp) return set_error(ctx, MVSV_E_INVALID_ARG, "the sharpness is not enabled on this stream");
-    if (st->head == st->tail) return set_error(ctx, MVSV_E_INVALID_ARG, "stream empty");
-    DeviceGuard dev_guard(ctx->device);
-    const long idx = st->tail % (long)st->slots.size();
-    auto& s = st->slots[idx];
+    const Sharpness& sh = st->sharp;
     int rc;
-    if (st->tail >= st->launched && (rc = stream_launch(st))) return rc;  // partial group
-    if ((rc = check_hip(ctx, hipEventSynchronize(s.done), "stream sync"))) return rc;
-    if (s.status) return s.status;
-    // the report word is left for pop to read and clear
-    if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[idx], __ATOMIC_ACQUIRE) != 0))
-        return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
+    if ((rc = front_check(st, sh.on, "the sharpness is not enabled on this stream"))) return rc;
+    DeviceGuard dev_guard(st->ctx->device);
+    long idx;
+    if ((rc = front_wait(st, &idx))) return rc;
     for (int i = 0; i < 2; i++) {
-        const mvsv_rect& q = st->sharp_roi[i];
-        const int64_t s4 = st->hSharp[2 * idx + i];
+        const mvsv_rect& q = sh.roi[i];
+        const int64_t s4 = sh.hSum[2 * idx + i];
         if (sum4) sum4[i] = s4;
         // cv::mean: sum * (1.0 / N), a reciprocal and a product, each rounded
         if (value) value[i] = ((double)s4 / 4.0) * (1.0 / ((double)(q.x1 - q.x0) * (double)(q.y1 - q.y0)));
@@ -1381,14 +1286,11 @@ int mvsv_stream_front_sharpness(mvsv_stream* st, double value[2], int64_t sum4[2
     return MVSV_OK;
 }
 
+// ---- point cloud ----
+
 int mvsv_stream_disable_cloud(mvsv_stream* st)
 {
-    if (!st) return MVSV_E_INVALID_ARG;
-    if (st->head != st->tail)
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the point cloud changes only while no frame is pending");
-    DeviceGuard dev_guard(st->ctx->device);
-    cloud_free(st);  // every frame was popped: nothing in flight uses the buffers
-    return MVSV_OK;
+    return stage_disable(st, &mvsv_stream::cloud, "the point cloud changes");
 }
 
 int mvsv_stream_enable_cloud(mvsv_stream* st, const mvsv_rect* roi, const float* Q, int max_points)
@@ -1396,49 +1298,31 @@ int mvsv_stream_enable_cloud(mvsv_stream* st, const mvsv_rect* roi, const float*
     if (!st) return MVSV_E_INVALID_ARG;
     mvsv_ctx* ctx = st->ctx;
     if (!Q) return set_error(ctx, MVSV_E_INVALID_ARG, "null Q matrix");
-    if (st->head != st->tail)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "the point cloud changes only while no frame is pending");
-    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, st->W, st->H};
-    if (q.x0 < 0 || q.y0 < 0 || q.x1 > st->W || q.y1 > st->H || q.x1 <= q.x0 || q.y1 <= q.y0)
+    if (int rc = idle_check(st, "the point cloud changes")) return rc;
+    mvsv_rect q;
+    if (!roi_or_whole(roi, st->W, st->H, &q))
         return set_error(ctx, MVSV_E_INVALID_ARG, "point cloud ROI empty or outside the image");
     const size_t roi_px = (size_t)(q.x1 - q.x0) * (q.y1 - q.y0);
     if (roi_px > (size_t)INT32_MAX) return set_error(ctx, MVSV_E_INVALID_ARG, "point cloud ROI too large");
     DeviceGuard dev_guard(ctx->device);
-    cloud_free(st);
-    st->cloud_roi = q;
-    std::memcpy(st->cloud_Q, Q, sizeof(st->cloud_Q));
-    st->cloud_max = (int)(max_points <= 0 ? roi_px : std::min((size_t)max_points, roi_px));
+    Cloud& c = st->cloud;
+    c = {};
+    c.roi = q;
+    std::memcpy(c.Q, Q, sizeof(c.Q));
+    c.max_points = (int)(max_points <= 0 ? roi_px : std::min((size_t)max_points, roi_px));
     const size_t depth = st->slots.size();
-    const bool ok =
-        hipMalloc((void**)&st->dCloud, depth * (size_t)st->cloud_max * sizeof(mvsv_cloud_point)) == hipSuccess &&
-        hipMalloc((void**)&st->dCloudHdr, depth * 3 * sizeof(int)) == hipSuccess &&
-        hipHostMalloc((void**)&st->hCloudHdr, depth * 3 * sizeof(int), hipHostMallocDefault) == hipSuccess &&
-        hipStreamCreateWithFlags(&st->cloud_copy, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        cloud_free(st);
-        return set_error(ctx, MVSV_E_OOM, "point cloud buffer allocation failed");
-    }
-    st->cloud = true;
+    if (!(c.dRec.alloc(depth * (size_t)c.max_points) && c.dHdr.alloc(depth * 3) && c.hHdr.alloc(depth * 3) &&
+          c.copy.create()))
+        return stage_oom(st, &c, "point cloud buffer allocation failed");
+    c.on = true;
     return MVSV_OK;
 }
 
-// the oldest pending frame, complete: its slot index in *idx
+// the oldest pending frame's cloud header; its slot index in *idx
 static int cloud_front(mvsv_stream* st, long* idx, int* count, int32_t* minmax)
 {
-    mvsv_ctx* ctx = st->ctx;
-    if (!st->cloud) return set_error(ctx, MVSV_E_INVALID_ARG, "the point cloud is not enabled on this stream");
-    if (st->head == st->tail) return set_error(ctx, MVSV_E_INVALID_ARG, "stream empty");
-    *idx = st->tail % (long)st->slots.size();
-    auto& s = st->slots[*idx];
-    int rc;
-    if (st->tail >= st->launched && (rc = stream_launch(st))) return rc;  // partial group
-    if ((rc = check_hip(ctx, hipEventSynchronize(s.done), "stream sync"))) return rc;
-    if (s.status) return s.status;
-    // the report word is left for pop to read and clear
-    if (s.gave_up || (s.run_len > 0 && __atomic_load_n(&st->rep[*idx], __ATOMIC_ACQUIRE) != 0))
-        return set_error(ctx, MVSV_E_TIMEOUT, "stream frame: a strip-boundary wait of its SGBM launch gave up");
-    const int* h = st->hCloudHdr + 3 * *idx;
+    if (int rc = front_slot(st, st->cloud.on, "the point cloud is not enabled on this stream", idx)) return rc;
+    const int* h = st->cloud.hHdr + 3 * *idx;
     if (count) *count = h[0];
     if (minmax) {
         minmax[0] = h[1];
@@ -1452,17 +1336,17 @@ int mvsv_stream_front_cloud(mvsv_stream* st, mvsv_cloud_point* records, int capa
     if (!st) return MVSV_E_INVALID_ARG;
     if (records && capacity < 0) return set_error(st->ctx, MVSV_E_INVALID_ARG, "negative point cloud capacity");
     DeviceGuard dev_guard(st->ctx->device);
+    const Cloud& c = st->cloud;
     long idx;
     int rc;
     if ((rc = cloud_front(st, &idx, count, minmax))) return rc;
-    const size_t k = records ? (size_t)std::min(std::min(st->hCloudHdr[3 * idx], st->cloud_max), capacity) : 0;
+    const size_t k = records ? (size_t)std::min(std::min(c.hHdr[3 * idx], c.max_points), capacity) : 0;
     if (k == 0) return MVSV_OK;
     // the frame is complete; a stream of its own, so the copy does not queue behind the later frames' downloads
-    if ((rc = check_hip(st->ctx, hipMemcpyAsync(records, st->dCloud + (size_t)idx * st->cloud_max,
-                                                k * sizeof(mvsv_cloud_point), hipMemcpyDeviceToHost, st->cloud_copy),
-                        "stream D2H")))
+    if ((rc = check_hip(st->ctx, hipMemcpyAsync(records, c.dev_records(idx), k * sizeof(mvsv_cloud_point),
+                                                hipMemcpyDeviceToHost, c.copy), "stream D2H")))
         return rc;
-    return check_hip(st->ctx, hipStreamSynchronize(st->cloud_copy), "stream sync");
+    return check_hip(st->ctx, hipStreamSynchronize(c.copy), "stream sync");
 }
 
 int mvsv_stream_front_cloud_device(mvsv_stream* st, const mvsv_cloud_point** records_dev, int* count, int32_t* minmax)
@@ -1471,94 +1355,11 @@ int mvsv_stream_front_cloud_device(mvsv_stream* st, const mvsv_cloud_point** rec
     if (!records_dev) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null records pointer");
     DeviceGuard dev_guard(st->ctx->device);
     long idx;
-    int rc;
-    if ((rc = cloud_front(st, &idx, count, minmax))) return rc;
-    *records_dev = st->dCloud + (size_t)idx * st->cloud_max;
+    if (int rc = cloud_front(st, &idx, count, minmax)) return rc;
+    *records_dev = st->cloud.dev_records(idx);
     return MVSV_OK;
 }
 
-static bool same_rect(const mvsv_rect& a, const mvsv_rect& b)
-{
-    return a.x0 == b.x0 && a.y0 == b.y0 && a.x1 == b.x1 && a.y1 == b.y1;
-}
-
-int mvsv_stream_disable_view(mvsv_stream* st)
-{
-    if (!st) return MVSV_E_INVALID_ARG;
-    if (st->head != st->tail)
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the view changes only while no frame is pending");
-    DeviceGuard dev_guard(st->ctx->device);
-    view_free(st);  // every frame was popped: nothing in flight uses the buffers
-    return MVSV_OK;
-}
-
-int mvsv_stream_enable_view(mvsv_stream* st, const mvsv_rect* roi, const mvsv_view_spec* spec)
-{
-    if (!st) return MVSV_E_INVALID_ARG;
-    mvsv_ctx* ctx = st->ctx;
-    const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, st->W, st->H};
-    if (q.x0 < 0 || q.y0 < 0 || q.x1 > st->W || q.y1 > st->H || q.x1 <= q.x0 || q.y1 <= q.y0)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "view ROI empty or outside the image");
-    if (const char* why = view_check(spec, q.x1 - q.x0, q.y1 - q.y0)) return set_error(ctx, MVSV_E_INVALID_ARG, why);
-    if (st->head != st->tail)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "the view changes only while no frame is pending");
-    if ((spec->layers & MVSV_VIEW_FOUND_TILES) && !(st->grid && same_rect(st->roi, q)))
-        return set_error(ctx, MVSV_E_INVALID_ARG, "FOUND_TILES needs a stream created with a grid_roi equal to the view's ROI");
-    if ((spec->layers & MVSV_VIEW_FOUND_POINTS) && !(st->sp && same_rect(st->sp_roi, q)))
-        return set_error(ctx, MVSV_E_INVALID_ARG, "FOUND_POINTS needs sample points enabled with the view's ROI");
-    DeviceGuard dev_guard(ctx->device);
-    view_free(st);
-    st->view_roi = q;
-    st->view_spec = *spec;
-    st->view_bytes = 3 * (size_t)(q.x1 - q.x0) * (q.y1 - q.y0);
-    st->view_slot_bytes = (((st->view_bytes + 1) & ~(size_t)1) + 2 * sizeof(int16_t) + 15) & ~(size_t)15;
-    const size_t depth = st->slots.size();
-    const bool ok = hipMalloc((void**)&st->dView, depth * st->view_bytes) == hipSuccess &&
-                    hipMalloc((void**)&st->dViewMM, depth * 2 * sizeof(int16_t)) == hipSuccess &&
-                    hipHostMalloc((void**)&st->hView, depth * st->view_slot_bytes, hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        view_free(st);
-        return set_error(ctx, MVSV_E_OOM, "view buffer allocation failed");
-    }
-    st->view = true;
-    return MVSV_OK;
-}
-
-static int view_front(mvsv_stream* st, long* idx, bool host = true)
-{
-    if (host && st->view && !(st->host_mask & MVSV_HOST_VIEW))
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the host view is switched off (mvsv_stream_set_host_outputs)");
-    return front_slot(st, st->view, "the view is not enabled on this stream", idx);
-}
-
-int mvsv_stream_front_view(mvsv_stream* st, uint8_t* out, size_t out_stride, int16_t* minmax)
-{
-    if (!st) return MVSV_E_INVALID_ARG;
-    const size_t rb = 3 * (size_t)(st->view_roi.x1 - st->view_roi.x0);
-    if (st->view && out && out_stride < rb)
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "view stride smaller than three times the ROI's width");
-    DeviceGuard dev_guard(st->ctx->device);
-    long idx;
-    int rc;
-    if ((rc = view_front(st, &idx))) return rc;
-    if (out) copy_rows(out, out_stride, st->view_img(idx), rb, rb, st->view_roi.y1 - st->view_roi.y0, 0, 1);
-    if (minmax) std::memcpy(minmax, st->view_minmax(idx), 2 * sizeof(int16_t));
-    return MVSV_OK;
-}
-
-int mvsv_stream_front_view_view(mvsv_stream* st, const uint8_t** view, int16_t* minmax)
-{
-    if (!st) return MVSV_E_INVALID_ARG;
-    if (!view) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null view pointer");
-    DeviceGuard dev_guard(st->ctx->device);
-    long idx;
-    int rc;
-    if ((rc = view_front(st, &idx))) return rc;
-    *view = st->view_img(idx);
-    if (minmax) std::memcpy(minmax, st->view_minmax(idx), 2 * sizeof(int16_t));
-    return MVSV_OK;
-}
 
 // ---- device ends of the stream ----
 
@@ -1582,8 +1383,6 @@ static bool source_ok(const mvsv_stream* st, const uint8_t* p, size_t span)
     return true;
 }
 
-enum PushKind { kPushRectified, kPushRaw, kPushBgr };
-
 // n frames from device-readable memory into the next n slots: one copy launch per
 // contiguous ring segment on the upload stream, ordered against the producer's
 // stream by events in both directions; then the bookkeeping of n single pushes.
@@ -1592,14 +1391,11 @@ static int stream_push_device(mvsv_stream* st, PushKind kind, int n, const uint8
 {
     if (!st) return MVSV_E_INVALID_ARG;
     mvsv_ctx* ctx = st->ctx;
-    if (kind == kPushRaw && !st->raw)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "stream of rectified pairs: push them with mvsv_stream_push_device");
-    if (kind != kPushRaw && st->raw)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "raw stream: push raw pairs with mvsv_stream_push_raw_device");
-    if (kind == kPushBgr && !st->bgr)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "colour input is not enabled on this stream");
-    const int rows = kind == kPushRaw ? st->rawH : kind == kPushBgr ? st->bgrH : st->H;
-    const size_t row = kind == kPushRaw ? (size_t)st->rawW : kind == kPushBgr ? 3 * (size_t)st->bgrW : (size_t)st->W;
+    int rc;
+    if ((rc = push_kind_check(st, kind, true))) return rc;
+    const PushGeom g = st->push_geom(kind);
+    const int rows = g.rows;
+    const size_t row = g.row;  // of the source; the slots' rows are g.stride apart
     if (!L || !R || ls < row || rs < row)
         return set_error(ctx, MVSV_E_INVALID_ARG, "null frame or stride smaller than the row");
     const long depth = (long)st->slots.size();
@@ -1613,7 +1409,6 @@ static int stream_push_device(mvsv_stream* st, PushKind kind, int n, const uint8
         return set_error(ctx, MVSV_E_INVALID_ARG,
                          "device push: memory of the stream's device or device-accessible host memory expected");
     hipStream_t prod = (hipStream_t)producer;
-    int rc;
     if ((rc = check_hip(ctx, hipEventRecord(st->producer_ev, prod), "stream event")) ||
         (rc = check_hip(ctx, hipStreamWaitEvent(st->up, st->producer_ev, 0), "stream wait")))
         return rc;
@@ -1621,21 +1416,12 @@ static int stream_push_device(mvsv_stream* st, PushKind kind, int n, const uint8
     const int nseg = ring_push_segments(st->head, n, depth, seg);
     // the slots' previous frames were popped, so everything that read or wrote them is complete
     int done = 0;
-    for (int g = 0; g < nseg; g++) {
-        auto& first = st->slots[seg[g].i0];
-        uint8_t *dl, *dr;
-        size_t ds, dfs;
-        if (kind == kPushRaw) {
-            dl = first.dRaw, dr = first.dRaw + row * rows, ds = row, dfs = 2 * row * rows;
-        } else if (kind == kPushBgr) {
-            dl = first.dBgr, dr = first.dBgr + st->bgrRow * rows, ds = st->bgrRow, dfs = 2 * st->bgrRow * rows;
-        } else {
-            dl = first.dL, dr = first.dR, ds = row, dfs = row * rows;
-        }
-        if ((rc = stream_copy_device(ctx, st->up, seg[g].n, L + done * lfs, ls, lfs, R + done * rfs, rs, rfs, dl, dr,
-                                     ds, dfs, (int)row, rows)))
+    for (int s = 0; s < nseg; s++) {
+        const PushEnds e = push_ends(st, kind, g, seg[s].i0);
+        if ((rc = stream_copy_device(ctx, st->up, seg[s].n, L + done * lfs, ls, lfs, R + done * rfs, rs, rfs, e.dl,
+                                     e.dr, g.stride, g.frame, (int)row, rows)))
             return rc;
-        done += seg[g].n;
+        done += seg[s].n;
     }
     // n single pushes: a launch waits for the `uploaded` event of its last slot, which is
     // the frame that completes a group, the ring's last slot or the call's last frame
@@ -1677,8 +1463,7 @@ int mvsv_stream_set_host_outputs(mvsv_stream* st, int mask)
 {
     if (!st) return MVSV_E_INVALID_ARG;
     if (mask & ~MVSV_HOST_ALL) return set_error(st->ctx, MVSV_E_INVALID_ARG, "unknown host output bit");
-    if (st->head != st->tail)
-        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the host outputs change only while no frame is pending");
+    if (int rc = idle_check(st, "the host outputs change")) return rc;
     st->host_mask = mask;
     return MVSV_OK;
 }
@@ -1732,28 +1517,12 @@ int mvsv_stream_front_rectified_device(mvsv_stream* st, const uint8_t** left_dev
 
 int mvsv_stream_front_display_device(mvsv_stream* st, const uint8_t** map_dev, int16_t* minmax)
 {
-    if (!st) return MVSV_E_INVALID_ARG;
-    if (!map_dev) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null map pointer");
-    DeviceGuard dev_guard(st->ctx->device);
-    long idx;
-    int rc;
-    if ((rc = display_front(st, &idx, false))) return rc;
-    *map_dev = st->dDisp + (size_t)idx * st->disp_px;
-    if (minmax) std::memcpy(minmax, st->disp_minmax(idx), 2 * sizeof(int16_t));
-    return MVSV_OK;
+    return image_front_ptr(st, &mvsv_stream::disp, kDisplayTexts, false, map_dev, minmax);
 }
 
 int mvsv_stream_front_view_device(mvsv_stream* st, const uint8_t** bgr_dev, int16_t* minmax)
 {
-    if (!st) return MVSV_E_INVALID_ARG;
-    if (!bgr_dev) return set_error(st->ctx, MVSV_E_INVALID_ARG, "null view pointer");
-    DeviceGuard dev_guard(st->ctx->device);
-    long idx;
-    int rc;
-    if ((rc = view_front(st, &idx, false))) return rc;
-    *bgr_dev = st->dView + (size_t)idx * st->view_bytes;
-    if (minmax) std::memcpy(minmax, st->view_minmax(idx), 2 * sizeof(int16_t));
-    return MVSV_OK;
+    return image_front_ptr(st, &mvsv_stream::view, kViewTexts, false, bgr_dev, minmax);
 }
 
 int mvsv_stream_fence(mvsv_stream* st, void* hip_stream)
@@ -1779,7 +1548,7 @@ void mvsv_stream_destroy(mvsv_stream* st)
     (void)hipStreamSynchronize(st->up);
     for (mvsv_ctx* c : st->lanes) (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(st->down);
-    stream_free(st);
+    delete st;
 }
 
 int mvsv_mean_disparity_grid(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H,

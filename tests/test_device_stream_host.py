@@ -39,6 +39,7 @@ def test_ring_segments_and_pointer_classes_under_asan_ubsan(tmp_path):
     r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 failures" in r.stdout and "segments:" in r.stdout and "sources:" in r.stdout
+    assert "slot blocks:" in r.stdout and "push geometry:" in r.stdout
 
 
 def c_params(decl):
