@@ -292,6 +292,29 @@ enum {
 MVSV_API int mvsv_sgbm_plan(mvsv_ctx* ctx, int n, int width, int height, const mvsv_sgbm_params* p,
                             int* plan);
 
+/* StereoSGBM on 3-channel pairs, as cv::StereoSGBM::compute takes CV_8UC3: images
+ * are interleaved 8-bit, 3 bytes per pixel (channel c of pixel x = byte 3x + c),
+ * and the Birchfield-Tomasi pixel cost is the sum of the three channels' costs
+ * ([OpenCV] calcPixelCostBT, cn == 3); everything after the pixel cost is that of
+ * mvsv_sgbm.  width is in pixels; the input strides are in bytes (row stride
+ * >= 3 * width), out_stride / out_frame_stride in int16 elements.  Arguments,
+ * mvsv_sgbm_validate's rules and error codes otherwise as mvsv_sgbm /
+ * mvsv_sgbm_device.  The channel order does not matter to the result. */
+MVSV_API int mvsv_sgbm_bgr(mvsv_ctx* ctx, const uint8_t* left, size_t left_stride,
+                           const uint8_t* right, size_t right_stride, int width, int height,
+                           const mvsv_sgbm_params* p, int16_t* out, size_t out_stride);
+MVSV_API int mvsv_sgbm_bgr_device(mvsv_ctx* ctx, int n, const uint8_t* left, size_t left_stride,
+                                  size_t left_frame_stride, const uint8_t* right,
+                                  size_t right_stride, size_t right_frame_stride, int width,
+                                  int height, const mvsv_sgbm_params* p, int16_t* out,
+                                  size_t out_stride, size_t out_frame_stride);
+/* mvsv_sgbm_workspace_bytes / mvsv_sgbm_plan for a pair of `channels` (1 or 3)
+ * channels: a colour launch never runs the bit-sliced or residual pipelines. */
+MVSV_API size_t mvsv_sgbm_workspace_bytes_cn(int n, int width, int height,
+                                             const mvsv_sgbm_params* p, int channels);
+MVSV_API int mvsv_sgbm_plan_cn(mvsv_ctx* ctx, int n, int width, int height, const mvsv_sgbm_params* p,
+                               int channels, int* plan);
+
 /* MeanDisparityDetection post-pass on device: 9x9 tile means of an int16 map
  * (tile = (W/9)x(H/9), remainder ignored; mean over values > 1 with integer
  * division, 0 for an empty tile).  means: 81 floats per frame (device ptr). */
@@ -732,6 +755,18 @@ MVSV_API int mvsv_stream_enable_bgr(mvsv_stream* s, int src_width, int src_heigh
 MVSV_API int mvsv_stream_disable_bgr(mvsv_stream* s);
 MVSV_API int mvsv_stream_push_bgr(mvsv_stream* s, const uint8_t* left, size_t left_stride, const uint8_t* right,
                                   size_t right_stride);
+/* mvsv_stream_set_bgr_match: with on != 0 the map of every BGR frame pushed from now on
+ * comes from the colour matcher (mvsv_sgbm_bgr_device) on the frame's BGR pair at the
+ * stream's size: the INTER_AREA half of mvsv_prepare_gray per channel, without the grey
+ * conversion, or the pushed pair itself with halve 0.  The grey pair is still prepared
+ * and feeds the sharpness product and every other grey product as before; every product
+ * computed from the map follows the colour map.  Valid after mvsv_stream_enable_bgr,
+ * while no frame is pending and with the SGBM matcher (MVSV_E_INVALID_ARG otherwise);
+ * while it is on, mvsv_stream_set_bm_params is MVSV_E_INVALID_ARG.  Grey pushes keep
+ * working; a frame-batch launch never holds grey-matched and colour-matched frames
+ * together (a frame of the other kind sends the pending ones off first, as a parameter
+ * change does).  mvsv_stream_disable_bgr and a new mvsv_stream_enable_bgr switch it off. */
+MVSV_API int mvsv_stream_set_bgr_match(mvsv_stream* s, int on);
 
 /* ---- device ends of a stream: frames from device memory, maps handed back there ------
  * mvsv_stream_push_device / _push_raw_device / _push_bgr_device: n >= 1 frames (strides in

@@ -51,16 +51,20 @@ inline void check_inputs(const cv::Mat& L, const cv::Mat& R)
     CV_Assert(L.size() == R.size() && L.type() == R.type() && L.type() == CV_8UC1);
 }
 
-// Drop-in for dispCompute->compute(L, R, out) with a cv::StereoSGBM matcher.
+// Drop-in for dispCompute->compute(L, R, out) with a cv::StereoSGBM matcher:
+// CV_8UC1 pairs, or CV_8UC3 pairs matched in colour as cv::StereoSGBM does.
 inline void compute(const cv::Ptr<cv::StereoSGBM>& m, const cv::Mat& L, const cv::Mat& R,
                     cv::Mat& out)
 {
-    check_inputs(L, R);
+    CV_Assert(L.size() == R.size() && L.type() == R.type() && (L.type() == CV_8UC1 || L.type() == CV_8UC3));
     out.create(L.size(), CV_16S);
     mvsv_sgbm_params p = params_of(*m);
     mvsv_ctx* c = mvsv::thread_context();
-    int rc = mvsv_sgbm(c, L.data, L.step, R.data, R.step, L.cols, L.rows, &p,
-                       out.ptr<int16_t>(), out.step / sizeof(int16_t));
+    int rc = L.type() == CV_8UC3
+                 ? mvsv_sgbm_bgr(c, L.data, L.step, R.data, R.step, L.cols, L.rows, &p, out.ptr<int16_t>(),
+                                 out.step / sizeof(int16_t))
+                 : mvsv_sgbm(c, L.data, L.step, R.data, R.step, L.cols, L.rows, &p,
+                             out.ptr<int16_t>(), out.step / sizeof(int16_t));
     if (rc < 0) CV_Error(cv::Error::StsError, mvsv_last_error(c));
 }
 

@@ -663,6 +663,10 @@ public:
         check(mvsv_stream_enable_bgr(s_, src_width, src_height, halve ? 1 : 0, variant), ctx_);
     }
     void disableBgr() { check(mvsv_stream_disable_bgr(s_), ctx_); }
+    // the maps of the colour pairs pushed from now on come from StereoSGBM on the halved
+    // BGR pair itself, as cv::StereoSGBM matches CV_8UC3 (after enableBgr, no frame
+    // pending, SGBM only; a switch to StereoBM throws while it is on)
+    void bgrMatch(bool on = true) { check(mvsv_stream_set_bgr_match(s_, on ? 1 : 0), ctx_); }
     void pushBgr(const Mat& left, const Mat& right)
     {
         if (left.empty() || left.type != MAT_8UC3 || right.type != MAT_8UC3 || left.rows != right.rows ||

@@ -134,6 +134,15 @@ inline void check_pair(const Mat& L, const Mat& R)
                     "left.size() == right.size() && left.type() == right.type() && CV_8UC1");
 }
 
+// cv::StereoSGBM::compute's assert: one size, one type, depth CV_8U (1 or 3 channels)
+inline void check_sgbm_pair(const Mat& L, const Mat& R)
+{
+    if (L.empty() || L.rows != R.rows || L.cols != R.cols || L.type != R.type ||
+        (L.type != MAT_8UC1 && L.type != MAT_8UC3))
+        throw Error(MVSV_E_INVALID_ARG,
+                    "left.size() == right.size() && left.type() == right.type() && left.depth() == CV_8U");
+}
+
 class StereoSGBM {
 public:
     enum { MODE_SGBM = MVSV_MODE_SGBM, MODE_HH = MVSV_MODE_HH };
@@ -149,11 +158,18 @@ public:
                                 speckleRange, mode);
         return m;
     }
+    // CV_8UC1 pairs, or CV_8UC3 pairs matched in colour (the BT cost summed over the channels)
     void compute(const Mat& left, const Mat& right, Mat& disparity)
     {
-        check_pair(left, right);
+        check_sgbm_pair(left, right);
         disparity.create(left.rows, left.cols, MAT_16SC1);
         mvsv_ctx* c = thread_context();
+        if (left.type == MAT_8UC3) {
+            check(mvsv_sgbm_bgr(c, left.data, left.step, right.data, right.step, left.cols, left.rows, &p,
+                                reinterpret_cast<int16_t*>(disparity.data), disparity.step / 2),
+                  c);
+            return;
+        }
         check(mvsv_sgbm(c, left.data, left.step, right.data, right.step, left.cols, left.rows, &p,
                         reinterpret_cast<int16_t*>(disparity.data), disparity.step / 2),
               c);

@@ -149,6 +149,10 @@ def _declare(lib, strict=True):
         "mvsv_bm_device": ([P, I, P, Z, Z, P, Z, Z, I, I, P, P, Z, Z], I),
         "mvsv_sgbm_workspace_bytes": ([I, I, I, P], Z),
         "mvsv_sgbm_plan": ([P, I, I, I, P, P], I),
+        "mvsv_sgbm_bgr": ([P, P, Z, P, Z, I, I, P, P, Z], I),
+        "mvsv_sgbm_bgr_device": ([P, I, P, Z, Z, P, Z, Z, I, I, P, P, Z, Z], I),
+        "mvsv_sgbm_workspace_bytes_cn": ([I, I, I, P, I], Z),
+        "mvsv_sgbm_plan_cn": ([P, I, I, I, P, I, P], I),
         "mvsv_mean_disparity_grid_device": ([P, I, P, Z, Z, I, I, P], I),
         "mvsv_load_sgbm_yaml": ([ctypes.c_char_p, P, P], I),
         "mvsv_load_bm_yaml": ([ctypes.c_char_p, P], I),
@@ -226,6 +230,7 @@ def _declare(lib, strict=True):
         "mvsv_stream_matcher": ([P], I),
         "mvsv_stream_enable_bgr": ([P, I, I, I, I], I),
         "mvsv_stream_disable_bgr": ([P], I),
+        "mvsv_stream_set_bgr_match": ([P, I], I),
         "mvsv_stream_push_bgr": ([P, P, Z, P, Z], I),
         "mvsv_stream_push_device": ([P, I, P, Z, Z, P, Z, Z, P], I),
         "mvsv_stream_push_raw_device": ([P, I, P, Z, Z, P, Z, Z, P], I),
@@ -378,9 +383,14 @@ def profile_read(ctx: Context) -> dict:
 PLAN_BITSLICE, PLAN_SIDE, PLAN_STRIPS, PLAN_RESIDUAL = 1, 2, 4, 8
 
 
-def sgbm_plan(ctx, n, width, height, params) -> int:
+def sgbm_plan(ctx, n, width, height, params, channels=1) -> int:
     """MVSV_PLAN_* bits of the pipeline ``ctx`` runs for an SGBM call of this
-    shape (mvsv_sgbm_plan): bit-sliced, side by side / strips, residual plane."""
+    shape (mvsv_sgbm_plan): bit-sliced, side by side / strips, residual plane.
+    channels=3: a colour (BGR) launch (mvsv_sgbm_plan_cn)."""
     out = ctypes.c_int(0)
-    check(lib().mvsv_sgbm_plan(ctx.handle, n, width, height, ctypes.byref(params), ctypes.byref(out)), ctx.handle)
+    if channels == 1:
+        check(lib().mvsv_sgbm_plan(ctx.handle, n, width, height, ctypes.byref(params), ctypes.byref(out)), ctx.handle)
+    else:
+        check(lib().mvsv_sgbm_plan_cn(ctx.handle, n, width, height, ctypes.byref(params), int(channels),
+                                      ctypes.byref(out)), ctx.handle)
     return out.value

@@ -1122,8 +1122,9 @@ __global__ __launch_bounds__(128) void bsgm_fixup_col0_kernel(uint32_t* __restri
 bool bsgm_eligible(const mvsv_ctx* ctx, const SgbmEff& e, int n, int H)
 {
     const long bs = 2L * e.SW2 + 1;
-    const bool no_wrap = (long)e.P2 + bs * bs * (2L * e.ftzero + 63) + e.P2 <= 32767;
-    return ctx->opt.bitslice && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && no_wrap &&
+    const bool no_wrap = (long)e.P2 + bs * bs * e.cn * (2L * e.ftzero + 63) + e.P2 <= 32767;
+    // (the C' planes come from the register-ring cost kernel: grey pairs only)
+    return e.cn == 1 && ctx->opt.bitslice && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && no_wrap &&
            e.W1 > 0 && (size_t)n * H * bs::padq(e.W1) * 16 < ((size_t)1 << 31);
 }
 

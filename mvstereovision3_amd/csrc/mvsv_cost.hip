@@ -79,6 +79,63 @@ __global__ __launch_bounds__(256) void sgbm_prefilter_kernel(
     }
 }
 
+// 1b. prefilter of an interleaved 3-channel (BGR) pair, as calcPixelCostBT with
+//     cn == 3 prepares it: every colour channel c gives the same two planes as
+//     above (x-Sobel of that channel alone; the channel's byte, columns 0 and
+//     W - 1 = ftzero), in the same u64 format, planes [frame][2][3][H][W].
+// The three source rows (3 W bytes each) go through LDS with byte-contiguous
+// loads, so the 3-byte pixel stride is only ever an LDS stride.
+__global__ __launch_bounds__(256) void sgbm_prefilter_bgr_kernel(
+    const uint8_t* __restrict__ L, size_t ls, size_t lfs, const uint8_t* __restrict__ R,
+    size_t rs, size_t rfs, int W, int H, int ftzero, uint64_t* __restrict__ pre)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int W3 = 3 * W;
+    uint8_t* sn = smem;          // rows yn, y, ys: [3][3 W] interleaved
+    uint8_t* s0 = smem + W3;
+    uint8_t* ss = smem + 2 * W3;
+    uint8_t* ch = smem + 3 * W3;  // [3][2][W]: channel c sobel, channel c raw
+    const int y = blockIdx.x;
+    const int img = blockIdx.y;  // 0 = left, 1 = right
+    const int f = blockIdx.z;
+    const uint8_t* base = img == 0 ? L + f * lfs : R + f * rfs;
+    const size_t st = img == 0 ? ls : rs;
+    const int yn = y > 0 ? y - 1 : y, ys = y < H - 1 ? y + 1 : y;
+    const uint8_t* r0 = base + (size_t)y * st;
+    const uint8_t* rn = base + (size_t)yn * st;
+    const uint8_t* rsr = base + (size_t)ys * st;
+    const uint8_t fz = (uint8_t)ftzero;
+    for (int i = threadIdx.x; i < W3; i += blockDim.x) {
+        sn[i] = rn[i];
+        s0[i] = r0[i];
+        ss[i] = rsr[i];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < W3; i += blockDim.x) {
+        const int x = i / 3, c = i - 3 * x;
+        uint8_t a = fz, b = fz;
+        if (x > 0 && x < W - 1) {
+            int g = (s0[i + 3] - s0[i - 3]) * 2 + sn[i + 3] - sn[i - 3] + ss[i + 3] - ss[i - 3];
+            a = (uint8_t)(clampi(g, -ftzero, ftzero) + ftzero);
+            b = s0[i];
+        }
+        ch[(2 * c) * W + x] = a;
+        ch[(2 * c + 1) * W + x] = b;
+    }
+    __syncthreads();
+    uint64_t* o = pre + ((((size_t)f * 2 + img) * 3) * H + y) * W;
+    for (int i = threadIdx.x; i < W3; i += blockDim.x) {
+        const int c = i / W, x = i - c * W;  // plane-major: contiguous stores
+        const uint8_t* c0 = ch + (2 * c) * W;
+        const uint8_t* c1 = c0 + W;
+        const bool hl = x > 0, hr = x < W - 1;
+        const int xl = hl ? x - 1 : x, xr = hr ? x + 1 : x;
+        uint32_t v0 = bt_interval(c0[x], c0[xl], c0[xr], hl, hr);
+        uint32_t v1 = bt_interval(c1[x], c1[xl], c1[xr], hl, hr);
+        o[(size_t)c * H * W + x] = (uint64_t)v0 | ((uint64_t)v1 << 32);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // 2. cost volume.
 // Block = 256 threads owns cost columns [x0, x0+TX) x rows [y0, y0+TY) x all d.
@@ -92,6 +149,10 @@ __global__ __launch_bounds__(256) void sgbm_prefilter_kernel(
 //   hsum   horizontal box sum, sliding along the thread's run of RUN columns;
 //   vsum   vertical window sum kept in registers, the last 2*SH2+1 horizontal
 //          sums in an LDS ring; emit C = P2 + window sum (u16 wrap = int16 cast).
+// CN = 3 (interleaved BGR pairs, planes [frame][2][3][H][W]): a source row is
+// staged and BT-costed once per colour channel and the channels' costs are
+// summed in the pixel-cost row (<= 3 * 189 per u16 half) before the row enters
+// the box sums -- calcPixelCostBT's cn == 3; everything after pix is shared.
 // ---------------------------------------------------------------------------
 constexpr int kCostRun = 4;  // output columns per thread
 
@@ -150,6 +211,7 @@ __device__ __forceinline__ uint32_t bt_pair(uint32_t u, uint32_t u0, uint32_t u1
 
 constexpr int kStageRegs = 3;  // staging loads per thread per row (nL + nR + 1 <= 768)
 
+template <int CN>
 __global__ __launch_bounds__(256) void sgbm_cost_kernel(const uint64_t* __restrict__ pre, int W,
                                                         int H, SgbmEff e, int TY,
                                                         int16_t* __restrict__ C)
@@ -173,8 +235,8 @@ __global__ __launch_bounds__(256) void sgbm_cost_kernel(const uint64_t* __restri
     uint32_t* pixrow = (uint32_t*)(smem + lay.off_pix);
     uint32_t* ring = (uint32_t*)(smem + lay.off_ring);
     const size_t plane = (size_t)W * H;
-    const uint64_t* PL = pre + (size_t)f * 2 * plane;
-    const uint64_t* PR = PL + plane;
+    const uint64_t* PL = pre + (size_t)f * 2 * CN * plane;
+    const uint64_t* PR = PL + CN * plane;
     const int tid = threadIdx.x;
     const int cl = tid / PP, p = tid - (tid / PP) * PP;
     const bool worker = cl < CL;
@@ -188,10 +250,10 @@ __global__ __launch_bounds__(256) void sgbm_cost_kernel(const uint64_t* __restri
     for (int i = 0; i < kCostRun; i++) csum[i] = 0;
     uint64_t pf[kStageRegs];
 
-    auto fetch_row = [&](int v) {
+    auto fetch_row = [&](int v, int c) {
         const int r = clampi(v, 0, H - 1);
-        const uint64_t* lrow = PL + (size_t)r * W;
-        const uint64_t* rrow = PR + (size_t)r * W;
+        const uint64_t* lrow = PL + c * plane + (size_t)r * W;
+        const uint64_t* rrow = PR + c * plane + (size_t)r * W;
 #pragma unroll
         for (int k = 0; k < kStageRegs; k++) {
             const int i = tid + 256 * k;
@@ -220,47 +282,53 @@ __global__ __launch_bounds__(256) void sgbm_cost_kernel(const uint64_t* __restri
     };
 
     const int vstart = y0 - SH2, vend = y1 + SH2;
-    fetch_row(vstart);
+    fetch_row(vstart, 0);
     stage_row();
     for (int v = vstart; v < vend; v++) {
-        __syncthreads();  // staging of row v visible; hsum of row v-1 done with pixrow
-        if (v + 1 < vend) fetch_row(v + 1);  // in flight during the pixel-cost phase
-        if (worker) {
-            for (int xv = cl; xv < NX; xv += CL) {
-                const int xc = clampi(x0 - SW2 + xv, 0, W1 - 1);
-                const uint64_t lw = lpk[xc - xclo];
-                const uint32_t l0 = (uint32_t)lw, l1 = (uint32_t)(lw >> 32);
-                // j of d = 2p at this column
-                const int j0 = (xchi - xc) + 2 * p;
-                const uint64_t* src = (j0 & 1) ? (rb + (j0 - 1)) : (ra + j0);
-                const uint4 rr = *(const uint4*)src;  // cols j0, j0+1 (both channels)
-                uint32_t acc;
-                {
-                    const uint32_t a = rr.x, b = rr.z;  // channel 0 of d, d+1
-                    uint32_t U = __builtin_amdgcn_perm(l0, l0, 0x0c040c00u);
-                    uint32_t U0 = __builtin_amdgcn_perm(l0, l0, 0x0c050c01u);
-                    uint32_t U1 = __builtin_amdgcn_perm(l0, l0, 0x0c060c02u);
-                    uint32_t V = __builtin_amdgcn_perm(b, a, 0x0c040c00u);
-                    uint32_t V0 = __builtin_amdgcn_perm(b, a, 0x0c050c01u);
-                    uint32_t V1 = __builtin_amdgcn_perm(b, a, 0x0c060c02u);
-                    acc = bt_pair(U, U0, U1, V, V0, V1);
+#pragma unroll
+        for (int c = 0; c < CN; c++) {
+            const bool more = c + 1 < CN || v + 1 < vend;  // another (row, channel) to stage
+            __syncthreads();  // staging of (v, c) visible; hsum of row v-1 done with pixrow
+            if (more) fetch_row(c + 1 < CN ? v : v + 1, c + 1 < CN ? c + 1 : 0);  // in flight during the pixel-cost phase
+            if (worker) {
+                for (int xv = cl; xv < NX; xv += CL) {
+                    const int xc = clampi(x0 - SW2 + xv, 0, W1 - 1);
+                    const uint64_t lw = lpk[xc - xclo];
+                    const uint32_t l0 = (uint32_t)lw, l1 = (uint32_t)(lw >> 32);
+                    // j of d = 2p at this column
+                    const int j0 = (xchi - xc) + 2 * p;
+                    const uint64_t* src = (j0 & 1) ? (rb + (j0 - 1)) : (ra + j0);
+                    const uint4 rr = *(const uint4*)src;  // cols j0, j0+1 (both channels)
+                    uint32_t acc;
+                    {
+                        const uint32_t a = rr.x, b = rr.z;  // channel 0 of d, d+1
+                        uint32_t U = __builtin_amdgcn_perm(l0, l0, 0x0c040c00u);
+                        uint32_t U0 = __builtin_amdgcn_perm(l0, l0, 0x0c050c01u);
+                        uint32_t U1 = __builtin_amdgcn_perm(l0, l0, 0x0c060c02u);
+                        uint32_t V = __builtin_amdgcn_perm(b, a, 0x0c040c00u);
+                        uint32_t V0 = __builtin_amdgcn_perm(b, a, 0x0c050c01u);
+                        uint32_t V1 = __builtin_amdgcn_perm(b, a, 0x0c060c02u);
+                        acc = bt_pair(U, U0, U1, V, V0, V1);
+                    }
+                    {
+                        const uint32_t a = rr.y, b = rr.w;  // channel 1 (raw) of d, d+1
+                        uint32_t U = __builtin_amdgcn_perm(l1, l1, 0x0c040c00u);
+                        uint32_t U0 = __builtin_amdgcn_perm(l1, l1, 0x0c050c01u);
+                        uint32_t U1 = __builtin_amdgcn_perm(l1, l1, 0x0c060c02u);
+                        uint32_t V = __builtin_amdgcn_perm(b, a, 0x0c040c00u);
+                        uint32_t V0 = __builtin_amdgcn_perm(b, a, 0x0c050c01u);
+                        uint32_t V1 = __builtin_amdgcn_perm(b, a, 0x0c060c02u);
+                        uint32_t cr = bt_pair(U, U0, U1, V, V0, V1);
+                        acc = pk_add_u16(acc, (cr >> 2) & 0x3fff3fffu);
+                    }
+                    // (the word is this thread's own for every colour channel of the row)
+                    if (c > 0) acc = pk_add_u16(acc, pixrow[xv * PP + p]);
+                    pixrow[xv * PP + p] = acc;
                 }
-                {
-                    const uint32_t a = rr.y, b = rr.w;  // channel 1 (raw) of d, d+1
-                    uint32_t U = __builtin_amdgcn_perm(l1, l1, 0x0c040c00u);
-                    uint32_t U0 = __builtin_amdgcn_perm(l1, l1, 0x0c050c01u);
-                    uint32_t U1 = __builtin_amdgcn_perm(l1, l1, 0x0c060c02u);
-                    uint32_t V = __builtin_amdgcn_perm(b, a, 0x0c040c00u);
-                    uint32_t V0 = __builtin_amdgcn_perm(b, a, 0x0c050c01u);
-                    uint32_t V1 = __builtin_amdgcn_perm(b, a, 0x0c060c02u);
-                    uint32_t c = bt_pair(U, U0, U1, V, V0, V1);
-                    acc = pk_add_u16(acc, (c >> 2) & 0x3fff3fffu);
-                }
-                pixrow[xv * PP + p] = acc;
             }
+            __syncthreads();  // pixrow of (v, c) complete; staging buffers free
+            if (more) stage_row();
         }
-        __syncthreads();  // pixrow complete; staging buffers free
-        if (v + 1 < vend) stage_row();
         if (worker) {
             const int k = v - vstart;
             const int slot = k % NR;
@@ -838,7 +906,8 @@ int launch_cost(mvsv_ctx* ctx, int n, int W, int H, const SgbmEff& e, int TY,
     *pinned_hh = false;
     hipStream_t s = ctx->stream;
     int rc;
-    if (ctx->opt.cost2 && e.SH2 <= 7 && e.SW2 == e.SH2) {
+    // (colour pairs, e.cn == 3: always the LDS-ring kernel, which sums the channels)
+    if (e.cn == 1 && ctx->opt.cost2 && e.SH2 <= 7 && e.SW2 == e.SH2) {
         const Cost2Layout l2 = cost2_layout(e.D, e.SW2, TY);
         const int items = 2 * l2.NX + e.D - 1;
         const bool two = items > kCost2Threads;
@@ -874,22 +943,23 @@ int launch_cost(mvsv_ctx* ctx, int n, int W, int H, const SgbmEff& e, int TY,
     if (lay.bytes > 160 * 1024)
         return set_error(ctx, MVSV_E_INVALID_ARG, "blockSize too large for the GPU cost kernel");
     dim3 cgrid((e.W1 + lay.TX - 1) / lay.TX, (H + TY - 1) / TY, n);
+    auto kern = e.cn == 3 ? sgbm_cost_kernel<3> : sgbm_cost_kernel<1>;
     if (lay.bytes > 65536 &&
-        (rc = check_hip(ctx, hipFuncSetAttribute((const void*)sgbm_cost_kernel,
+        (rc = check_hip(ctx, hipFuncSetAttribute((const void*)kern,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)lay.bytes),
                         "sgbm cost LDS attribute")))
         return rc;
     {
         StageTimer tm(ctx, kStageCost);
-        hipLaunchKernelGGL(sgbm_cost_kernel, cgrid, dim3(256), lay.bytes, s, pre, W, H, e, TY, Cv);
+        hipLaunchKernelGGL(kern, cgrid, dim3(256), lay.bytes, s, pre, W, H, e, TY, Cv);
     }
     return check_hip(ctx, hipGetLastError(), "sgbm cost kernel");
 }
 
 bool cost2_runs(const mvsv_ctx* ctx, const SgbmEff& e)
 {
-    if (!ctx->opt.cost2 || e.SH2 > 7 || e.SW2 != e.SH2) return false;
+    if (e.cn != 1 || !ctx->opt.cost2 || e.SH2 > 7 || e.SW2 != e.SH2) return false;
     const Cost2Layout l2 = cost2_layout(e.D, e.SW2, 120);  // (the layout does not depend on the tile height)
     const int items = 2 * l2.NX + e.D - 1;
     const int ppc = !ctx->opt.cost_fixed_pp ? 0 : l2.PP == 64 ? 64 : (l2.PP == 128 ? 128 : 0);
@@ -898,8 +968,23 @@ bool cost2_runs(const mvsv_ctx* ctx, const SgbmEff& e)
 }
 
 int launch_prefilter(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R, size_t rs,
-                     size_t rfs, int W, int H, int ftzero, uint64_t* pre)
+                     size_t rfs, int W, int H, int ftzero, int cn, uint64_t* pre)
 {
+    if (cn == 3) {
+        // three interleaved source rows + the six planes of the row
+        const size_t lbytes = (size_t)W * 15;
+        if (lbytes > 160 * 1024) return set_error(ctx, MVSV_E_INVALID_ARG, "colour pair too wide for the GPU prefilter");
+        int rc;
+        if (lbytes > 65536 &&
+            (rc = check_hip(ctx, hipFuncSetAttribute((const void*)sgbm_prefilter_bgr_kernel,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lbytes),
+                            "sgbm prefilter LDS attribute")))
+            return rc;
+        StageTimer tm(ctx, kStagePre);
+        hipLaunchKernelGGL(sgbm_prefilter_bgr_kernel, dim3(H, 2, n), dim3(256), lbytes, ctx->stream, L, ls, lfs, R,
+                           rs, rfs, W, H, ftzero, pre);
+        return check_hip(ctx, hipGetLastError(), "sgbm prefilter");
+    }
     StageTimer tm(ctx, kStagePre);
     hipLaunchKernelGGL(sgbm_prefilter_kernel, dim3(H, 2, n), dim3(256), (size_t)W * 2, ctx->stream, L, ls, lfs, R,
                        rs, rfs, W, H, ftzero, pre);

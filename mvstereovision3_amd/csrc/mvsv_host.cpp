@@ -160,6 +160,7 @@ int resolve_sgbm(const mvsv_sgbm_params* p, int W, int H, SgbmEff* e, std::strin
     e->variant = p->variant;
     e->speckle_window = p->speckle_window_size;
     e->speckle_diff = kDispScale * p->speckle_range;
+    e->cn = 1;
     if (e->W1 > 0 && e->W1 <= e->SW2) {
         *why = "image narrower than the SGBM block half-width (OpenCV reads uninitialised memory)";
         return MVSV_E_INVALID_ARG;
@@ -559,11 +560,12 @@ int mvsv_synchronize(mvsv_ctx* ctx)
     return rc ? rc : check_report(ctx);
 }
 
-size_t mvsv_sgbm_workspace_bytes(int n, int W, int H, const mvsv_sgbm_params* p)
+size_t mvsv_sgbm_workspace_bytes_cn(int n, int W, int H, const mvsv_sgbm_params* p, int cn)
 {
     SgbmEff e;
     std::string why;
-    if (n <= 0 || resolve_sgbm(p, W, H, &e, &why) != MVSV_OK) return 0;
+    if (n <= 0 || (cn != 1 && cn != 3) || resolve_sgbm(p, W, H, &e, &why) != MVSV_OK) return 0;
+    e.cn = cn;
     size_t frame = (size_t)W * H;
     size_t vol = e.W1 > 0 ? (size_t)e.W1 * H * e.D * 2 : 0;
     size_t b = (size_t)n * (frame * 4 + 2 * vol + frame * 2);
@@ -571,15 +573,15 @@ size_t mvsv_sgbm_workspace_bytes(int n, int W, int H, const mvsv_sgbm_params* p)
     // words, u16 local roots and the compact root list (+ its count)
     if (e.speckle_window > 0) b += (size_t)n * frame * (4 + 4 + 4 + 2 + 4) + 4;
     // cost residual plane + per-pixel minimum (MVSV_OPT_COST_RESIDUAL, where exact)
-    if (3 * e.P2 <= 15 && e.D <= 128 && e.W1 > 0) b += (size_t)n * e.W1 * H * (e.D / 2 + 2);
-    // the BT interval planes of both views (u64 per pixel each)
-    b += (size_t)n * frame * 16;
+    if (cn == 1 && 3 * e.P2 <= 15 && e.D <= 128 && e.W1 > 0) b += (size_t)n * e.W1 * H * (e.D / 2 + 2);
+    // the BT interval planes of both views (u64 per pixel and channel each)
+    b += (size_t)n * frame * 16 * cn;
     // the bit-sliced pipeline (MVSV_OPT_BITSLICE, default on):
     // rows padded to 4 pixels, delta planes beyond the accumulator budget above
     // (eight 48-byte planes side by side for small launches), strip boundary
     // granules (2 passes x strips of 64 U-columns x H rows x 36 u64)
     const long bsz = 2L * e.SW2 + 1;
-    const bool bs_regime = e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && e.W1 > 0 &&
+    const bool bs_regime = cn == 1 && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && e.W1 > 0 &&
                            (long)e.P2 + bsz * bsz * (2L * e.ftzero + 63) + e.P2 <= 32767;
     if (bs_regime) {
         const size_t W1q = (size_t)(e.W1 + 3) & ~(size_t)3;
@@ -599,29 +601,45 @@ size_t mvsv_sgbm_workspace_bytes(int n, int W, int H, const mvsv_sgbm_params* p)
     return b;
 }
 
-int mvsv_sgbm_plan(mvsv_ctx* ctx, int n, int W, int H, const mvsv_sgbm_params* p, int* plan)
+size_t mvsv_sgbm_workspace_bytes(int n, int W, int H, const mvsv_sgbm_params* p)
+{
+    return mvsv_sgbm_workspace_bytes_cn(n, W, H, p, 1);
+}
+
+int mvsv_sgbm_plan_cn(mvsv_ctx* ctx, int n, int W, int H, const mvsv_sgbm_params* p, int cn, int* plan)
 {
     if (!ctx || !plan || n <= 0) return MVSV_E_INVALID_ARG;
+    if (cn != 1 && cn != 3) return set_error(ctx, MVSV_E_INVALID_ARG, "channels must be 1 or 3");
     SgbmEff e;
     std::string why;
     const int rc = resolve_sgbm(p, W, H, &e, &why);
     if (rc) return set_error(ctx, rc, why);
+    e.cn = cn;
     *plan = sgbm_plan(ctx, e, n, H);
     return MVSV_OK;
 }
 
-int mvsv_sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs,
-                     const uint8_t* R, size_t rs, size_t rfs, int W, int H,
-                     const mvsv_sgbm_params* p, int16_t* out, size_t os, size_t ofs)
+int mvsv_sgbm_plan(mvsv_ctx* ctx, int n, int W, int H, const mvsv_sgbm_params* p, int* plan)
+{
+    return mvsv_sgbm_plan_cn(ctx, n, W, H, p, 1, plan);
+}
+
+}  // extern "C"
+
+// mvsv_sgbm_device (cn 1) / mvsv_sgbm_bgr_device (cn 3: W in pixels, rows of 3 W bytes)
+static int sgbm_device_call(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
+                            size_t rs, size_t rfs, int W, int H, const mvsv_sgbm_params* p, int16_t* out,
+                            size_t os, size_t ofs, int cn)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     if (n <= 0 || !L || !R || !out) return set_error(ctx, MVSV_E_INVALID_ARG, "null buffer or n <= 0");
-    if (ls < (size_t)W || rs < (size_t)W || os < (size_t)W)
+    if (ls < (size_t)W * cn || rs < (size_t)W * cn || os < (size_t)W)
         return set_error(ctx, MVSV_E_INVALID_ARG, "stride smaller than width");
     SgbmEff e;
     std::string why;
     int rc = resolve_sgbm(p, W, H, &e, &why);
     if (rc) return set_error(ctx, rc, why);
+    e.cn = cn;
     // an earlier launch that has finished by now gave up a strip wait: its
     // maps are INVALID; say so before anything else runs on this context
     if ((rc = check_report(ctx))) return rc;
@@ -648,6 +666,22 @@ int mvsv_sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t l
         return mark_last_use(ctx, graph_run(ctx, key, body));
     }
     return mark_last_use(ctx, body());
+}
+
+extern "C" {
+
+int mvsv_sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs,
+                     const uint8_t* R, size_t rs, size_t rfs, int W, int H,
+                     const mvsv_sgbm_params* p, int16_t* out, size_t os, size_t ofs)
+{
+    return sgbm_device_call(ctx, n, L, ls, lfs, R, rs, rfs, W, H, p, out, os, ofs, 1);
+}
+
+int mvsv_sgbm_bgr_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs,
+                         const uint8_t* R, size_t rs, size_t rfs, int W, int H,
+                         const mvsv_sgbm_params* p, int16_t* out, size_t os, size_t ofs)
+{
+    return sgbm_device_call(ctx, n, L, ls, lfs, R, rs, rfs, W, H, p, out, os, ofs, 3);
 }
 
 int mvsv_bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs,
@@ -877,13 +911,14 @@ int mvsv_view(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, const
 }
 
 // Host-pointer path: stage through cached device buffers, run, copy back, sync.
+// cn: bytes per input pixel (3: mvsv_sgbm_bgr)
 static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs,
-                     int W, int H, int16_t* out, size_t os, bool sgbm, const void* params)
+                     int W, int H, int16_t* out, size_t os, bool sgbm, const void* params, int cn = 1)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     if (!L || !R || !out || W <= 0 || H <= 0)
         return set_error(ctx, MVSV_E_INVALID_ARG, "null buffer or empty image");
-    if (ls < (size_t)W || rs < (size_t)W || os < (size_t)W)
+    if (ls < (size_t)W * cn || rs < (size_t)W * cn || os < (size_t)W)
         return set_error(ctx, MVSV_E_INVALID_ARG, "stride smaller than width");
     int rc;
     SgbmEff se;
@@ -892,6 +927,7 @@ static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* 
     rc = sgbm ? resolve_sgbm((const mvsv_sgbm_params*)params, W, H, &se, &why)
               : resolve_bm((const mvsv_bm_params*)params, W, H, &be, &why);
     if (rc) return set_error(ctx, rc, why);
+    if (sgbm) se.cn = cn;
     if (sgbm && (rc = check_report(ctx))) return rc;  // an earlier device call's give-up
     DeviceGuard dev_guard(ctx->device);
     // every exit after the first enqueue records the context's last-use event,
@@ -899,15 +935,16 @@ static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* 
     return mark_last_use(ctx, [&]() -> int {
     int rc;
     size_t fb = (size_t)W * H;
-    if ((rc = ensure(ctx, ctx->h_left, fb, "left staging"))) return rc;
-    if ((rc = ensure(ctx, ctx->h_right, fb, "right staging"))) return rc;
+    const size_t rb = (size_t)W * cn, ib = rb * H;  // input row / frame bytes
+    if ((rc = ensure(ctx, ctx->h_left, ib, "left staging"))) return rc;
+    if ((rc = ensure(ctx, ctx->h_right, ib, "right staging"))) return rc;
     if ((rc = ensure(ctx, ctx->h_out, fb * 2, "output staging"))) return rc;
     hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_left.ptr, W, L, ls, W, H, hipMemcpyHostToDevice, s), "H2D left"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_right.ptr, W, R, rs, W, H, hipMemcpyHostToDevice, s), "H2D right"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_left.ptr, rb, L, ls, rb, H, hipMemcpyHostToDevice, s), "H2D left"))) return rc;
+    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_right.ptr, rb, R, rs, rb, H, hipMemcpyHostToDevice, s), "H2D right"))) return rc;
     int16_t* dout = (int16_t*)ctx->h_out.ptr;
-    rc = sgbm ? sgbm_device(ctx, 1, (const uint8_t*)ctx->h_left.ptr, W, fb,
-                            (const uint8_t*)ctx->h_right.ptr, W, fb, W, H, se, dout, W, fb)
+    rc = sgbm ? sgbm_device(ctx, 1, (const uint8_t*)ctx->h_left.ptr, rb, ib,
+                            (const uint8_t*)ctx->h_right.ptr, rb, ib, W, H, se, dout, W, fb)
               : bm_device(ctx, 1, (const uint8_t*)ctx->h_left.ptr, W, fb,
                           (const uint8_t*)ctx->h_right.ptr, W, fb, W, H, be, dout, W, fb);
     if (rc) return rc;
@@ -923,6 +960,12 @@ int mvsv_sgbm(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size
               int H, const mvsv_sgbm_params* p, int16_t* out, size_t os)
 {
     return host_call(ctx, L, ls, R, rs, W, H, out, os, true, p);
+}
+
+int mvsv_sgbm_bgr(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs, int W,
+                  int H, const mvsv_sgbm_params* p, int16_t* out, size_t os)
+{
+    return host_call(ctx, L, ls, R, rs, W, H, out, os, true, p, 3);
 }
 
 int mvsv_bm(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs, int W,

@@ -29,6 +29,9 @@ struct SgbmEff {
     int fullDP;   // MODE_HH
     int variant;
     int speckle_window, speckle_diff;  // speckle_diff = 16 * speckleRange
+    // colour channels of the pair: 1 (grey; resolve_sgbm) or 3 (interleaved BGR,
+    // set by the colour entry points).  A pixel cost is <= cn * (2*ftzero + 63).
+    int cn;
 };
 
 struct BmEff {
@@ -223,7 +226,8 @@ struct StageTimer {
 };
 
 // Device pipelines (defined in the .hip translation units). All enqueue on
-// ctx->stream. Strides are in elements.
+// ctx->stream. Strides are in elements (sgbm_device with e.cn == 3: W in pixels,
+// input strides in bytes, rows of 3 W interleaved bytes).
 int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
                 size_t rs, size_t rfs, int W, int H, const SgbmEff& e, int16_t* out, size_t os,
                 size_t ofs);
@@ -242,7 +246,7 @@ int bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, con
 // planes *Bv where given and possible -- each is set to nullptr otherwise), and
 // OpenCV 3.4's cost-row quirks on the int16 volume.
 int launch_prefilter(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R, size_t rs,
-                     size_t rfs, int W, int H, int ftzero, uint64_t* pre);
+                     size_t rfs, int W, int H, int ftzero, int cn, uint64_t* pre);
 int launch_cost(mvsv_ctx* ctx, int n, int W, int H, const SgbmEff& e, int TY, const uint64_t* pre, int16_t* Cv,
                 uint8_t** Rv, uint16_t* Mv, bool* pinned_hh, uint32_t** Bv);
 int launch_cost_fixup(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, int16_t* Cv, uint8_t* Rv, uint16_t* Mv);
@@ -284,6 +288,10 @@ int resize_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sf
 int prepare_size(int sw, int sh, int halve, int* dw, int* dh);
 int prepare_gray_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t ss, size_t sfs, int sw, int sh, int halve,
                         int variant, uint8_t* dst, size_t ds, size_t dfs);
+// The INTER_AREA half of prepare_gray_device alone, per channel: interleaved BGR in,
+// interleaved BGR of mvsv_prepare_size(sw, sh, 1) out (the colour-matched stream frames)
+int halve_bgr_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t ss, size_t sfs, int sw, int sh, uint8_t* dst,
+                     size_t ds, size_t dfs);
 // The frame stream's device push (mvsv_prepare.hip): rows of row_bytes bytes of both
 // sides of n frames (strides in bytes) into dL / dR, which share ds / dfs; one launch
 // on `stream`.  The pointers must be readable / writable by the device.

@@ -121,6 +121,23 @@ __global__ __launch_bounds__(256) void bgr_gray_kernel(const uint8_t* __restrict
     }
 }
 
+// The halving alone, for the frames a stream matches in colour: a lane per output
+// byte (consecutive lanes, consecutive bytes of an interleaved row), each from its
+// channel's 2 x 2 block by halve_narrow's rules.
+__global__ __launch_bounds__(256) void bgr_halve_kernel(const uint8_t* __restrict__ src, size_t ss, size_t sfs, int sw,
+                                                        int sh, uint8_t* __restrict__ dst, size_t ds, size_t dfs,
+                                                        int dw, int dh)
+{
+    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int f = blockIdx.z;
+    if (b >= 3 * dw || y >= dh) return;
+    const int x = b / 3, c = b - 3 * x;
+    int v = 0;
+    if (2 * x < sw && 2 * y < sh) v = halve_narrow(src + f * sfs, ss, sw, sh, 2 * x, 2 * y, c);
+    dst[f * dfs + (size_t)y * ds + b] = (uint8_t)v;
+}
+
 // The frame stream's device push (mvsv_stream_push_device): rows of row_bytes bytes
 // of both sides of n frames, from the caller's buffers into consecutive slots.
 // blockIdx.z = 2 * frame + side; a block is 64 units of 4 rows.  A wide side moves
@@ -186,6 +203,19 @@ int prepare_size(int sw, int sh, int halve, int* dw, int* dh)
     *dw = sw;
     *dh = sh;
     return MVSV_OK;
+}
+
+int halve_bgr_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t ss, size_t sfs, int sw, int sh, uint8_t* dst,
+                     size_t ds, size_t dfs)
+{
+    int dw, dh;
+    if (n < 1 || prepare_size(sw, sh, 1, &dw, &dh))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad prepare size or factor");
+    if (ss < 3 * (size_t)sw || ds < 3 * (size_t)dw)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "prepare stride smaller than the row");
+    dim3 grid((3 * dw + 63) / 64, (dh + 3) / 4, n);
+    hipLaunchKernelGGL(bgr_halve_kernel, grid, dim3(256), 0, ctx->stream, bgr, ss, sfs, sw, sh, dst, ds, dfs, dw, dh);
+    return check_hip(ctx, hipGetLastError(), "halve bgr");
 }
 
 int prepare_gray_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t ss, size_t sfs, int sw, int sh, int halve,

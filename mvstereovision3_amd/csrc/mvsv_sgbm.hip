@@ -2169,7 +2169,7 @@ void launch_final16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const 
                            ctx->stream, Cv, Av, plane, H, W, e, raw, keys, dummy, nullptr, nullptr);
 }
 
-// Every cost C = P2 + (box sum of blockSize^2 BT costs, each <= 2*ftzero + 63),
+// Every cost C = P2 + (box sum of blockSize^2 BT costs, each <= cn * (2*ftzero + 63)),
 // every L <= C and delta = minLp + P2: when that bound stays <= 32767 nothing
 // wraps in int16 and the path kernels may use the NW recurrence (sgm_pair).
 // The split side-by-side form (sgbm_wta_planes_kernel): byte / u16 planes,
@@ -2186,7 +2186,7 @@ static bool wta_split(const mvsv_ctx* ctx, const SgbmEff& e)
 static bool sgbm_no_wrap(const SgbmEff& e)
 {
     const long bs = 2L * e.SW2 + 1;
-    return (long)e.P2 + bs * bs * (2L * e.ftzero + 63) + e.P2 <= 32767;
+    return (long)e.P2 + bs * bs * e.cn * (2L * e.ftzero + 63) + e.P2 <= 32767;
 }
 
 // The direction passes read the residual plane (see its definition above)
@@ -2195,7 +2195,8 @@ static bool sgbm_no_wrap(const SgbmEff& e)
 // D <= 128 (one cost kernel wave segment holds a pixel's D costs).
 static bool use_residual(const mvsv_ctx* ctx, const SgbmEff& e, int sched)
 {
-    return ctx->opt.cost_res && (sched == 1 || sched == 2) && sgbm_no_wrap(e) && 3 * e.P2 <= 15 &&
+    // (written by the register-ring cost kernel only: grey pairs)
+    return e.cn == 1 && ctx->opt.cost_res && (sched == 1 || sched == 2) && sgbm_no_wrap(e) && 3 * e.P2 <= 15 &&
            (e.D == 32 || e.D == 64 || e.D == 128);
 }
 
@@ -2703,7 +2704,7 @@ int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, c
     if (e.D > 512) return set_error(ctx, MVSV_E_INVALID_ARG, "numDisparities > 512 not supported");
     const size_t plane = (size_t)W * H;
     const size_t vol = (size_t)e.W1 * H * e.D;
-    if ((rc = ensure(ctx, ctx->pre, (size_t)n * 2 * plane * 8, "sgbm BT interval planes"))) return rc;
+    if ((rc = ensure(ctx, ctx->pre, (size_t)n * 2 * e.cn * plane * 8, "sgbm BT interval planes"))) return rc;
     // (rows padded to a multiple of 4 pixels: the bit-sliced pipeline's layout)
     if ((rc = ensure(ctx, ctx->cost, (size_t)n * H * ((e.W1 + 3) & ~3) * e.D * 2, "sgbm cost volume"))) return rc;
     // bit-sliced MODE_HH paths (round 5, mvsv_bsgm.hip): the cost kernel writes
@@ -2750,7 +2751,7 @@ int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, c
     int16_t* raw = (int16_t*)ctx->raw.ptr;
     const unsigned epoch0 = ctx->tri_epoch;
 
-    if ((rc = launch_prefilter(ctx, n, L, ls, lfs, R, rs, rfs, W, H, e.ftzero, pre))) return rc;
+    if ((rc = launch_prefilter(ctx, n, L, ls, lfs, R, rs, rfs, W, H, e.ftzero, e.cn, pre))) return rc;
 
     // cost volume: one block per TX x TY tile; keep the LDS image <= 160 KiB
     // Taller tiles re-read fewer halo rows (2*SH2 per tile); shorter ones give

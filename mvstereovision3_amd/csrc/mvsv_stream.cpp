@@ -38,6 +38,9 @@
 // With mvsv_stream_enable_bgr, a stream of rectified pairs also takes interleaved
 // BGR pairs (mvsv_stream_push_bgr): uploaded once as BGR, halved and converted to
 // grey into the slot's dL / dR ahead of the matcher (disparityTest.cpp:201-211).
+// With mvsv_stream_set_bgr_match the map of such a frame comes from SGBM on the
+// halved BGR pair itself (cv::StereoSGBM matches CV_8UC3 pairs in colour), in
+// launches that hold no grey-matched frame.
 // With mvsv_stream_push_device (and its raw / BGR forms), frames come from device
 // memory: one copy kernel per contiguous piece of the ring puts them into the
 // slots, ordered against the producer's stream by events; set_host_outputs drops
@@ -246,6 +249,11 @@ struct Bgr {
     int W = 0, H = 0, halve = 0, variant = 0;
     DevArray<uint8_t> dev;      // [depth] pairs in kPushBgr's geometry
     PinnedArray<uint8_t> host;  // the same, staged
+    // colour matching (mvsv_stream_set_bgr_match): a BGR frame's map comes from the
+    // colour matcher on the pair at the stream's size -- the halved pair in `half`
+    // ([depth][2][H][3 W]), or the staged pair itself without halving
+    bool match = false;
+    DevArray<uint8_t> half;
 };
 
 struct mvsv_stream {
@@ -272,6 +280,7 @@ struct mvsv_stream {
         int16_t* dOut = nullptr;
         float* dMeans = nullptr;
         bool is_bgr = false;  // the pending frame was pushed as BGR (written by every push)
+        bool colour = false;  // ... and is matched in colour (bgr.match at its push)
         Event uploaded, computed, done;
         Event released;                // pop_device's copy of dOut on the consumer's stream
         bool release_pending = false;  // the slot's next launch waits for `released`
@@ -562,6 +571,42 @@ static int stream_prepare(mvsv_stream* st, mvsv_ctx* ctx, long i0, int n)
     return MVSV_OK;
 }
 
+// The map of the colour-matched frames of a run (all of it: pushes keep the two kinds
+// of frames in launches of their own): mvsv_sgbm_bgr_device's pipeline on the BGR
+// pair at the stream's size.
+static int stream_match_colour(mvsv_stream* st, mvsv_ctx* ctx, long i0, int n)
+{
+    const int W = st->W, H = st->H;
+    const size_t px = (size_t)W * H;
+    const PushGeom g = st->push_geom(kPushBgr);
+    const Bgr& b = st->bgr;
+    auto& first = st->slots[i0];
+    SgbmEff e = st->eff;
+    e.cn = 3;
+    const uint8_t* pair = b.dev + (size_t)i0 * g.frame;
+    if (!b.halve)
+        return sgbm_device(ctx, n, pair, g.stride, g.frame, pair + g.right, g.stride, g.frame, W, H, e, first.dOut,
+                           W, px);
+    const size_t row = 3 * (size_t)W, side = row * H;
+    uint8_t* half = b.half + (size_t)i0 * 2 * side;
+    int rc;
+    if ((rc = halve_bgr_device(ctx, n, pair, g.stride, g.frame, b.W, b.H, half, row, 2 * side)) ||
+        (rc = halve_bgr_device(ctx, n, pair + g.right, g.stride, g.frame, b.W, b.H, half + side, row, 2 * side)))
+        return rc;
+    return sgbm_device(ctx, n, half, row, 2 * side, half + side, row, 2 * side, W, H, e, first.dOut, W, px);
+}
+
+// A frame-batch launch holds frames of one kind of matching: a frame that is matched
+// in colour where the pending ones are not, or the reverse, sends those off first,
+// as a change of matcher or parameters does.
+static int stream_launch(mvsv_stream* st);
+static int stream_kind_boundary(mvsv_stream* st, bool colour)
+{
+    if (st->launched == st->head) return MVSV_OK;
+    const auto& prev = st->slots[(st->head - 1) % (long)st->slots.size()];
+    return prev.colour == colour ? MVSV_OK : stream_launch(st);
+}
+
 // Enqueue compute + download for the pushed frames [launched, head): one
 // frame-batch launch per run of consecutive slots (a run ends at the ring's end).
 static int stream_launch(mvsv_stream* st)
@@ -596,6 +641,8 @@ static int stream_launch(mvsv_stream* st)
         if (status == MVSV_OK)
             status = st->matcher == MVSV_MATCHER_BM
                          ? bm_device(ctx, n, first.dL, W, px, first.dR, W, px, W, H, st->bm_eff, first.dOut, W, px)
+                     : first.colour
+                         ? stream_match_colour(st, ctx, i0, n)
                          : sgbm_device(ctx, n, first.dL, W, px, first.dR, W, px, W, H, st->eff, first.dOut, W, px);
         ctx->report_target = prev_target;
         // the run's maps at a stage's ROI
@@ -750,6 +797,8 @@ int mvsv_stream_set_bm_params(mvsv_stream* st, const mvsv_bm_params* p)
     std::string why;
     int rc = resolve_bm(p, st->W, st->H, &e, &why);
     if (rc) return set_error(st->ctx, rc, why);
+    if (st->bgr.match)
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "colour matching is on: StereoBM takes grey pairs only");
     DeviceGuard dev_guard(st->ctx->device);
     if ((rc = stream_launch(st))) return rc;  // pending frames keep their matcher and parameters
     st->bm_params = *p;
@@ -859,6 +908,8 @@ static int stream_push_host(mvsv_stream* st, PushKind kind, const uint8_t* L, si
     if (ring_full(st->head, st->tail, depth))
         return set_error(ctx, MVSV_E_INVALID_ARG, "stream full: pop a frame first");
     DeviceGuard dev_guard(ctx->device);
+    const bool colour = kind == kPushBgr && st->bgr.match;
+    if ((rc = stream_kind_boundary(st, colour))) return rc;
     auto& s = st->slots[st->head % depth];
     const PushEnds e = push_ends(st, kind, g, st->head % depth);
     // the slot's previous frame was popped, so its copies and what read its device buffers are complete
@@ -875,6 +926,7 @@ static int stream_push_host(mvsv_stream* st, PushKind kind, const uint8_t* L, si
         (rc = check_hip(ctx, hipEventRecord(s.uploaded, st->up), "stream event")))
         return rc;
     if (kind != kPushRaw) s.is_bgr = kind == kPushBgr;
+    s.colour = colour;
     st->head++;
     // a full group, or a group that would otherwise wrap past the ring's end
     if (ring_launch_after_push(st->head, st->launched, st->batch, depth)) return stream_launch(st);
@@ -924,6 +976,24 @@ int mvsv_stream_enable_bgr(mvsv_stream* st, int sw, int sh, int halve, int varia
     return MVSV_OK;
 }
 
+int mvsv_stream_set_bgr_match(mvsv_stream* st, int on)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (!st->bgr.on) return set_error(ctx, MVSV_E_INVALID_ARG, "colour input is not enabled on this stream");
+    if (int rc = idle_check(st, "colour matching changes")) return rc;
+    if (on && st->matcher != MVSV_MATCHER_SGBM)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "colour matching is for the SGBM matcher: StereoBM takes grey pairs only");
+    DeviceGuard dev_guard(ctx->device);
+    Bgr& b = st->bgr;
+    if (on && b.halve && !b.half &&
+        !b.half.alloc((size_t)st->W * st->H * 6 * st->slots.size())) {
+        (void)hipGetLastError();
+        return set_error(ctx, MVSV_E_OOM, "colour pair allocation failed");
+    }
+    b.match = on != 0;
+    return MVSV_OK;
+}
 
 // Wait for the oldest pending frame and release its slot: its status, and the
 // slot whose pinned map / means hold the result (valid until the slot's reuse).
@@ -1408,6 +1478,8 @@ static int stream_push_device(mvsv_stream* st, PushKind kind, int n, const uint8
         !source_ok(st, R, (size_t)(n - 1) * rfs + (size_t)(rows - 1) * rs + row))
         return set_error(ctx, MVSV_E_INVALID_ARG,
                          "device push: memory of the stream's device or device-accessible host memory expected");
+    const bool colour = kind == kPushBgr && st->bgr.match;
+    if ((rc = stream_kind_boundary(st, colour))) return rc;
     hipStream_t prod = (hipStream_t)producer;
     if ((rc = check_hip(ctx, hipEventRecord(st->producer_ev, prod), "stream event")) ||
         (rc = check_hip(ctx, hipStreamWaitEvent(st->up, st->producer_ev, 0), "stream wait")))
@@ -1429,6 +1501,7 @@ static int stream_push_device(mvsv_stream* st, PushKind kind, int n, const uint8
     for (int k = 0; k < n; k++) {
         auto& s = st->slots[st->head % depth];
         if (kind != kPushRaw) s.is_bgr = kind == kPushBgr;
+        s.colour = colour;
         st->head++;
         const bool launch = ring_launch_after_push(st->head, st->launched, st->batch, depth);
         if (launch || k == n - 1) {

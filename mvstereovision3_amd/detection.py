@@ -561,6 +561,15 @@ class DisparityStream:
         check(lib().mvsv_stream_disable_bgr(self._live()), self._ctx.handle)
         self._bgr_shape = None
 
+    def bgr_match(self, on=True):
+        """The maps of the colour pairs pushed from now on come from the colour matcher
+        (StereoSGBM.compute_bgr) on the pair at the stream's size -- the halved BGR
+        pair, or the pushed one without halving -- instead of the prepared grey pair,
+        which still feeds sharpness and the rectified pair (mvsv_stream_set_bgr_match).
+        After enable_bgr, only while no frame is pending, SGBM only; grey pushes keep
+        working and never share a launch with colour-matched frames."""
+        check(lib().mvsv_stream_set_bgr_match(self._live(), 1 if on else 0), self._ctx.handle)
+
     def push_bgr(self, left, right):
         """Push a colour pair: uint8 (height, width, 3) BGR arrays of enable_bgr's shape."""
         self._live()

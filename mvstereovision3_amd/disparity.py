@@ -119,6 +119,63 @@ def _run_device(fn, params, left, right, out, what):
     return out
 
 
+def _run_host_bgr(fn, params, left, right, out, what):
+    """(H, W, 3) or (N, H, W, 3) uint8 host arrays through the host colour entry."""
+    L = np.asarray(left)
+    R = np.asarray(right)
+    if L.ndim not in (3, 4) or L.shape[-1] != 3 or L.dtype != np.uint8 or R.dtype != np.uint8:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be (H,W,3) or (N,H,W,3) CV_8UC3 (uint8)")
+    if L.shape != R.shape:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: left and right sizes differ")
+    if L.strides[-1] != 1 or L.strides[-2] != 3:
+        L = np.ascontiguousarray(L)
+    if R.strides[-1] != 1 or R.strides[-2] != 3:
+        R = np.ascontiguousarray(R)
+    batched = L.ndim == 4
+    H, W = L.shape[-3], L.shape[-2]
+    if out is None or not isinstance(out, np.ndarray) or out.shape != L.shape[:-1] \
+            or out.dtype != np.int16 or out.strides[-1] != 2:
+        out = np.empty(L.shape[:-1], np.int16)  # cv::Mat::create semantics: reallocate
+    ctx = context(0)
+    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    for Lf, Rf, Of in (zip(L, R, out) if batched else ((L, R, out),)):
+        rc = fn(ctx.handle, Lf.ctypes.data, Lf.strides[0], Rf.ctypes.data, Rf.strides[0], W, H,
+                ctypes.byref(params), Of.ctypes.data, Of.strides[0] // 2)
+        check(rc, ctx.handle)
+    return out
+
+
+def _run_device_bgr(fn, params, left, right, out, what):
+    """(H, W, 3) or (N, H, W, 3) uint8 device tensors on the current torch stream."""
+    import torch
+    if left.dtype != torch.uint8 or right.dtype != torch.uint8:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be uint8")
+    if left.shape != right.shape or left.dim() not in (3, 4) or left.shape[-1] != 3:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be (H,W,3) or (N,H,W,3), equal")
+    if not left.is_cuda or not right.is_cuda or left.device != right.device:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: device tensors on one GPU expected")
+    batched = left.dim() == 4
+    Lt = left if batched else left.unsqueeze(0)
+    Rt = right if batched else right.unsqueeze(0)
+    if Lt.stride(3) != 1 or Lt.stride(2) != 3:
+        Lt = Lt.contiguous()
+    if Rt.stride(3) != 1 or Rt.stride(2) != 3:
+        Rt = Rt.contiguous()
+    n, H, W, _ = Lt.shape
+    oshape = tuple(left.shape[:-1])
+    if out is None or tuple(out.shape) != oshape or out.dtype != torch.int16 \
+            or out.device != left.device or out.stride(-1) != 1:
+        out = torch.empty(oshape, dtype=torch.int16, device=left.device)
+    Ot = out if batched else out.unsqueeze(0)
+    ctx = context(left.device.index or 0)
+    stream = torch.cuda.current_stream(left.device).cuda_stream
+    check(lib().mvsv_set_stream(ctx.handle, ctypes.c_void_p(stream)), ctx.handle)
+    rc = fn(ctx.handle, n, Lt.data_ptr(), Lt.stride(1), Lt.stride(0), Rt.data_ptr(), Rt.stride(1),
+            Rt.stride(0), W, H, ctypes.byref(params), Ot.data_ptr(), Ot.stride(1), Ot.stride(0))
+    check(rc, ctx.handle)
+    return out
+
+
 class StereoMatcher:
     DISP_SHIFT = DISP_SHIFT
     DISP_SCALE = DISP_SCALE
@@ -171,6 +228,18 @@ class StereoSGBM(StereoMatcher):
     def _host_fn(self): return lib().mvsv_sgbm         # noqa: E704
     def _dev_fn(self): return lib().mvsv_sgbm_device   # noqa: E704
 
+    def compute_bgr(self, left, right, disparity=None):
+        """cv::StereoSGBM::compute on a CV_8UC3 pair: the Birchfield-Tomasi cost
+        summed over the three channels.  (H, W, 3) or (N, H, W, 3) uint8, numpy
+        arrays or torch device tensors, otherwise as :meth:`compute` (which reads
+        a 3-D array as a batch of grey frames, so the colour form has its own
+        name).  Rows may be padded; pixels must be 3 contiguous bytes."""
+        if _is_torch(left) != _is_torch(right):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "StereoSGBM: left and right must both be numpy or both torch")
+        if _is_torch(left):
+            return _run_device_bgr(lib().mvsv_sgbm_bgr_device, self._params, left, right, disparity, "StereoSGBM")
+        return _run_host_bgr(lib().mvsv_sgbm_bgr, self._params, left, right, disparity, "StereoSGBM")
+
     def setPreFilterCap(self, v): self._params.pre_filter_cap = int(v)      # noqa: E704
     def getPreFilterCap(self): return self._params.pre_filter_cap            # noqa: E704
     def setUniquenessRatio(self, v): self._params.uniqueness_ratio = int(v)  # noqa: E704
@@ -222,6 +291,11 @@ class Disparity:
     def sgbm(inputImages: Stereopair, output, dispCompute: StereoSGBM):
         """src/disparity.cpp:6-10: forwards to compute(); returns the (re)allocated map."""
         return dispCompute.compute(inputImages.mLeft, inputImages.mRight, output)
+
+    @staticmethod
+    def sgbm_bgr(inputImages: Stereopair, output, dispCompute: StereoSGBM):
+        """Disparity::sgbm on a CV_8UC3 pair (cv::StereoSGBM::compute matches in colour)."""
+        return dispCompute.compute_bgr(inputImages.mLeft, inputImages.mRight, output)
 
     @staticmethod
     def bm(inputImages: Stereopair, output, dispCompute: StereoBM):
