@@ -276,7 +276,11 @@ MVSV_API int mvsv_bm_device(mvsv_ctx* ctx, int n, const uint8_t* left, size_t le
                             int height, const mvsv_bm_params* p, int16_t* out,
                             size_t out_stride, size_t out_frame_stride);
 
-/* Device bytes the context will cache for one SGBM / BM call of this shape. */
+/* Device bytes the context will cache for one SGBM call of this shape: the buffer
+ * sizes of the launch plan the library makes for it, plus the speckle filter's
+ * buffers.  The figure is for a context with default options (no MVSV_*
+ * environment, no mvsv_set_option) on a 256-CU device; 0 for invalid parameters
+ * and for an empty column range (such a call only fills the map). */
 MVSV_API size_t mvsv_sgbm_workspace_bytes(int n, int width, int height,
                                           const mvsv_sgbm_params* p);
 

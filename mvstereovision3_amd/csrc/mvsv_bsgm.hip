@@ -142,7 +142,7 @@ __device__ __forceinline__ void bs_quad_step(const uint32_t (&s)[3], const uint3
 // ---------------------------------------------------------------------------
 template <int NG>
 struct BsStripCfg {
-    static constexpr int kSW = 32 * NG;          // U-columns per strip
+    static constexpr int kSW = bs_strip_cols(NG);  // U-columns per strip
     static constexpr int kCompute = 3 * NG;      // compute waves
     static constexpr int kThreads = 64 * (kCompute + 1);
     static constexpr int kCols = kSW + 2;        // + two columns of the right strip
@@ -150,9 +150,7 @@ struct BsStripCfg {
     static constexpr int kDl = 2 * 2 * 6 * kSW * 2;    // deltas [buf][dir b, c][word][col][h]
     static constexpr size_t kBytes = (size_t)(kSt + kDl) * 4;
 };
-// boundary words per strip step: (dir b, column 0), (dir c, column 0), (dir c,
-// column 1), each 2 lanes x 6 words; one u64 granule = 32-bit launch tag | word
-constexpr int kBsGran = 36;
+// (boundary words per strip step: kBsGran u64 granules, mvsv_sgbm_plan.hpp)
 constexpr int kBsPF = 4;  // steps of C' prefetch (compute waves)
 constexpr int kBsStripLds = 96 * 1024;  // strip block LDS allocation (launch_bs_strips)
 constexpr int kBsBF = 4;  // steps of boundary prefetch (exchange wave)
@@ -1119,85 +1117,39 @@ __global__ __launch_bounds__(128) void bsgm_fixup_col0_kernel(uint32_t* __restri
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-bool bsgm_eligible(const mvsv_ctx* ctx, const SgbmEff& e, int n, int H)
-{
-    const long bs = 2L * e.SW2 + 1;
-    const bool no_wrap = (long)e.P2 + bs * bs * e.cn * (2L * e.ftzero + 63) + e.P2 <= 32767;
-    // (the C' planes come from the register-ring cost kernel: grey pairs only)
-    return e.cn == 1 && ctx->opt.bitslice && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && no_wrap &&
-           e.W1 > 0 && (size_t)n * H * bs::padq(e.W1) * 16 < ((size_t)1 << 31);
-}
-
-size_t bsgm_plane_bytes(int n, int H, int W1) { return (size_t)n * H * bs::padq(W1) * 64; }
-
+// (what runs and on which planes is the SgbmPlan's, mvsv_sgbm_plan.hpp; the
+// buffers are ensured by sgbm_device)
 template <int NG>
-static int launch_bs_strips(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const uint32_t* Bv, uint32_t* Av,
-                            size_t aplane, uint32_t* dummy)
+static int launch_bs_strips(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, const SgbmEff& e, const uint32_t* Bv,
+                            uint32_t* Av, size_t aplane, uint32_t* dummy)
 {
     using Cfg = BsStripCfg<NG>;
-    const int npass = e.fullDP ? 2 : 1;  // MODE_SGBM: the down pass only
-    const int nstrips = (e.W1 + H - 1 + Cfg::kSW - 1) / Cfg::kSW;
-    const size_t bytes = (size_t)npass * n * nstrips * H * kBsGran * 8;
     int rc;
-    if (ctx->bs_bnd.bytes < bytes) {
-        if ((rc = ensure(ctx, ctx->bs_bnd, bytes, "bit-sliced strip boundary granules"))) return rc;
-        // tag 0 (fresh memory) is never a launch epoch
-        if ((rc = check_hip(ctx, hipMemsetAsync(ctx->bs_bnd.ptr, 0, ctx->bs_bnd.bytes, ctx->stream),
-                            "bit-sliced boundary reset")))
-            return rc;
-    }
-    if (!ctx->status.ptr) {
-        if ((rc = ensure(ctx, ctx->status, 16, "device status words"))) return rc;
-        if ((rc = check_hip(ctx, hipMemsetAsync(ctx->status.ptr, 0, 16, ctx->stream), "status reset"))) return rc;
-        ctx->tri_tickets = 0;
-    }
-    // one epoch counter with the packed strip kernel: 32-bit tags here never repeat
-    if ((++ctx->tri_epoch & 0xffffu) == 0) ++ctx->tri_epoch;
-    const unsigned epoch = ctx->tri_epoch;
-    const dim3 grid(nstrips * npass * n);
-    const bool tickets = ctx->opt.strip_tickets != 0;
-    // MVSV_BS_STATS: per-strip spans and hand-off spin time on stderr
-    // (diagnostics only: the buffer is cleared on the context stream, and any
-    // failure turns the statistics off instead of touching a null buffer)
-    unsigned long long* stats = nullptr;
-    if (std::getenv("MVSV_BS_STATS")) {
-        if (hipMalloc(&stats, (size_t)grid.x * 64) != hipSuccess) {
-            (void)hipGetLastError();
-            stats = nullptr;
-        } else if (hipMemsetAsync(stats, 0, (size_t)grid.x * 64, ctx->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(stats);
-            stats = nullptr;
-        }
-    }
+    unsigned epoch;
+    long long ticket0;
+    if ((rc = strip_begin(ctx, ctx->bs_bnd, 32, &epoch, &ticket0))) return rc;
+    const dim3 grid((unsigned)plan.blocks);
+    // bs_stats: per-strip spans and hand-off spin time on stderr
+    unsigned long long* stats = ctx->opt.bs_stats ? strip_stats_alloc(ctx, (size_t)grid.x * 64) : nullptr;
     // one strip block per CU: dynamic LDS past half the CU's 160 KiB (a second
     // strip block on the same CU makes that CU's strips, and every strip left of
     // them in the chain, step at half speed -- 2-group strips measured 1.17 ms
     // two to a CU, 0.88 ms one to a CU, 4-group strips 0.98 ms either way;
     // the lines / cost blocks of a concurrent batch still fit beside it).
-    // MVSV_BS_LDSPAD overrides the size (A/B).
-    size_t lds = std::max(Cfg::kBytes, (size_t)kBsStripLds);
-    if (const char* pv = std::getenv("MVSV_BS_LDSPAD")) lds = std::max(Cfg::kBytes, (size_t)std::atol(pv));
+    // bs_ldspad overrides the size (A/B).
+    const size_t lds = std::max(Cfg::kBytes, (size_t)(ctx->opt.bs_ldspad >= 0 ? ctx->opt.bs_ldspad : kBsStripLds));
     if (lds > 65536 &&
         (rc = check_hip(ctx, hipFuncSetAttribute((const void*)bsgm_strip_kernel<NG, 2, 5>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
                         "bit-sliced strip LDS attribute")))
         return rc;
     hipLaunchKernelGGL((bsgm_strip_kernel<NG, 2, 5>), grid, dim3(Cfg::kThreads), lds, ctx->stream, Bv, Av,
-                       aplane, dummy, H, e.W1, npass, (unsigned long long*)ctx->bs_bnd.ptr, epoch, n,
-                       (int*)ctx->status.ptr, ctx->opt.spin_limit, ctx->report_target,
-                       tickets ? (long long)ctx->tri_tickets : -1ll, stats, 0);
+                       aplane, dummy, H, e.W1, plan.passes, (unsigned long long*)ctx->bs_bnd.ptr, epoch, n,
+                       (int*)ctx->status.ptr, ctx->opt.spin_limit, ctx->report_target, ticket0, stats, 0);
     rc = check_hip(ctx, hipGetLastError(), "bit-sliced strip kernel");
-    if (rc == MVSV_OK && tickets) ctx->tri_tickets += grid.x;
-    if (stats) {
-        std::vector<unsigned long long> hv((size_t)grid.x * 8);
-        const bool ok = hipStreamSynchronize(ctx->stream) == hipSuccess &&
-                        hipMemcpy(hv.data(), stats, hv.size() * 8, hipMemcpyDeviceToHost) == hipSuccess;
-        (void)hipFree(stats);
-        if (!ok) {
-            (void)hipGetLastError();
-            return rc;
-        }
+    if (rc == MVSV_OK && ticket0 >= 0) ctx->tri_tickets += grid.x;
+    std::vector<unsigned long long> hv;
+    if (stats && strip_stats_read(ctx, stats, (size_t)grid.x * 8, &hv)) {
         unsigned long long t0 = ~0ull, t1 = 0, spin = 0, busy = 0, steps = 0;
         for (size_t b = 0; b < grid.x; b++) {
             const unsigned long long* q = &hv[b * 8];
@@ -1209,27 +1161,25 @@ static int launch_bs_strips(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const
             steps += q[4];
         }
         std::fprintf(stderr, "[bs] NG %d strips %d blocks %u span %llu ticks, block-ticks %llu, spin %.1f%%, ticks/step %.1f\n",
-                     NG, nstrips, grid.x, t1 - t0, busy, 100.0 * spin / std::max(busy, 1ull),
+                     NG, plan.nstrips, grid.x, t1 - t0, busy, 100.0 * spin / std::max(busy, 1ull),
                      (double)busy / std::max(steps, 1ull));
     }
     return rc;
 }
 
-// Small launches (path_schedule 2): all eight directions as independent
-// lane-quad chains in one launch, eight delta planes, then the WTA over them.
-static int bsgm_paths_side(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const int16_t* Cv,
-                           const uint32_t* Bv, const uint16_t* Mv, int16_t* raw)
+// Small launches (schedule 2): all eight (five) directions as independent
+// lane-quad chains in one launch, one delta plane each, then the WTA over them.
+static int bsgm_paths_side(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e,
+                           const int16_t* Cv, const uint32_t* Bv, const uint16_t* Mv, int16_t* raw)
 {
     int rc;
-    const int npass = e.fullDP ? 2 : 1, ndir = 3 * npass + 2;
-    const size_t dplane = (size_t)n * H * bs::padq(e.W1) * 12;  // words per delta plane (grouped)
-    // + 256 words: dummy store slots of cells outside the image
-    if ((rc = ensure(ctx, ctx->agg, (ndir * dplane + 256) * 4, "bit-sliced delta planes"))) return rc;
-    if ((rc = ensure(ctx, ctx->keys, (size_t)n * H * W * 4, "sgbm right-view keys"))) return rc;
+    const int npass = e.fullDP ? 2 : 1, ndir = plan.nplanes;
+    const size_t dplane = plan.bs_dplane;  // words per delta plane (grouped)
     uint32_t* Dv = (uint32_t*)ctx->agg.ptr;
     hipStream_t s = ctx->stream;
     {
         StageTimer tm(ctx, kStagePath);
+        // (Dv + ndir * dplane: the dummy store slots of cells outside the image)
         hipLaunchKernelGGL((bsgm_dir_kernel<2, 5>), dim3((e.W1 + H - 1 + 15) / 16, n, ndir), dim3(64), 0, s, Bv,
                            Dv, dplane, H, e.W1, Dv + ndir * dplane, npass);
         if ((rc = check_hip(ctx, hipGetLastError(), "bit-sliced direction kernel"))) return rc;
@@ -1261,35 +1211,22 @@ int bsgm_cost_fixup(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, int16_t* Cv, 
     return check_hip(ctx, hipGetLastError(), "bit-sliced cost fixup");
 }
 
-int bsgm_paths(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const int16_t* Cv, const uint32_t* Bv,
-               const uint16_t* Mv, int16_t* raw, bool side)
+int bsgm_paths(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, const int16_t* Cv,
+               const uint32_t* Bv, const uint16_t* Mv, int16_t* raw)
 {
     int rc;
-    if (side) return bsgm_paths_side(ctx, n, H, W, e, Cv, Bv, Mv, raw);
-    const int npass = e.fullDP ? 2 : 1;  // strip passes (MODE_SGBM: down only)
-    const size_t aplane = (size_t)n * H * e.W1 * 16;  // words per strip-pass plane
-    const size_t dplane = (size_t)n * H * bs::padq(e.W1) * 12;  // words per line plane (grouped, padded rows)
-    // + 512 words: the strip kernel's dummy store slots (cells outside the image)
-    if ((rc = ensure(ctx, ctx->agg, (npass * aplane + 2 * dplane + 512) * 4, "bit-sliced delta planes")))
-        return rc;
-    if ((rc = ensure(ctx, ctx->keys, (size_t)n * H * W * 4, "sgbm right-view keys"))) return rc;
+    if (plan.sched == 2) return bsgm_paths_side(ctx, plan, n, H, W, e, Cv, Bv, Mv, raw);
+    const int npass = plan.passes;  // strip passes (MODE_SGBM: down only)
+    const size_t aplane = plan.bs_aplane, dplane = plan.bs_dplane;  // words per strip-pass / line plane
     uint32_t* Av = (uint32_t*)ctx->agg.ptr;
     uint32_t* Dv = Av + npass * aplane;
     hipStream_t s = ctx->stream;
-    if (!ctx->aux) {
-        if ((rc = check_hip(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking), "aux stream")) ||
-            (rc = check_hip(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming), "event")) ||
-            (rc = check_hip(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming), "event")))
-            return rc;
-    }
+    if ((rc = ensure_aux(ctx))) return rc;
     {
         StageTimer tm(ctx, kStagePath);
-        // the row directions beside the strips on the aux stream (the strip
-        // chain leaves CUs idle while it fills and drains, the line waves are
-        // few and memory-bound): bench 2970 vs 2850 Mpix/s with the lines after
-        // the strips on the context stream (MVSV_BS_SERIAL=1, same box, with
-        // one-block-per-CU 2-group strips and the grouped planes)
-        const bool side = !ctx->opt.bs_serial;
+        // the row directions beside the strips on the second stream, or
+        // (plan.lines_aux 0) after them on the context stream
+        const bool side = plan.lines_aux != 0;
         if (side && ((rc = check_hip(ctx, hipEventRecord(ctx->ev_fork, s), "fork")) ||
                      (rc = check_hip(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0), "fork wait"))))
             return rc;
@@ -1305,18 +1242,15 @@ int bsgm_paths(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const int16
         if (side && (rc = lines())) return rc;
         {
             StageTimer ts(ctx, kStageStrips);
-            // 3 column groups (96 U-columns, 10 waves) for MODE_HH batches: 352
-            // strip blocks per 8-frame batch instead of 528 overlap better with
-            // the other batch in flight (bench 3114-3120 -> 3164-3169 Mpix/s,
-            // same box, r06n; one batch alone: strips 1.14 -> 1.15 ms); 4 groups
-            // leave no room for the line waves beside them (lines 0.55 -> 2.0 ms)
-            const int ng = ctx->opt.bs_groups ? ctx->opt.bs_groups : (e.fullDP ? 3 : 2);
-            uint32_t* dummy = Dv + 2 * dplane;
-            rc = ng == 1   ? launch_bs_strips<1>(ctx, n, H, e, Bv, Av, aplane, dummy)
-                 : ng == 3 ? launch_bs_strips<3>(ctx, n, H, e, Bv, Av, aplane, dummy)
-                 : ng == 4 ? launch_bs_strips<4>(ctx, n, H, e, Bv, Av, aplane, dummy)
-                 : ng == 5 ? launch_bs_strips<5>(ctx, n, H, e, Bv, Av, aplane, dummy)
-                           : launch_bs_strips<2>(ctx, n, H, e, Bv, Av, aplane, dummy);
+            uint32_t* dummy = Dv + 2 * dplane;  // store slots of cells outside the image
+            switch (plan.bs_groups) {
+            case 1: rc = launch_bs_strips<1>(ctx, plan, n, H, e, Bv, Av, aplane, dummy); break;
+            case 2: rc = launch_bs_strips<2>(ctx, plan, n, H, e, Bv, Av, aplane, dummy); break;
+            case 3: rc = launch_bs_strips<3>(ctx, plan, n, H, e, Bv, Av, aplane, dummy); break;
+            case 4: rc = launch_bs_strips<4>(ctx, plan, n, H, e, Bv, Av, aplane, dummy); break;
+            case 5: rc = launch_bs_strips<5>(ctx, plan, n, H, e, Bv, Av, aplane, dummy); break;
+            default: rc = set_error(ctx, MVSV_E_HIP, "internal: no bit-sliced strip kernel of the SGBM plan's width");
+            }
             if (rc) return rc;
         }
         if (!side && (rc = lines())) return rc;

@@ -895,48 +895,36 @@ static Cost2Kern cost2_pick(int nr, int stg, int ppc, bool bse)
                         : cost2_pick_nr<2, 0, false>(nr);
 }
 
-// Cost-volume launch: the register-ring kernel when blockSize <= 15 and the
-// tile fits, else the LDS-ring kernel.  *Rv (residual plane, may be nullptr)
-// is written by the register-ring kernel only: the LDS-ring fallback sets it
-// to nullptr, and the direction passes then read C.
-int launch_cost(mvsv_ctx* ctx, int n, int W, int H, const SgbmEff& e, int TY,
-                       const uint64_t* pre, int16_t* Cv, uint8_t** Rv, uint16_t* Mv, bool* pinned_hh,
-                       uint32_t** Bv)
+// Cost-volume launch: the kernel the plan names -- the register-ring kernel
+// (grey pairs, blockSize <= 15, the tile fits), which alone writes the residual
+// plane Rv or the bit-sliced C' planes Bv, else the LDS-ring kernel.  A plane
+// the plan orders from a launch that cannot write it is an internal error.
+int launch_cost(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int W, int H, const SgbmEff& e, const uint64_t* pre,
+                int16_t* Cv, uint8_t* Rv, uint16_t* Mv, uint32_t* Bv)
 {
-    *pinned_hh = false;
     hipStream_t s = ctx->stream;
+    const int TY = plan.cost_ty;
     int rc;
-    // (colour pairs, e.cn == 3: always the LDS-ring kernel, which sums the channels)
-    if (e.cn == 1 && ctx->opt.cost2 && e.SH2 <= 7 && e.SW2 == e.SH2) {
-        const Cost2Layout l2 = cost2_layout(e.D, e.SW2, TY);
-        const int items = 2 * l2.NX + e.D - 1;
-        const bool two = items > kCost2Threads;
-        // numDisparities 128 / 256: the pair count is a compile-time
-        // constant (unrolled pixel-cost loop, immediate LDS offsets)
-        const int ppc = !ctx->opt.cost_fixed_pp ? 0 : l2.PP == 64 ? 64 : (l2.PP == 128 ? 128 : 0);
-        const size_t lbytes = cost2_total_bytes(l2, 2 * e.SH2 + 1, two ? 2 : 1, ppc);
-        if (l2.CL >= 1 && items <= kCost2Threads * 2 && lbytes <= 160 * 1024) {
-            dim3 grid2((e.W1 + l2.TX - 1) / l2.TX, (H + TY - 1) / TY, n);
-            Cost2Kern kern = nullptr;
-            if (ppc != 64) *Bv = nullptr;  // the bit-sliced plane: D = 128 kernels only
-            kern = cost2_pick(2 * e.SH2 + 1, two ? 2 : 1, ppc, *Bv != nullptr);
-            if (lbytes > 65536 &&
-                (rc = check_hip(ctx, hipFuncSetAttribute((const void*)kern,
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                         (int)lbytes),
-                                "sgbm cost LDS attribute")))
-                return rc;
-            {
-                StageTimer tm(ctx, kStageCost);
-                hipLaunchKernelGGL(kern, grid2, dim3(kCost2Threads), lbytes, s, pre, W, H, e, TY,
-                                   Cv, *Bv ? nullptr : *Rv, Mv, *Bv, ctx->opt.cost_xcd ? 1 : 0);
-            }
-            *pinned_hh = e.fullDP != 0;  // MODE_HH fix-up rows/column written by the kernel
-            return check_hip(ctx, hipGetLastError(), "sgbm cost kernel");
+    if (plan.cost2) {
+        const Cost2Launch c = cost2_launch(e, ctx->opt.cost_fixed_pp, TY);
+        // (the bit-sliced emission: D = 128 kernels only)
+        if (!c.fits || (Bv && c.ppc != 64) || (Bv && Rv))
+            return set_error(ctx, MVSV_E_HIP, "internal: the SGBM plan's cost kernel cannot write its planes");
+        dim3 grid2((e.W1 + c.l.TX - 1) / c.l.TX, (H + TY - 1) / TY, n);
+        Cost2Kern kern = cost2_pick(2 * e.SH2 + 1, c.stg, c.ppc, Bv != nullptr);
+        if (c.lds > 65536 &&
+            (rc = check_hip(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     (int)c.lds),
+                            "sgbm cost LDS attribute")))
+            return rc;
+        {
+            StageTimer tm(ctx, kStageCost);
+            hipLaunchKernelGGL(kern, grid2, dim3(kCost2Threads), c.lds, s, pre, W, H, e, TY, Cv, Rv, Mv, Bv,
+                               ctx->opt.cost_xcd ? 1 : 0);
         }
+        return check_hip(ctx, hipGetLastError(), "sgbm cost kernel");
     }
-    *Rv = nullptr;
-    *Bv = nullptr;
+    if (Rv || Bv) return set_error(ctx, MVSV_E_HIP, "internal: the LDS-ring cost kernel writes no residual or bit planes");
     CostLayout lay = cost_layout(e.D, e.SW2, e.SH2, TY);
     if (lay.nLmax + lay.nRmax + 1 > 256 * kStageRegs)
         return set_error(ctx, MVSV_E_INVALID_ARG, "numDisparities too large for the GPU cost kernel");
@@ -955,16 +943,6 @@ int launch_cost(mvsv_ctx* ctx, int n, int W, int H, const SgbmEff& e, int TY,
         hipLaunchKernelGGL(kern, cgrid, dim3(256), lay.bytes, s, pre, W, H, e, TY, Cv);
     }
     return check_hip(ctx, hipGetLastError(), "sgbm cost kernel");
-}
-
-bool cost2_runs(const mvsv_ctx* ctx, const SgbmEff& e)
-{
-    if (e.cn != 1 || !ctx->opt.cost2 || e.SH2 > 7 || e.SW2 != e.SH2) return false;
-    const Cost2Layout l2 = cost2_layout(e.D, e.SW2, 120);  // (the layout does not depend on the tile height)
-    const int items = 2 * l2.NX + e.D - 1;
-    const int ppc = !ctx->opt.cost_fixed_pp ? 0 : l2.PP == 64 ? 64 : (l2.PP == 128 ? 128 : 0);
-    const size_t lbytes = cost2_total_bytes(l2, 2 * e.SH2 + 1, items > kCost2Threads ? 2 : 1, ppc);
-    return l2.CL >= 1 && items <= kCost2Threads * 2 && lbytes <= 160 * 1024;
 }
 
 int launch_prefilter(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R, size_t rs,

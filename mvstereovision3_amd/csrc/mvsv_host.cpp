@@ -382,6 +382,10 @@ int mvsv_create(mvsv_ctx** out, int hip_device)
     if (const char* v = std::getenv("MVSV_BS_SERIAL")) c->opt.bs_serial = std::atoi(v) != 0;
     if (const char* v = std::getenv("MVSV_COST_XCD")) c->opt.cost_xcd = std::atoi(v) != 0;
     if (const char* v = std::getenv("MVSV_BS_FUSE")) c->opt.bs_fuse = std::atoi(v) != 0;
+    c->opt.tri_stats = std::getenv("MVSV_TRI_STATS") != nullptr;
+    if (const char* v = std::getenv("MVSV_TRI_TRACE")) c->opt.tri_trace = v;
+    c->opt.bs_stats = std::getenv("MVSV_BS_STATS") != nullptr;
+    if (const char* v = std::getenv("MVSV_BS_LDSPAD")) c->opt.bs_ldspad = std::max(0L, std::atol(v));
     if (const char* v = std::getenv("MVSV_BS_GROUPS")) {
         const int g = std::atoi(v);
         c->opt.bs_groups = (g >= 1 && g <= 5) ? g : 0;
@@ -566,39 +570,11 @@ size_t mvsv_sgbm_workspace_bytes_cn(int n, int W, int H, const mvsv_sgbm_params*
     std::string why;
     if (n <= 0 || (cn != 1 && cn != 3) || resolve_sgbm(p, W, H, &e, &why) != MVSV_OK) return 0;
     e.cn = cn;
-    size_t frame = (size_t)W * H;
-    size_t vol = e.W1 > 0 ? (size_t)e.W1 * H * e.D * 2 : 0;
-    size_t b = (size_t)n * (frame * 4 + 2 * vol + frame * 2);
-    // speckle filter (speckle_buffers, mvsv_post.hip): parent, size and tile
-    // words, u16 local roots and the compact root list (+ its count)
-    if (e.speckle_window > 0) b += (size_t)n * frame * (4 + 4 + 4 + 2 + 4) + 4;
-    // cost residual plane + per-pixel minimum (MVSV_OPT_COST_RESIDUAL, where exact)
-    if (cn == 1 && 3 * e.P2 <= 15 && e.D <= 128 && e.W1 > 0) b += (size_t)n * e.W1 * H * (e.D / 2 + 2);
-    // the BT interval planes of both views (u64 per pixel and channel each)
-    b += (size_t)n * frame * 16 * cn;
-    // the bit-sliced pipeline (MVSV_OPT_BITSLICE, default on):
-    // rows padded to 4 pixels, delta planes beyond the accumulator budget above
-    // (eight 48-byte planes side by side for small launches), strip boundary
-    // granules (2 passes x strips of 64 U-columns x H rows x 36 u64)
-    const long bsz = 2L * e.SW2 + 1;
-    const bool bs_regime = cn == 1 && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && e.W1 > 0 &&
-                           (long)e.P2 + bsz * bsz * (2L * e.ftzero + 63) + e.P2 <= 32767;
-    if (bs_regime) {
-        const size_t W1q = (size_t)(e.W1 + 3) & ~(size_t)3;
-        b += (size_t)n * H * (W1q - e.W1) * (e.D * 2 + 64);               // padded C and C'
-        const size_t side = (size_t)n * H * W1q * 8 * 48, acc = (size_t)n * vol;
-        if (side > acc) b += side - acc;
-        const size_t nstrips = ((size_t)e.W1 + H - 1 + 63) / 64;
-        b += 2 * (size_t)n * nstrips * H * 36 * 8;
-    } else if (e.P2 > 15 && e.W1 > 0) {
-        // directions side by side on byte / u16 planes (round 6: the reference's
-        // liveDisparity / captureDisparity shapes), one plane per direction
-        // (D <= 32: R->L included), beyond the one-volume accumulator budget above
-        const size_t planes = (e.fullDP ? 7 : 4) + (e.D <= 32 ? 1 : 0), ebytes = (e.fullDP ? 8 : 5) * e.P2 <= 255 ? 1 : 2;
-        const size_t side = (size_t)n * e.W1 * H * e.D * planes * ebytes, acc = (size_t)n * vol;
-        if (side > acc) b += side - acc;
-    }
-    return b;
+    // what a context with default kernel options on a 256-CU device allocates:
+    // the plan's buffers, and the speckle filter's
+    const SgbmPlan plan = sgbm_make_plan(KernelOptions(), 256, e, n, W, H);
+    if (plan.empty) return 0;  // an empty column range only fills the map
+    return plan.total_bytes() + (e.speckle_window > 0 ? speckle_bytes(n, W, H).total() : 0);
 }
 
 size_t mvsv_sgbm_workspace_bytes(int n, int W, int H, const mvsv_sgbm_params* p)
@@ -615,7 +591,7 @@ int mvsv_sgbm_plan_cn(mvsv_ctx* ctx, int n, int W, int H, const mvsv_sgbm_params
     const int rc = resolve_sgbm(p, W, H, &e, &why);
     if (rc) return set_error(ctx, rc, why);
     e.cn = cn;
-    *plan = sgbm_plan(ctx, e, n, H);
+    *plan = sgbm_make_plan(ctx, e, n, W, H).bits();
     return MVSV_OK;
 }
 
@@ -647,7 +623,7 @@ static int sgbm_device_call(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, s
     auto body = [&]() { return sgbm_device(ctx, n, L, ls, lfs, R, rs, rfs, W, H, e, out, os, ofs); };
     // small launches (one camera frame): one graph launch instead of ~8 kernel
     // launches (config 3, one 640x480 frame: ~5 us of launch gap per kernel)
-    if (ctx->graphs && !ctx->prof && sgbm_graphable(ctx, e, n, H)) {
+    if (ctx->graphs && !ctx->prof && sgbm_make_plan(ctx, e, n, W, H).graphable()) {
         std::vector<unsigned char> key;
         key_put(key, 'S');
         key_put(key, n);

@@ -9,30 +9,13 @@
 #include <vector>
 
 #include "../../include/mvsv.h"
+#include "mvsv_sgbm_plan.hpp"
 
 namespace mvsv {
 
 constexpr int kMaxCost = 32767;    // OpenCV StereoSGBM MAX_COST (SHRT_MAX)
 constexpr int kDispShift = 4;      // StereoMatcher::DISP_SHIFT
 constexpr int kDispScale = 16;
-
-// Effective StereoSGBM parameters after OpenCV's defaulting rules
-// ([OpenCV] computeDisparitySGBM prologue).
-struct SgbmEff {
-    int minD, maxD, D;
-    int SW2, SH2;
-    int ftzero;
-    int uniq, disp12;
-    int P1, P2;
-    int minX1, maxX1, W1;
-    int invalid;  // (minD - 1) * 16
-    int fullDP;   // MODE_HH
-    int variant;
-    int speckle_window, speckle_diff;  // speckle_diff = 16 * speckleRange
-    // colour channels of the pair: 1 (grey; resolve_sgbm) or 3 (interleaved BGR,
-    // set by the colour entry points).  A pixel cost is <= cn * (2*ftzero + 63).
-    int cn;
-};
 
 struct BmEff {
     int ndisp, mindisp, wsz2, cap, tex, uniq;
@@ -77,40 +60,9 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
-// Default number of polls a strip-boundary wait of the sheared-strip kernel
-// makes before it gives up (each poll = one s_sleep + one L2 load of the
-// producer's granule, ~1 us): ~1 s, far beyond any producer delay of a
-// healthy launch; the wait only exists to turn a lost hand-off into an error
-// instead of a hang.  mvsv_set_option(MVSV_OPT_STRIP_SPIN_LIMIT) overrides it.
-constexpr unsigned kStripSpinLimitDefault = 1u << 20;
-
-// The launch-shape options of a context (MVSV_* environment at creation,
-// mvsv_set_option): which kernels run and how their launches are cut.  A frame
-// stream's own lane contexts take the caller context's as a whole.
-struct KernelOptions {
-    // strip blocks draw their strip as a ticket (status[2]) unless strip_tickets
-    // is 0 (blockIdx order, MVSV_STRIP_ORDER=blockidx)
-    int strip_tickets = 1;
-    unsigned spin_limit = kStripSpinLimitDefault;
-    int path16 = 1;  // 16-lanes-per-scanline path kernels where D allows
-    int cost2 = 1;   // register-ring cost kernel where blockSize <= 15
-    int cost_fixed_pp = 1;  // fixed-pair-count cost kernels for D = 128 / 256 (MVSV_KERNELS=cost-generic: off)
-    int cost_ty = 0;  // cost-volume tile height (0 = by image height); MVSV_COST_TY for A/B runs
-    int tri = 1;     // sheared-strip kernels: three directions per sweep
-    int path_sched = 0;   // 16-lane path schedule: 0 = by launch size, 1 = strips, 2 = directions side by side
-    int tri32 = 1;        // D = 256 narrow strips on 32 lanes per column (MVSV_TRI32)
-    int final_split = 1;  // side by side on byte / u16 planes: R->L as a chain set + per-pixel WTA (MVSV_FINAL_SPLIT)
-    int strip_waves = 0;  // compute waves per strip (0 = by launch size; 4 or the wide count forces)
-    int cost_res = 1;     // direction passes read the cost residual plane where exact (MVSV_OPT_COST_RESIDUAL)
-    int lines_aux = -1;  // L->R line kernel beside the strip kernel: -1 = small launches only, 0 / 1 / 2 force
-    int bitslice = 1;    // bit-sliced MODE_HH paths where they apply (MVSV_OPT_BITSLICE, env MVSV_BITSLICE)
-    int bs_groups = 0;   // column groups (3 direction waves each) per bit-sliced strip: 1-5 (MVSV_BS_GROUPS), 0 = by mode
-    int cost_xcd = 1;    // cost kernel: whole row bands per XCD (MVSV_COST_XCD=0: blockIdx order, A/B)
-    int bs_fuse = 1;     // bit-sliced batches: R->L lines fused with the WTA (MVSV_BS_FUSE=0: separate, A/B)
-    int bs_serial = 0;   // 1: bit-sliced line kernel after the strips on the context stream (MVSV_BS_SERIAL, A/B)
-    int bm2 = 1;     // StereoBM: disparities-on-lanes match kernel where blockSize <= 21, D <= 128
-    int bm_ty = 0;   // its tile height (0 = chosen per launch); MVSV_BM_TY for A/B runs
-};
+static_assert(kPlanBitslice == MVSV_PLAN_BITSLICE && kPlanSide == MVSV_PLAN_SIDE && kPlanStrips == MVSV_PLAN_STRIPS &&
+                  kPlanResidual == MVSV_PLAN_RESIDUAL,
+              "SgbmPlan::bits() speaks include/mvsv.h's MVSV_PLAN_* word");
 
 }  // namespace mvsv
 
@@ -231,39 +183,51 @@ struct StageTimer {
 int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
                 size_t rs, size_t rfs, int W, int H, const SgbmEff& e, int16_t* out, size_t os,
                 size_t ofs);
-// the launch runs no strip chain (path schedule 2): its kernels and arguments are
-// the same on every call with the same arguments, so it may be replayed as a graph
-bool sgbm_graphable(const mvsv_ctx* ctx, const SgbmEff& e, int n, int H);
-// MVSV_PLAN_* bits of the pipeline sgbm_device runs for these arguments
-int sgbm_plan(const mvsv_ctx* ctx, const SgbmEff& e, int n, int H);
-// the register-ring cost kernel runs (and can write the bit-sliced planes)
-bool cost2_runs(const mvsv_ctx* ctx, const SgbmEff& e);
+// The plan of an SGBM call on this context (mvsv_sgbm_plan.hpp)
+inline SgbmPlan sgbm_make_plan(const mvsv_ctx* ctx, const SgbmEff& e, int n, int W, int H)
+{
+    return sgbm_make_plan(ctx->opt, ctx->cus, e, n, W, H);
+}
 int bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
               size_t rs, size_t rfs, int W, int H, const BmEff& e, int16_t* out, size_t os,
               size_t ofs);
-// SGBM stages 1-3 (mvsv_cost.hip): BT interval planes, the cost volume (the
-// register-ring kernel also writes the residual plane *Rv or the bit-sliced C'
-// planes *Bv where given and possible -- each is set to nullptr otherwise), and
-// OpenCV 3.4's cost-row quirks on the int16 volume.
+// SGBM stages 1-3 (mvsv_cost.hip): BT interval planes, the cost volume (the kernel
+// and tile height the plan names; the register-ring kernel also writes the residual
+// plane Rv or the bit-sliced C' planes Bv where the plan says so), and OpenCV 3.4's
+// cost-row quirks on the int16 volume.
 int launch_prefilter(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R, size_t rs,
                      size_t rfs, int W, int H, int ftzero, int cn, uint64_t* pre);
-int launch_cost(mvsv_ctx* ctx, int n, int W, int H, const SgbmEff& e, int TY, const uint64_t* pre, int16_t* Cv,
-                uint8_t** Rv, uint16_t* Mv, bool* pinned_hh, uint32_t** Bv);
+int launch_cost(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int W, int H, const SgbmEff& e, const uint64_t* pre,
+                int16_t* Cv, uint8_t* Rv, uint16_t* Mv, uint32_t* Bv);
 int launch_cost_fixup(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, int16_t* Cv, uint8_t* Rv, uint16_t* Mv);
+// Bit-sliced path aggregation + WTA, MODE_HH and MODE_SGBM (mvsv_bsgm.hip): where the
+// plan's family is kFamBitslice the cost kernel writes the C' planes Bv and bsgm_paths
+// computes raw disparities from them, on the plan's schedule, strip width and planes.
+int bsgm_paths(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, const int16_t* Cv,
+               const uint32_t* Bv, const uint16_t* Mv, int16_t* raw);
+// The second stream and its fork / join events (the L->R lines beside the strips)
+int ensure_aux(mvsv_ctx* ctx);
+// The preamble of a strip launch, packed or bit-sliced (one launch counter for both).
+// *epoch: the next launch number whose low 16 bits are not 0 -- tag 0 means "never
+// written".  16-bit tags (tag_bits 16) repeat when they wrap, so every granule of bnd
+// is zeroed again then and a slot carrying this launch's tag was written by it; 32-bit
+// tags only skip 0.  *ticket0: the launch's first strip ticket, -1 for blockIdx order
+// (strip tickets, round 4: a launch of at most one block per CU is not resident all at
+// once when other work shares the GPU, so blockIdx order would rest on in-order
+// dispatch; tickets never do).  The caller adds its block count to ctx->tri_tickets.
+int strip_begin(mvsv_ctx* ctx, DevBuf& bnd, int tag_bits, unsigned* epoch, long long* ticket0);
+// Strip statistics (diagnostics only): a zeroed device buffer, cleared on the context
+// stream -- nullptr on any failure, which switches the statistics off; and its words
+// after the stream has drained (frees the buffer; false: nothing to print).
+unsigned long long* strip_stats_alloc(mvsv_ctx* ctx, size_t bytes);
+bool strip_stats_read(mvsv_ctx* ctx, unsigned long long* stats, size_t words, std::vector<unsigned long long>* h);
+// MODE_SGBM's never-recomputed rows and column 0 on the bit-sliced layouts (C'
+// planes, pixel-quad C, m); no-op for MODE_HH, whose cost kernel pins them
+int bsgm_cost_fixup(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, int16_t* Cv, uint32_t* Bv, uint16_t* Mv);
 // Post filters shared by both matchers.
 // poison != nullptr: when *poison == epoch (the launch `epoch` gave up a strip
 // wait) every output pixel is `invalid` instead of the median -- no map computed
 // from stale hand-off data leaves the pipeline.
-// Bit-sliced path aggregation + WTA, MODE_HH and MODE_SGBM (mvsv_bsgm.hip).  bsgm_eligible:
-// the parameters admit it; the cost kernel then writes the C' planes Bv
-// (bsgm_plane_bytes) and bsgm_paths computes raw disparities from them.
-bool bsgm_eligible(const mvsv_ctx* ctx, const SgbmEff& e, int n, int H);
-size_t bsgm_plane_bytes(int n, int H, int W1);
-int bsgm_paths(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const int16_t* Cv, const uint32_t* Bv,
-               const uint16_t* Mv, int16_t* raw, bool side);
-// MODE_SGBM's never-recomputed rows and column 0 on the bit-sliced layouts (C'
-// planes, pixel-quad C, m); no-op for MODE_HH, whose cost kernel pins them
-int bsgm_cost_fixup(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, int16_t* Cv, uint32_t* Bv, uint16_t* Mv);
 int median3x3_device(mvsv_ctx* ctx, int n, const int16_t* src, size_t ss, size_t sfs,
                      int16_t* dst, size_t ds, size_t dfs, int W, int H,
                      const int* poison = nullptr, unsigned epoch = 0, int invalid = 0);

@@ -1278,15 +1278,15 @@ static int speckle_buffers(mvsv_ctx* ctx, int n, int W, int H, int** parent, int
                            uint16_t** lroot, unsigned** list)
 {
     int rc;
-    const size_t npix = (size_t)n * W * H;
+    const SpeckleBytes sb = speckle_bytes(n, W, H);  // (mvsv_sgbm_plan.hpp: also the workspace estimate's)
     // the list count is rewound by the apply kernel of every run; a fresh
     // (re)allocation, or a run that did not reach its apply launch, rewinds here
-    const bool fresh_list = ctx->uf_list.bytes < (npix + 1) * 4 || ctx->uf_list_dirty;
-    if ((rc = ensure(ctx, ctx->uf_parent, npix * 4, "speckle labels"))) return rc;
-    if ((rc = ensure(ctx, ctx->uf_size, npix * 4, "speckle sizes"))) return rc;
-    if ((rc = ensure(ctx, ctx->uf_tile, npix * 4, "speckle tile components"))) return rc;
-    if ((rc = ensure(ctx, ctx->uf_lroot, npix * 2, "speckle local roots"))) return rc;
-    if ((rc = ensure(ctx, ctx->uf_list, (npix + 1) * 4, "speckle root list"))) return rc;
+    const bool fresh_list = ctx->uf_list.bytes < sb.list || ctx->uf_list_dirty;
+    if ((rc = ensure(ctx, ctx->uf_parent, sb.parent, "speckle labels"))) return rc;
+    if ((rc = ensure(ctx, ctx->uf_size, sb.size, "speckle sizes"))) return rc;
+    if ((rc = ensure(ctx, ctx->uf_tile, sb.tile, "speckle tile components"))) return rc;
+    if ((rc = ensure(ctx, ctx->uf_lroot, sb.lroot, "speckle local roots"))) return rc;
+    if ((rc = ensure(ctx, ctx->uf_list, sb.list, "speckle root list"))) return rc;
     if (fresh_list && (rc = check_hip(ctx, hipMemsetAsync(ctx->uf_list.ptr, 0, 4, ctx->stream), "root list reset")))
         return rc;
     ctx->uf_list_dirty = true;  // until this run's apply kernel is launched

@@ -44,21 +44,14 @@ struct Line {
     int xs, ys, len;
 };
 
-// u8 accumulator when the summed path deltas (each <= P2) fit a byte
-__host__ __device__ inline bool acc_is_u8(const SgbmEff& e)
-{
-    return (e.fullDP ? 8 : 5) * e.P2 <= 255;
-}
-
 // 4-bit accumulator planes: the sheared-strip schedule writes one plane per
 // group of at most three directions (3 strip directions, or the L->R line),
-// so each plane holds sums <= 3 * P2; with P2 <= 5 (OpenCV's default P2 = 5,
-// which configs/sgbm.yml gets because it leaves P1/P2 at 0) they fit a nibble.
+// so each plane holds sums <= 3 * P2; with P2 <= 5 they fit a nibble
+// (acc_is_nib, mvsv_sgbm_plan.hpp).
 // Element offsets stay in disparity units; a byte holds two of them.
 struct nib2_t {
     uint8_t v;
 };
-__host__ __device__ inline bool acc_is_nib(const SgbmEff& e) { return 3 * e.P2 <= 15; }
 template <typename T>
 struct AccEpu {
     static constexpr int v = 1;  // accumulator elements per storage unit
@@ -804,7 +797,7 @@ __global__ __launch_bounds__(256) void sgbm_pathdirs16_kernel(const void* __rest
 // per lane, ~200 VGPRs) -- the throughput shape for frame batches; narrow
 // strips, 8 (4 for D = 256) compute waves -- the latency shape for one or two
 // frames, where wide strips leave most CUs idle and each step of a strip is
-// the serial work of its CU (see launch_tri)
+// the serial work of its CU (the strip shape is chosen by sgbm_make_plan)
 // LPC = lanes per U-column (2*NP disparities each, D = 2*NP*LPC): 16 (one DPP
 // row per column) or 8 (half a DPP row, twice the disparities per lane: the
 // per-column minimum is a 3-step butterfly, and the lane-boundary neighbours,
@@ -815,15 +808,12 @@ __global__ __launch_bounds__(256) void sgbm_pathdirs16_kernel(const void* __rest
 // half the per-wave work of a strip step at the same strip width (8 compute
 // waves x 2 columns); the three boundary items then need 96 exchange lanes,
 // so such a block has two exchange waves.
-template <int NP, int LPC = 16>
-constexpr int tri_wide_waves() { return LPC == 8 ? 7 : (NP >= 8 ? 7 : 15); }
-template <int NP, int LPC = 16>
-constexpr int tri_narrow_waves() { return LPC == 8 ? 4 : LPC == 32 ? 8 : (NP >= 8 ? 4 : 8); }
+// (the wave counts per (NP, LPC): tri_wide_waves / tri_narrow_waves, mvsv_sgbm_plan.hpp)
 template <int NP, int WV, int LPC = 16>
 struct TriCfg {
     static constexpr int kWaves = WV;
     static constexpr int kCPW = 64 / LPC;   // U-columns per compute wave
-    static constexpr int kSW = kCPW * kWaves;  // U-columns per strip
+    static constexpr int kSW = tri_strip_cols(WV, LPC);  // U-columns per strip
     static constexpr int kComm = LPC == 32 ? 2 : 1;  // exchange waves: 3 items x LPC lanes
     static constexpr int kThreads = 64 * (kWaves + kComm);
     // blocks per CU the register budget aims at: one 1024-thread block, or two
@@ -875,7 +865,7 @@ struct TriLayout {
 // (bits 48-63): the tag is the data-ready flag.
 template <int NP>
 struct TriGran {
-    static constexpr int NG = (2 * NP + 1 + 2) / 3;
+    static constexpr int NG = tri_granules(NP);
     static __device__ __forceinline__ void pack(const uint32_t (&v)[NP], int mn, unsigned long long tag,
                                                 unsigned long long (&g)[NG])
     {
@@ -2136,7 +2126,11 @@ __global__ void fill_s16_kernel(int16_t* __restrict__ out, size_t os, size_t ofs
     for (int x = threadIdx.x; x < W; x += blockDim.x) o[x] = v;
 }
 
-// sheared-strip schedule: enabled, and int32 element offsets cover a frame
+// ---------------------------------------------------------------------------
+// host side: launchers.  They launch what the SgbmPlan (mvsv_sgbm_plan.hpp)
+// names on the buffers sgbm_device ensured from it; none of them decides a
+// schedule, a kernel shape or a buffer size.
+// ---------------------------------------------------------------------------
 template <int NP, int NACC, typename AccT, bool NW = false, bool RES = false, int LPC = 16>
 void launch_final16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const int16_t* Cv,
                     const AccT* Av, size_t plane, int16_t* raw, const void* Rv = nullptr,
@@ -2169,136 +2163,28 @@ void launch_final16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const 
                            ctx->stream, Cv, Av, plane, H, W, e, raw, keys, dummy, nullptr, nullptr);
 }
 
-// Every cost C = P2 + (box sum of blockSize^2 BT costs, each <= cn * (2*ftzero + 63)),
-// every L <= C and delta = minLp + P2: when that bound stays <= 32767 nothing
-// wraps in int16 and the path kernels may use the NW recurrence (sgm_pair).
-// The split side-by-side form (sgbm_wta_planes_kernel): byte / u16 planes,
-// D <= 32.  Measured (MI355X r06 sp2, split vs fused R->L + WTA): D 16 640x480
-// x 1 / 2 / 8 frames 0.278 -> 0.196, 0.297 -> 0.220, 0.515 -> 0.477 ms; D 32
-// 1280x960 0.522 -> 0.491; D 64 x 1 / 2 0.746 -> 0.802, 1.125 -> 1.282 and D 128
-// 1.083 -> 1.370 (the fifth chain set lengthens the direction pass more than
-// the chain-free WTA saves); MODE_HH D 64 1.01 either way
-static bool wta_split(const mvsv_ctx* ctx, const SgbmEff& e)
-{
-    return ctx->opt.final_split && e.P2 > 15 && e.D <= 32;
-}
-
-static bool sgbm_no_wrap(const SgbmEff& e)
-{
-    const long bs = 2L * e.SW2 + 1;
-    return (long)e.P2 + bs * bs * e.cn * (2L * e.ftzero + 63) + e.P2 <= 32767;
-}
-
-// The direction passes read the residual plane (see its definition above)
-// when it is exact and smaller: no-wrap regime, residuals <= 3 * P2 in a
-// nibble, a 16-lane path schedule (1 = strips + lines, 2 = side by side) and
-// D <= 128 (one cost kernel wave segment holds a pixel's D costs).
-static bool use_residual(const mvsv_ctx* ctx, const SgbmEff& e, int sched)
-{
-    // (written by the register-ring cost kernel only: grey pairs)
-    return e.cn == 1 && ctx->opt.cost_res && (sched == 1 || sched == 2) && sgbm_no_wrap(e) && 3 * e.P2 <= 15 &&
-           (e.D == 32 || e.D == 64 || e.D == 128);
-}
-
-static bool use_strips(const mvsv_ctx* ctx, const SgbmEff& e, int H)
-{
-    return ctx->opt.tri && (size_t)H * e.W1 * e.D < ((size_t)1 << 31);
-}
-
-// Path schedule of the 16-lane kernels (D = 32 / 64 / 128 / 256):
-// 2 = all line directions side by side (sgbm_pathdirs16_kernel, one 4-bit plane
-// per direction, P2 <= 15) -- the latency shape for launches too small to fill
-// the chip with strips (one camera frame); 1 = sheared strips (batches).
-// ctx->opt.path_sched: 0 = by launch size, 1 / 2 force (tests, A/B).
-static int path_schedule(const mvsv_ctx* ctx, const SgbmEff& e, int H, int n)
-{
-    if (e.D == 16 && ctx->opt.path16 && ctx->opt.path_sched != 1) return 2;  // launch_paths_d16
-    if (!ctx->opt.path16 || !(e.D == 32 || e.D == 64 || e.D == 128 || e.D == 256)) return 0;
-    const bool dirs_ok = e.P2 <= 15 || ctx->opt.path_sched == 2;  // nibble planes; wider planes when forced
-    if (ctx->opt.path_sched == 2) return 2;
-    if (ctx->opt.path_sched == 0 && bsgm_eligible(ctx, e, n, H) && e.SH2 <= 7 && e.SW2 == e.SH2) {
-        // bit-sliced regime (round 6): the side-by-side chains' work grows with
-        // the direction-pixels, the strips' time with the chain length; measured
-        // (8 frames, MI355X r06e): 640x480 5 paths 0.90 side vs 1.11 ms strips,
-        // 8 paths 1.10 vs 1.06; 1280x960 5 paths 3.49 vs 3.07, 8 paths 4.53 vs
-        // 3.20; one 1280x960 frame, 8 paths 0.73 vs 1.03 (round 5)
-        const long long dirpix = (long long)n * e.W1 * H * (e.fullDP ? 8 : 5);
-        if (dirpix <= 12000000LL) return 2;
-        return use_strips(ctx, e, H) ? 1 : 0;
-    }
-    if (ctx->opt.path_sched == 0 && dirs_ok) {
-        const int wide = e.D > 128 ? 7 : 15;
-        const long long blocks = (long long)(e.fullDP ? 2 : 1) * n * ((e.W1 + H - 1 + 4 * wide - 1) / (4 * wide));
-        // measured: one 640x480 or 1280x960 frame and two 640x480 frames gain
-        // (0.76 -> 0.43, 1.62 -> 1.11, 0.83 -> 0.60 ms); two 1280x960 frames
-        // lose (1.87 -> 1.95 ms: seven planes into the final kernel)
-        if (2 * blocks <= ctx->cus) return 2;
-    }
-    if (ctx->opt.path_sched == 0 && e.P2 > 15) {
-        // byte / u16 planes (liveDisparity's create(0, 64, 9, 648, 2592)): side by
-        // side while the planes stay small -- their bytes against the strip
-        // chain's latency.  Measured (1280x960, MI355X r06 s2a / d16a): MODE_SGBM
-        // D 32 x 1-3 frames 0.91 -> 0.53, 1.20 -> 1.07 ms; D 64 x 1, 2 frames
-        // 1.16 -> 0.71, 1.34 -> 1.12 ms, x 4 1.98 -> 2.14 (strips kept); D 128 x 1
-        // 1.50 -> 1.08, x 2 1.86 -> 1.90; D 256 x 1 2.08 -> 2.16; MODE_HH D 64 x 1
-        // 1.18 -> 0.90, x 2 1.52 -> 1.59
-        const double bytes = (double)n * e.W1 * H * e.D * (e.fullDP ? 7 : 4) * (acc_is_u8(e) ? 1 : 2);
-        if (bytes <= 1.4e9) return 2;
-    }
-    return use_strips(ctx, e, H) ? 1 : 0;
-}
+// the line directions: the first four are MODE_SGBM's, the first seven
+// MODE_HH's; the last is R->L as a chain set of its own (the split WTA form)
+constexpr int kPathDirs[8][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}, {1, -1}, {0, -1}, {-1, -1}, {-1, 0}};
 
 template <int NP, int WV, int LPC, typename AccT, bool NW, bool RES>
-int launch_tri_wv(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const void* Cv, AccT* Av, size_t plane,
-                  int npass)
+int launch_tri_wv(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, const SgbmEff& e, const void* Cv, AccT* Av,
+                  size_t plane)
 {
     using TL = TriLayout<NP, WV, LPC>;
     constexpr int kTriSW = TriCfg<NP, WV, LPC>::kSW;
-    const int nstrips = (e.W1 + H - 1 + kTriSW - 1) / kTriSW;
-    const size_t bytes = (size_t)npass * n * nstrips * H * 4 * LPC * TriGran<NP>::NG * 8;
+    const int nstrips = plan.nstrips, npass = plan.passes;
     int rc;
-    if (ctx->tri_bnd.bytes < bytes) {
-        if ((rc = ensure(ctx, ctx->tri_bnd, bytes, "sgbm strip boundary granules"))) return rc;
-        // fresh granules carry tag 0, which no launch uses
-        if ((rc = check_hip(ctx, hipMemsetAsync(ctx->tri_bnd.ptr, 0, ctx->tri_bnd.bytes, ctx->stream),
-                            "sgbm boundary reset")))
-            return rc;
-    }
-    if (!ctx->status.ptr) {
-        // [0] give-up epoch, [2] strip tickets drawn
-        if ((rc = ensure(ctx, ctx->status, 16, "device status words"))) return rc;
-        if ((rc = check_hip(ctx, hipMemsetAsync(ctx->status.ptr, 0, 16, ctx->stream), "status reset")))
-            return rc;
-        ctx->tri_tickets = 0;
-    }
-    // Launch epochs never repeat between two zeroings of the granules: tag 0
-    // means "never written", and when the 16-bit tag wraps every slot is
-    // zeroed again, so a slot carrying this launch's tag was written by it.
-    if ((++ctx->tri_epoch & 0xffffu) == 0) {
-        ++ctx->tri_epoch;
-        if ((rc = check_hip(ctx, hipMemsetAsync(ctx->tri_bnd.ptr, 0, ctx->tri_bnd.bytes, ctx->stream),
-                            "sgbm boundary reset")))
-            return rc;
-    }
-    const unsigned epoch = ctx->tri_epoch;
-    dim3 grid(nstrips * npass * n);
-    unsigned long long* stats = nullptr;
-    // MVSV_TRI_STATS: per-strip summary on stderr; MVSV_TRI_TRACE=path: also
-    // every step's publish / consume time (100 MHz) of every strip, to a file
-    const char* trace_path = std::getenv("MVSV_TRI_TRACE");
-    const bool want_stats = std::getenv("MVSV_TRI_STATS") != nullptr || trace_path;
-    const int trace_h = trace_path ? H : 0;
-    const size_t sb = 8 + 2 * (size_t)trace_h;  // u64 per block
-    if (want_stats) {
-        (void)hipMalloc(&stats, (size_t)grid.x * sb * 8);
-        (void)hipMemset(stats, 0, (size_t)grid.x * sb * 8);
-    }
-    // Strip tickets for every launch (round 4): a launch of at most one block
-    // per CU is not resident all at once when other work shares the GPU
-    // (stream lanes, batches in flight), so blockIdx order would rest on
-    // in-order dispatch; tickets never do.  MVSV_OPT_STRIP_TICKETS = 0 keeps
-    // blockIdx order for A/B runs.
-    const bool tickets = ctx->opt.strip_tickets != 0;
+    unsigned epoch;
+    long long ticket0;
+    if ((rc = strip_begin(ctx, ctx->tri_bnd, 16, &epoch, &ticket0))) return rc;
+    dim3 grid((unsigned)plan.blocks);
+    // tri_stats: per-strip summary on stderr; tri_trace: also every step's
+    // publish / consume time (100 MHz) of every strip, to a file
+    const bool trace = !ctx->opt.tri_trace.empty();
+    const size_t sb = 8 + (trace ? 2 * (size_t)H : 0);  // u64 per block
+    unsigned long long* stats = (ctx->opt.tri_stats || trace) ? strip_stats_alloc(ctx, (size_t)grid.x * sb * 8) : nullptr;
+    const int trace_h = stats && trace ? H : 0;
     if (TL::kBytes > 65536 &&
         (rc = check_hip(ctx, hipFuncSetAttribute((const void*)sgbm_tri_kernel<NP, WV, LPC, AccT, NW, RES>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)TL::kBytes),
@@ -2307,17 +2193,13 @@ int launch_tri_wv(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const void* Cv,
     hipLaunchKernelGGL((sgbm_tri_kernel<NP, WV, LPC, AccT, NW, RES>), grid, dim3(TriCfg<NP, WV, LPC>::kThreads), TL::kBytes,
                        ctx->stream, Cv, Av, plane, (AccT*)ctx->dummy.ptr, H, e.W1, e.D, npass, e.P1,
                        e.P2, (unsigned long long*)ctx->tri_bnd.ptr, epoch, n, nstrips,
-                       (int*)ctx->status.ptr, ctx->opt.spin_limit, ctx->report_target, stats, trace_h,
-                       tickets ? (long long)ctx->tri_tickets : -1ll);
+                       (int*)ctx->status.ptr, ctx->opt.spin_limit, ctx->report_target, stats, trace_h, ticket0);
     rc = check_hip(ctx, hipGetLastError(), "sgbm sheared-strip path kernel");
-    if (rc == MVSV_OK && tickets) ctx->tri_tickets += grid.x;  // one ticket per block (u32 wrap is harmless)
-    if (want_stats) {
-        (void)hipStreamSynchronize(ctx->stream);
-        std::vector<unsigned long long> h((size_t)grid.x * sb);
-        (void)hipMemcpy(h.data(), stats, h.size() * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(stats);
-        if (trace_path) {
-            if (FILE* fp = std::fopen(trace_path, "wb")) {
+    if (rc == MVSV_OK && ticket0 >= 0) ctx->tri_tickets += grid.x;  // one ticket per block (u32 wrap is harmless)
+    std::vector<unsigned long long> h;
+    if (stats && strip_stats_read(ctx, stats, (size_t)grid.x * sb, &h)) {
+        if (trace_h) {
+            if (FILE* fp = std::fopen(ctx->opt.tri_trace.c_str(), "wb")) {
                 const unsigned long long hdr[8] = {grid.x, sb, (unsigned long long)H, (unsigned long long)nstrips,
                                                    (unsigned long long)npass, (unsigned long long)n,
                                                    (unsigned long long)kTriSW, (unsigned long long)e.W1};
@@ -2350,122 +2232,62 @@ int launch_tri_wv(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const void* Cv,
     return rc;
 }
 
-// Strip width: wide strips while the launch has at least one block per CU
-// (frame batches: the kernel is VALU-bound and wide strips share the step
-// barrier and the exchange wave among 15 compute waves); narrow strips when it
-// would not (one 640x480 frame: 34 wide blocks on 256 CUs, each strip step the
-// serial VALU work of 15 waves on one CU) -- the chain of strips then spreads
-// over more CUs at about half the per-step work (640x480, one frame: strips
-// 0.62 -> 0.41 ms; 4 waves per strip: 0.42 ms, its longer chain of strips
-// eats the shorter steps).  MVSV_OPT_STRIP_WAVES forces either shape.
+// The strip kernel of the plan's shape: 32 lanes per column (D = 256 launches
+// too small for wide strips), else wide or narrow strips on 16 lanes.
 // (Round 3's 8-lanes-per-column variant, LPC = 8, measured slower and is no
 // longer instantiated; the kernel keeps the LPC parameter.)
-template <int NP, int LPC, typename AccT, bool NW, bool RES>
-int launch_tri_lpc(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const void* Cv, AccT* Av, size_t plane,
-                   int npass)
-{
-    constexpr int wide = tri_wide_waves<NP, LPC>(), narrow = tri_narrow_waves<NP, LPC>();
-    constexpr int cpw = 64 / LPC;
-    int wv = ctx->opt.strip_waves;
-    if (wv != wide && wv != narrow) {
-        const long long blocks = (long long)npass * n * ((e.W1 + H - 1 + cpw * wide - 1) / (cpw * wide));
-        wv = blocks < ctx->cus ? narrow : wide;
-    }
-    if (wv == narrow) return launch_tri_wv<NP, narrow, LPC, AccT, NW, RES>(ctx, n, H, e, Cv, Av, plane, npass);
-    return launch_tri_wv<NP, wide, LPC, AccT, NW, RES>(ctx, n, H, e, Cv, Av, plane, npass);
-}
-
 template <int NP, typename AccT, bool NW, bool RES>
-int launch_tri(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, const void* Cv, AccT* Av, size_t plane,
-               int npass)
+int launch_strips(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, const SgbmEff& e, const void* Cv, AccT* Av,
+                  size_t plane)
 {
     if constexpr (NP == 8 && !RES) {
-        // D = 256 launches that would run narrow strips (one or two frames):
-        // 32 lanes per column (MVSV_TRI32 = 0: the 16-lane narrow strips)
-        constexpr int wide = tri_wide_waves<NP, 16>();
-        const long long blocks = (long long)npass * n * ((e.W1 + H - 1 + 4 * wide - 1) / (4 * wide));
-        if (ctx->opt.tri32 && ctx->opt.strip_waves == 0 && blocks < ctx->cus)
-            return launch_tri_wv<NP / 2, tri_narrow_waves<NP / 2, 32>(), 32, AccT, NW, RES>(ctx, n, H, e, Cv, Av,
-                                                                                           plane, npass);
+        if (plan.lpc == 32)
+            return launch_tri_wv<NP / 2, tri_narrow_waves(NP / 2, 32), 32, AccT, NW, RES>(ctx, plan, n, H, e, Cv, Av,
+                                                                                         plane);
     }
-    return launch_tri_lpc<NP, 16, AccT, NW, RES>(ctx, n, H, e, Cv, Av, plane, npass);
+    constexpr int wide = tri_wide_waves(NP, 16), narrow = tri_narrow_waves(NP, 16);
+    if (plan.lpc != 16 || (plan.waves != wide && plan.waves != narrow))
+        return set_error(ctx, MVSV_E_HIP, "internal: no strip kernel of the SGBM plan's shape");
+    if (plan.waves == narrow) return launch_tri_wv<NP, narrow, 16, AccT, NW, RES>(ctx, plan, n, H, e, Cv, Av, plane);
+    return launch_tri_wv<NP, wide, 16, AccT, NW, RES>(ctx, plan, n, H, e, Cv, Av, plane);
 }
 
 // Sheared-strip schedule: the down pass ((1,1) (0,1) (-1,1)), the up pass
 // ((1,-1) (0,-1) (-1,-1), MODE_HH) and the L->R lines each write their own
-// accumulator plane; the L->R lines run on a second stream beside the strip
-// kernel, and the final kernel (R->L + WTA) sums the planes.  The direction
-// passes read Cin -- the cost volume, or (RES) its residual plane -- and the
-// final kernel the cost volume Cv.
+// accumulator plane; the L->R lines run where plan.lines_aux says (0 = after
+// the strip kernel on the same stream, 1 = on the second stream launched
+// before it, 2 = on the second stream after it), and the final kernel (R->L +
+// WTA) sums the planes.  The direction passes read Cin -- the cost volume, or
+// (RES) its residual plane -- and the final kernel the cost volume Cv.
 template <int NP, typename AccT, bool NW, bool RES = false>
-int launch_paths_tri(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* Cv, const void* Cin,
-                     AccT* Av, size_t plane, int16_t* raw, const uint16_t* Mv = nullptr)
+int launch_paths_tri(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, int16_t* Cv,
+                     const void* Cin, AccT* Av, int16_t* raw, const uint16_t* Mv = nullptr)
 {
     hipStream_t s = ctx->stream;
     int rc;
-    if (!ctx->aux) {
-        if ((rc = check_hip(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking), "aux stream")) ||
-            (rc = check_hip(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming), "event")) ||
-            (rc = check_hip(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming), "event")))
-            return rc;
-    }
-    const int npass = e.fullDP ? 2 : 1;
-    AccT* dummy = (AccT*)ctx->dummy.ptr;
+    if ((rc = ensure_aux(ctx))) return rc;
+    const int npass = plan.passes;
+    const size_t plane = (size_t)n * H * e.W1 * e.D;
     {
         StageTimer tm(ctx, kStagePath);
         if ((rc = check_hip(ctx, hipEventRecord(ctx->ev_fork, s), "fork")) ||
             (rc = check_hip(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0), "fork wait")))
             return rc;
-        // lines_aux < 0 (default): beside the strips when the launch is small
-        // (the strips then occupy a fraction of the CUs -- one frame: ~60 of
-        // 256 -- and the L->R lines fill idle ones); after them for batches,
-        // where both kernels saturate the GPU and running them together was
-        // measured slower
-        // Round 4: with the residual input the line kernel needs 53 VGPRs and
-        // the wide strip kernel 103, so a line wave fits beside a strip block
-        // on every SIMD -- launched after the strips on the second stream, the
-        // lines fill the strips' step-barrier and hand-off waits (one batch of
-        // 8 frames: 4.49 -> 4.37-4.40 ms, MI355X r04d A/B)
-        // Round 6: "small" counts the strip blocks the launch will really have
-        // (launch_tri_lpc picks narrow strips -- 1.7x the blocks -- whenever the
-        // wide ones would not fill the CUs): beside the strips only while those
-        // occupy at most 60 % of the CUs (one 1280x960 frame: 125 narrow D = 256
-        // blocks, 132 narrow D = 128 MODE_HH blocks).  Two config-5 frames (D 256,
-        // 248 narrow blocks) had the lines beside them at 2.68 ms instead of
-        // 0.66 for one frame (r04g c5_frame.jsonl): every CU held a strip.
-        int aux_mode = ctx->opt.lines_aux;
-        if (aux_mode < 0) {
-            constexpr int wide = tri_wide_waves<NP>(), narrow = tri_narrow_waves<NP>();
-            auto nblocks = [&](int wv) {
-                return (long long)npass * n * ((e.W1 + H - 1 + 4 * wv - 1) / (4 * wv));
-            };
-            const int wv = ctx->opt.strip_waves == wide || ctx->opt.strip_waves == narrow
-                               ? ctx->opt.strip_waves
-                               : (nblocks(wide) < ctx->cus ? narrow : wide);
-            // Round 6: byte / u16 planes at D <= 64 run the lines beside the
-            // strips in batches too (liveDisparity default, 1280x960 x 4 / x 8:
-            // 1.97 -> 1.87, 3.13 -> 2.88 ms); D = 256 keeps them after the
-            // strips (x 4: 4.90 -> 5.7 ms beside, x 8: 8.60 -> 8.50;
-            // profiles/r06/aux/lines_aux_ab.txt)
-            aux_mode = 5 * nblocks(wv) <= 3 * ctx->cus ? 1 : ((RES || NP <= 2) ? 2 : 0);
-        }
-        hipStream_t ls = aux_mode ? ctx->aux : s;
+        hipStream_t ls = plan.lines_aux ? ctx->aux : s;
         auto lines = [&]() {
             StageTimer tl(ctx, kStageLines, ls);
             dim3 grid((num_lines(1, 0, e.W1, H) + 15) / 16, n);
             hipLaunchKernelGGL((sgbm_path16_kernel<NP, true, AccT, NW, RES>), grid, dim3(256), 0, ls, Cin,
-                               acc_add(Av, (ptrdiff_t)npass * (ptrdiff_t)plane), dummy, H, e.W1,
+                               acc_add(Av, (ptrdiff_t)npass * (ptrdiff_t)plane), (AccT*)ctx->dummy.ptr, H, e.W1,
                                e.D, 1, 0, e.P1, e.P2);
         };
-        // lines_aux: 0 = after the strip kernel on the same stream, 1 = on the
-        // second stream launched before it, 2 = on the second stream after it
-        if (aux_mode == 1) lines();
+        if (plan.lines_aux == 1) lines();
         if ((rc = check_hip(ctx, hipGetLastError(), "sgbm L->R lines"))) return rc;
         {
             StageTimer ts(ctx, kStageStrips);
-            if ((rc = launch_tri<NP, AccT, NW, RES>(ctx, n, H, e, Cin, Av, plane, npass))) return rc;
+            if ((rc = launch_strips<NP, AccT, NW, RES>(ctx, plan, n, H, e, Cin, Av, plane))) return rc;
         }
-        if (aux_mode != 1) lines();
+        if (plan.lines_aux != 1) lines();
         if ((rc = check_hip(ctx, hipEventRecord(ctx->ev_join, ctx->aux), "join")) ||
             (rc = check_hip(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0), "join wait")))
             return rc;
@@ -2478,34 +2300,16 @@ int launch_paths_tri(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16
     return check_hip(ctx, hipGetLastError(), "sgbm path kernels (sheared strips)");
 }
 
+// schedule 0 on 16 lanes: one launch per direction into one plane
 template <int NP, typename AccT>
-int launch_paths16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* Cv, AccT* Av,
-                   int16_t* raw)
+int launch_paths_lines16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* Cv, AccT* Av, int16_t* raw)
 {
     hipStream_t s = ctx->stream;
-    static const int dirs_sgbm[4][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}};
-    static const int dirs_hh[7][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}, {1, -1}, {0, -1}, {-1, -1}};
-    int rc;
-    if ((rc = ensure(ctx, ctx->dummy, 512 * 16 * 2 * NP, "sgbm dummy slots"))) return rc;
-    if ((rc = ensure(ctx, ctx->keys, (size_t)n * H * W * 4, "sgbm right-view keys"))) return rc;
     AccT* dummy = (AccT*)ctx->dummy.ptr;
-    const size_t plane = (size_t)n * H * e.W1 * e.D;
-    // u8 / u16 planes (P2 > 5) at D = 256 (liveDisparity, config 5): the
-    // no-wrap recurrence wherever no int16 can wrap -- its adds / subtracts
-    // run at the full 32-bit rate, so it is the cheaper form here too (one
-    // frame 2.04 -> 1.99 ms, profiles/r04/c5ab04); other D keep the general
-    // form (compile time)
-    if (use_strips(ctx, e, H)) {
-        if constexpr (NP == 8)
-            if (sgbm_no_wrap(e)) return launch_paths_tri<NP, AccT, true>(ctx, n, H, W, e, Cv, Cv, Av, plane, raw);
-        return launch_paths_tri<NP, AccT, false>(ctx, n, H, W, e, Cv, Cv, Av, plane, raw);
-    }
     const int ndir = e.fullDP ? 7 : 4;
     for (int k = 0; k < ndir; k++) {
-        int dx = e.fullDP ? dirs_hh[k][0] : dirs_sgbm[k][0];
-        int dy = e.fullDP ? dirs_hh[k][1] : dirs_sgbm[k][1];
-        int nl = num_lines(dx, dy, e.W1, H);
-        dim3 grid((nl + 15) / 16, n);
+        const int dx = kPathDirs[k][0], dy = kPathDirs[k][1];
+        dim3 grid((num_lines(dx, dy, e.W1, H) + 15) / 16, n);
         StageTimer tm(ctx, kStagePath);
         if (k == 0)
             hipLaunchKernelGGL((sgbm_path16_kernel<NP, true, AccT>), grid, dim3(256), 0, s, Cv, Av,
@@ -2515,21 +2319,19 @@ int launch_paths16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t
                                Av, dummy, H, e.W1, e.D, dx, dy, e.P1, e.P2);
     }
     StageTimer tm(ctx, kStageFinal);
-    launch_final16<NP, 1, AccT>(ctx, n, H, W, e, Cv, Av, plane, raw);
+    launch_final16<NP, 1, AccT>(ctx, n, H, W, e, Cv, Av, (size_t)n * H * e.W1 * e.D, raw);
     return check_hip(ctx, hipGetLastError(), "sgbm path kernels (16-lane)");
 }
 
+// the generic kernels: one wave per scanline, NP = ceil(D / 128) pairs per lane
 template <int NP, typename AccT>
 int launch_paths(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* Cv, AccT* Av,
                  int16_t* raw)
 {
     hipStream_t s = ctx->stream;
-    static const int dirs_sgbm[4][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}};
-    static const int dirs_hh[7][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}, {1, -1}, {0, -1}, {-1, -1}};
     const int ndir = e.fullDP ? 7 : 4;
     for (int k = 0; k < ndir; k++) {
-        int dx = e.fullDP ? dirs_hh[k][0] : dirs_sgbm[k][0];
-        int dy = e.fullDP ? dirs_hh[k][1] : dirs_sgbm[k][1];
+        const int dx = kPathDirs[k][0], dy = kPathDirs[k][1];
         int nl = num_lines(dx, dy, e.W1, H);
         dim3 grid((nl + 3) / 4, n);
         StageTimer tm(ctx, kStagePath);
@@ -2558,22 +2360,23 @@ int launch_paths(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* 
     return check_hip(ctx, hipGetLastError(), "sgbm path kernels");
 }
 
+// Directions side by side: one plane per direction (plan.nplanes of them; the
+// split form has the R->L direction as one more chain set and the WTA on its
+// own), then the final kernel over the planes.
 template <int NP, typename AccT, bool NW, bool RES = false, int LPC = 16>
-int launch_paths_dirs(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* Cv, const void* Cin,
-                      AccT* Av, int16_t* raw, const uint16_t* Mv = nullptr)
+int launch_paths_dirs(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, int16_t* Cv,
+                      const void* Cin, AccT* Av, int16_t* raw, const uint16_t* Mv = nullptr)
 {
-    static const int dirs_sgbm[4][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}};
-    static const int dirs_hh[7][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}, {1, -1}, {0, -1}, {-1, -1}};
-    // split form: the R->L direction as one more chain set, the WTA on its own
     constexpr bool kPlainPlanes = std::is_same<AccT, uint16_t>::value || std::is_same<AccT, uint8_t>::value;
-    const bool split = !RES && kPlainPlanes && wta_split(ctx, e);
-    const int ndir = (e.fullDP ? 7 : 4) + (split ? 1 : 0);
+    const int ndir = plan.nplanes;
+    if (plan.split && (RES || !kPlainPlanes))
+        return set_error(ctx, MVSV_E_HIP, "internal: the SGBM plan splits the WTA on packed planes");
     PathDirs pd{};
     int maxnl = 0;
     for (int k = 0; k < ndir; k++) {
-        const bool rl = split && k == ndir - 1;
-        pd.dx[k] = rl ? -1 : e.fullDP ? dirs_hh[k][0] : dirs_sgbm[k][0];
-        pd.dy[k] = rl ? 0 : e.fullDP ? dirs_hh[k][1] : dirs_sgbm[k][1];
+        const int* d = kPathDirs[plan.split && k == ndir - 1 ? 7 : k];
+        pd.dx[k] = d[0];
+        pd.dy[k] = d[1];
         maxnl = std::max(maxnl, num_lines(pd.dx[k], pd.dy[k], e.W1, H));
     }
     const size_t plane = (size_t)n * H * e.W1 * e.D;
@@ -2586,7 +2389,7 @@ int launch_paths_dirs(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int1
     }
     StageTimer tm(ctx, kStageFinal);
     if constexpr (kPlainPlanes) {
-        if (split) {
+        if (plan.split) {
             constexpr int LPP = 2 * NP * LPC / 8;  // D / 8
             if (e.uniq > 0)
                 hipLaunchKernelGGL((sgbm_wta_planes_kernel<AccT, true, LPP>), dim3(H, n), dim3(kWtaThreads), 0,
@@ -2604,92 +2407,146 @@ int launch_paths_dirs(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int1
     return check_hip(ctx, hipGetLastError(), "sgbm path kernels (directions side by side)");
 }
 
-// Rv: the residual plane written by the cost kernel (nullptr: none; only ever
-// set in the no-wrap regime with 3 * P2 <= 15, use_residual)
-template <int NP>
-int launch_paths16_acc(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* Cv,
-                       const uint8_t* Rv, const uint16_t* Mv, void* Av, int16_t* raw)
+// 16 lanes on byte / u16 planes.  The final kernel sums the planes in the
+// plane's element type; the strips run the no-wrap recurrence at D = 256 only
+// (plan.nw; other D keep the general form: compile time).
+template <int NP, typename AccT>
+int launch_plain16(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, int16_t* Cv, AccT* Av,
+                   int16_t* raw)
 {
-    if (path_schedule(ctx, e, H, n) == 2) {
-        int rc;
-        if ((rc = ensure(ctx, ctx->dummy, 512 * 16 * 2 * NP, "sgbm dummy slots"))) return rc;
-        if ((rc = ensure(ctx, ctx->keys, (size_t)n * H * W * 4, "sgbm right-view keys"))) return rc;
-        // one plane per direction: a delta <= P2 in a nibble (4 or 7 of them <= 105
-    // per byte lane), a byte (when all directions' sum fits) or a u16
-        if (e.P2 <= 15) {
-            if (sgbm_no_wrap(e)) {
-                if constexpr (NP <= 4)
-                    if (Rv) return launch_paths_dirs<NP, nib2_t, true, true>(ctx, n, H, W, e, Cv, Rv, (nib2_t*)Av, raw, Mv);
-                return launch_paths_dirs<NP, nib2_t, true>(ctx, n, H, W, e, Cv, Cv, (nib2_t*)Av, raw);
-            }
-            return launch_paths_dirs<NP, nib2_t, false>(ctx, n, H, W, e, Cv, Cv, (nib2_t*)Av, raw);
-        }
-        // the final kernel sums the planes in the plane's element type
-        if (acc_is_u8(e)) return launch_paths_dirs<NP, uint8_t, false>(ctx, n, H, W, e, Cv, Cv, (uint8_t*)Av, raw);
-        return launch_paths_dirs<NP, uint16_t, false>(ctx, n, H, W, e, Cv, Cv, (uint16_t*)Av, raw);
-    }
-    if (use_strips(ctx, e, H) && acc_is_nib(e)) {
-        int rc;
-        if ((rc = ensure(ctx, ctx->dummy, 512 * 16 * 2 * NP, "sgbm dummy slots"))) return rc;
-        if ((rc = ensure(ctx, ctx->keys, (size_t)n * H * W * 4, "sgbm right-view keys"))) return rc;
-        const size_t plane = (size_t)n * H * e.W1 * e.D;
-        if (sgbm_no_wrap(e)) {
-            if constexpr (NP <= 4)
-                if (Rv) return launch_paths_tri<NP, nib2_t, true, true>(ctx, n, H, W, e, Cv, Rv, (nib2_t*)Av, plane, raw, Mv);
-            return launch_paths_tri<NP, nib2_t, true>(ctx, n, H, W, e, Cv, Cv, (nib2_t*)Av, plane, raw);
-        }
-        return launch_paths_tri<NP, nib2_t, false>(ctx, n, H, W, e, Cv, Cv, (nib2_t*)Av, plane, raw);
-    }
-    if (acc_is_u8(e)) return launch_paths16<NP, uint8_t>(ctx, n, H, W, e, Cv, (uint8_t*)Av, raw);
-    return launch_paths16<NP, uint16_t>(ctx, n, H, W, e, Cv, (uint16_t*)Av, raw);
+    if (plan.sched == 2) return launch_paths_dirs<NP, AccT, false>(ctx, plan, n, H, W, e, Cv, Cv, Av, raw);
+    if (plan.sched == 0) return launch_paths_lines16<NP, AccT>(ctx, n, H, W, e, Cv, Av, raw);
+    if constexpr (NP == 8)
+        if (plan.nw) return launch_paths_tri<NP, AccT, true>(ctx, plan, n, H, W, e, Cv, Cv, Av, raw);
+    return launch_paths_tri<NP, AccT, false>(ctx, plan, n, H, W, e, Cv, Cv, Av, raw);
 }
 
-// D = 16 (captureDisparity's create(0, 16, 5, 200, 800)): the directions side
-// by side at 8 lanes per line / row (one disparity pair per lane), in every
-// launch shape -- the per-pixel work is small enough that the planes' traffic
-// never outweighs the single-frame latency of a strip chain.  Planes as in
-// launch_paths16_acc's side-by-side branch: nibbles (P2 <= 15), else bytes or
-// u16.
-int launch_paths_d16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* Cv, void* Av,
-                     int16_t* raw)
+// The 16-lane kernels (D = 32 NP): the template instance for the plan's
+// schedule, plane element, recurrence and cost input (Rv: the residual plane)
+template <int NP>
+int launch_packed16(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, int16_t* Cv,
+                    const uint8_t* Rv, const uint16_t* Mv, void* Av, int16_t* raw)
+{
+    if (plan.acc == kAccU8) return launch_plain16<NP, uint8_t>(ctx, plan, n, H, W, e, Cv, (uint8_t*)Av, raw);
+    if (plan.acc == kAccU16) return launch_plain16<NP, uint16_t>(ctx, plan, n, H, W, e, Cv, (uint16_t*)Av, raw);
+    nib2_t* A = (nib2_t*)Av;
+    const bool side = plan.sched == 2;
+    if constexpr (NP <= 4)
+        if (plan.residual)
+            return side ? launch_paths_dirs<NP, nib2_t, true, true>(ctx, plan, n, H, W, e, Cv, Rv, A, raw, Mv)
+                        : launch_paths_tri<NP, nib2_t, true, true>(ctx, plan, n, H, W, e, Cv, Rv, A, raw, Mv);
+    if (plan.nw)
+        return side ? launch_paths_dirs<NP, nib2_t, true>(ctx, plan, n, H, W, e, Cv, Cv, A, raw)
+                    : launch_paths_tri<NP, nib2_t, true>(ctx, plan, n, H, W, e, Cv, Cv, A, raw);
+    return side ? launch_paths_dirs<NP, nib2_t, false>(ctx, plan, n, H, W, e, Cv, Cv, A, raw)
+                : launch_paths_tri<NP, nib2_t, false>(ctx, plan, n, H, W, e, Cv, Cv, A, raw);
+}
+
+// D = 16: the directions side by side at 8 lanes per line / row (one disparity
+// pair per lane)
+int launch_packed8(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, int16_t* Cv, void* Av,
+                   int16_t* raw)
+{
+    if (plan.acc == kAccU8)
+        return launch_paths_dirs<1, uint8_t, false, false, 8>(ctx, plan, n, H, W, e, Cv, Cv, (uint8_t*)Av, raw);
+    if (plan.acc == kAccU16)
+        return launch_paths_dirs<1, uint16_t, false, false, 8>(ctx, plan, n, H, W, e, Cv, Cv, (uint16_t*)Av, raw);
+    if (plan.nw) return launch_paths_dirs<1, nib2_t, true, false, 8>(ctx, plan, n, H, W, e, Cv, Cv, (nib2_t*)Av, raw);
+    return launch_paths_dirs<1, nib2_t, false, false, 8>(ctx, plan, n, H, W, e, Cv, Cv, (nib2_t*)Av, raw);
+}
+
+template <int NP>
+int launch_generic(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, int16_t* Cv, void* Av,
+                   int16_t* raw)
+{
+    if (plan.acc == kAccU8) return launch_paths<NP, uint8_t>(ctx, n, H, W, e, Cv, (uint8_t*)Av, raw);
+    return launch_paths<NP, uint16_t>(ctx, n, H, W, e, Cv, (uint16_t*)Av, raw);
+}
+
+// every cached buffer of the call, at the plan's size (0: the call does not touch it)
+int ensure_plan_buffers(mvsv_ctx* ctx, const SgbmPlan& plan)
 {
     int rc;
-    if ((rc = ensure(ctx, ctx->dummy, 512 * 16 * 2, "sgbm dummy slots"))) return rc;
-    if ((rc = ensure(ctx, ctx->keys, (size_t)n * H * W * 4, "sgbm right-view keys"))) return rc;
-    if (e.P2 <= 15) {
-        if (sgbm_no_wrap(e)) return launch_paths_dirs<1, nib2_t, true, false, 8>(ctx, n, H, W, e, Cv, Cv, (nib2_t*)Av, raw);
-        return launch_paths_dirs<1, nib2_t, false, false, 8>(ctx, n, H, W, e, Cv, Cv, (nib2_t*)Av, raw);
+    auto need = [&](DevBuf& b, size_t bytes, const char* what) { return bytes ? ensure(ctx, b, bytes, what) : MVSV_OK; };
+    // boundary granules and status words start zeroed: fresh granules carry
+    // tag 0, which no launch uses; status [0] give-up epoch, [2] strip tickets drawn
+    auto need_zeroed = [&](DevBuf& b, size_t bytes, const char* what) {
+        if (b.bytes >= bytes) return (int)MVSV_OK;
+        if (int r = ensure(ctx, b, bytes, what)) return r;
+        return check_hip(ctx, hipMemsetAsync(b.ptr, 0, b.bytes, ctx->stream), what);
+    };
+    if ((rc = need(ctx->pre, plan.pre, "sgbm BT interval planes")) ||
+        (rc = need(ctx->cost, plan.cost, "sgbm cost volume")) ||
+        (rc = need(ctx->cres, plan.cres, plan.residual ? "sgbm cost residual plane" : "sgbm bit-sliced cost planes")) ||
+        (rc = need(ctx->agg, plan.agg, plan.family == kFamBitslice ? "bit-sliced delta planes"
+                                                                   : "sgbm path-delta accumulator")) ||
+        (rc = need(ctx->raw, plan.raw, "sgbm raw disparity")) ||
+        (rc = need(ctx->keys, plan.keys, "sgbm right-view keys")) ||
+        (rc = need(ctx->dummy, plan.dummy, "sgbm dummy slots")) ||
+        (rc = need_zeroed(ctx->tri_bnd, plan.tri_bnd, "sgbm strip boundary granules")) ||
+        (rc = need_zeroed(ctx->bs_bnd, plan.bs_bnd, "bit-sliced strip boundary granules")))
+        return rc;
+    if (plan.status && !ctx->status.ptr) {
+        if ((rc = need_zeroed(ctx->status, plan.status, "device status words"))) return rc;
+        ctx->tri_tickets = 0;
     }
-    if (acc_is_u8(e)) return launch_paths_dirs<1, uint8_t, false, false, 8>(ctx, n, H, W, e, Cv, Cv, (uint8_t*)Av, raw);
-    return launch_paths_dirs<1, uint16_t, false, false, 8>(ctx, n, H, W, e, Cv, Cv, (uint16_t*)Av, raw);
-}
-
-template <int NP>
-int launch_paths_acc(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* Cv,
-                     void* Av, int16_t* raw)
-{
-    if (acc_is_u8(e)) return launch_paths<NP, uint8_t>(ctx, n, H, W, e, Cv, (uint8_t*)Av, raw);
-    return launch_paths<NP, uint16_t>(ctx, n, H, W, e, Cv, (uint16_t*)Av, raw);
+    return MVSV_OK;
 }
 
 }  // namespace
 
-int sgbm_plan(const mvsv_ctx* ctx, const SgbmEff& e, int n, int H)
+int ensure_aux(mvsv_ctx* ctx)
 {
-    if (e.minX1 >= e.maxX1) return 0;
-    const int sched = path_schedule(ctx, e, H, n);
-    const bool bs = bsgm_eligible(ctx, e, n, H) && (sched == 1 || sched == 2) && ctx->opt.path16 && ctx->opt.tri &&
-                    ctx->opt.cost_fixed_pp && e.SH2 <= 7 && e.SW2 == e.SH2 && cost2_runs(ctx, e);
-    int plan = (bs ? MVSV_PLAN_BITSLICE : 0) | (sched == 2 ? MVSV_PLAN_SIDE : 0) | (sched == 1 ? MVSV_PLAN_STRIPS : 0);
-    if (!bs && use_residual(ctx, e, sched) && cost2_runs(ctx, e)) plan |= MVSV_PLAN_RESIDUAL;
-    return plan;
+    if (ctx->aux) return MVSV_OK;
+    int rc;
+    if ((rc = check_hip(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking), "aux stream")) ||
+        (rc = check_hip(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming), "event")) ||
+        (rc = check_hip(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming), "event")))
+        return rc;
+    return MVSV_OK;
 }
 
-bool sgbm_graphable(const mvsv_ctx* ctx, const SgbmEff& e, int n, int H)
+int strip_begin(mvsv_ctx* ctx, DevBuf& bnd, int tag_bits, unsigned* epoch, long long* ticket0)
 {
-    return e.minX1 < e.maxX1 && e.D <= 512 && path_schedule(ctx, e, H, n) == 2;
+    if ((++ctx->tri_epoch & 0xffffu) == 0) {
+        ++ctx->tri_epoch;
+        if (tag_bits == 16)
+            if (int rc = check_hip(ctx, hipMemsetAsync(bnd.ptr, 0, bnd.bytes, ctx->stream), "strip boundary reset"))
+                return rc;
+    }
+    *epoch = ctx->tri_epoch;
+    *ticket0 = ctx->opt.strip_tickets ? (long long)ctx->tri_tickets : -1ll;
+    return MVSV_OK;
 }
 
+unsigned long long* strip_stats_alloc(mvsv_ctx* ctx, size_t bytes)
+{
+    unsigned long long* stats = nullptr;
+    if (hipMalloc(&stats, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    if (hipMemsetAsync(stats, 0, bytes, ctx->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(stats);
+        return nullptr;
+    }
+    return stats;
+}
+
+bool strip_stats_read(mvsv_ctx* ctx, unsigned long long* stats, size_t words, std::vector<unsigned long long>* h)
+{
+    h->resize(words);
+    const bool ok = hipStreamSynchronize(ctx->stream) == hipSuccess &&
+                    hipMemcpy(h->data(), stats, words * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(stats);
+    if (!ok) (void)hipGetLastError();
+    return ok;
+}
+
+// The pipeline: make the plan, ensure every buffer from it, then prefilter,
+// cost, fix-up, one dispatch on the plan's fields to the path kernels' template
+// instance, post filters.
 int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
                 size_t rs, size_t rfs, int W, int H, const SgbmEff& e, int16_t* out, size_t os,
                 size_t ofs)
@@ -2702,129 +2559,53 @@ int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, c
         return check_hip(ctx, hipGetLastError(), "sgbm fill");
     }
     if (e.D > 512) return set_error(ctx, MVSV_E_INVALID_ARG, "numDisparities > 512 not supported");
-    const size_t plane = (size_t)W * H;
-    const size_t vol = (size_t)e.W1 * H * e.D;
-    if ((rc = ensure(ctx, ctx->pre, (size_t)n * 2 * e.cn * plane * 8, "sgbm BT interval planes"))) return rc;
-    // (rows padded to a multiple of 4 pixels: the bit-sliced pipeline's layout)
-    if ((rc = ensure(ctx, ctx->cost, (size_t)n * H * ((e.W1 + 3) & ~3) * e.D * 2, "sgbm cost volume"))) return rc;
-    // bit-sliced MODE_HH paths (round 5, mvsv_bsgm.hip): the cost kernel writes
-    // the C' bit planes instead of the residual nibbles; the planes of the
-    // direction passes are sized by bsgm_paths
-    // accumulator planes: one per concurrently written direction group
-    const int sched = path_schedule(ctx, e, H, n);
-    // (frame batches: the bit-sliced strips; launches too small to fill the
-    // GPU with strips -- one camera frame, schedule 2 -- the bit-sliced
-    // directions side by side, each on its own chains: bsgm_paths)
-    const bool bs = bsgm_eligible(ctx, e, n, H) && (sched == 1 || sched == 2) && ctx->opt.path16 && ctx->opt.tri &&
-                    ctx->opt.cost2 && ctx->opt.cost_fixed_pp && e.SH2 <= 7 && e.SW2 == e.SH2;
-    uint32_t* Bv = nullptr;
-    const int nplanes = sched == 2 ? (e.fullDP ? 7 : 4) + (wta_split(ctx, e) ? 1 : 0)
-                                   : sched == 1 ? (e.fullDP ? 3 : 2) : 1;
-    // 4-bit planes: one per direction (side by side, P2 <= 15) or per strip
-    // pass + lines; bytes / u16 otherwise (side by side: one delta <= P2 each)
-    const bool nib = (sched == 2 && e.P2 <= 15) || (sched == 1 && nplanes > 1 && acc_is_nib(e));
-    const bool u8 = acc_is_u8(e);
-    if (!bs && (rc = ensure(ctx, ctx->agg, nib ? (size_t)nplanes * n * vol / 2
-                                               : (size_t)nplanes * n * vol * (u8 ? 1 : 2),
-                            "sgbm path-delta accumulator")))
-        return rc;
-    if ((rc = ensure(ctx, ctx->raw, (size_t)n * plane * 2, "sgbm raw disparity"))) return rc;
-    // residual plane for the direction passes (0.5 byte per cost instead of 2)
-    // + the per-pixel cost minimum (u16 per cost column) behind it
-    uint8_t* Rv = nullptr;
-    uint16_t* Mv = nullptr;
-    if (bs) {
-        const size_t bbytes = (bsgm_plane_bytes(n, H, e.W1) + 255) & ~(size_t)255;
-        if ((rc = ensure(ctx, ctx->cres, bbytes + (size_t)n * e.W1 * H * 2, "sgbm bit-sliced cost planes")))
-            return rc;
-        Bv = (uint32_t*)ctx->cres.ptr;
-        Mv = (uint16_t*)((uint8_t*)ctx->cres.ptr + bbytes);
-    } else if (use_residual(ctx, e, sched)) {
-        const size_t rbytes = (n * vol / 2 + 255) & ~(size_t)255;
-        if ((rc = ensure(ctx, ctx->cres, rbytes + (size_t)n * e.W1 * H * 2, "sgbm cost residual plane"))) return rc;
-        Rv = (uint8_t*)ctx->cres.ptr;
-        Mv = (uint16_t*)(Rv + rbytes);
-    }
+    const SgbmPlan plan = sgbm_make_plan(ctx, e, n, W, H);
+    if ((rc = ensure_plan_buffers(ctx, plan))) return rc;
     uint64_t* pre = (uint64_t*)ctx->pre.ptr;
     int16_t* Cv = (int16_t*)ctx->cost.ptr;
     void* Sv = ctx->agg.ptr;
     int16_t* raw = (int16_t*)ctx->raw.ptr;
-    const unsigned epoch0 = ctx->tri_epoch;
+    // the residual plane (0.5 byte per cost) or the bit-sliced C' planes, and
+    // the per-pixel cost minimum (u16 per cost column) behind either
+    const bool bits = plan.family == kFamBitslice;
+    uint32_t* Bv = bits ? (uint32_t*)ctx->cres.ptr : nullptr;
+    uint8_t* Rv = plan.residual ? (uint8_t*)ctx->cres.ptr : nullptr;
+    uint16_t* Mv = plan.cres ? (uint16_t*)((uint8_t*)ctx->cres.ptr + plan.cres_min) : nullptr;
 
     if ((rc = launch_prefilter(ctx, n, L, ls, lfs, R, rs, rfs, W, H, e.ftzero, e.cn, pre))) return rc;
-
-    // cost volume: one block per TX x TY tile; keep the LDS image <= 160 KiB
-    // Taller tiles re-read fewer halo rows (2*SH2 per tile); shorter ones give
-    // small batches enough blocks (>= 2 per CU) to fill the chip.
-    int TY = 16;
-    if (ctx->opt.cost_ty > 0) {
-        TY = ctx->opt.cost_ty;
-    } else if (H >= 256) {
-        const int TX = cost2_layout(e.D, e.SW2, 120).TX;
-        const long tiles_x = (e.W1 + TX - 1) / TX;
-        auto tiles = [&](int ty) { return tiles_x * ((H + ty - 1) / ty) * n; };
-        TY = 120;
-        if (tiles(120) < 1024) {
-            // small launches: least per-CU work, tiles per CU x rows per tile
-            // incl. the 2*SH2 halo, a lone tile on a CU counted 1.5x (8 waves
-            // hide less latency than 16); measured against forced heights: one
-            // 640x480 frame 0.097 -> 0.073 ms, two 0.124 -> 0.110 ms, one
-            // 1280x960 frame 0.227 -> 0.187 ms
-            long best = -1;
-            for (int ty : kCostTileHeights) {
-                const long per_cu = (tiles(ty) + ctx->cus - 1) / ctx->cus;
-                const long c = per_cu * (ty + 2 * e.SH2) * (per_cu == 1 ? 3 : 2);
-                if (best < 0 || c < best) {
-                    best = c;
-                    TY = ty;
-                }
-            }
-        }
-    }
-    bool pinned_hh = false;
-    if ((rc = launch_cost(ctx, n, W, H, e, TY, pre, Cv, &Rv, Mv, &pinned_hh, &Bv))) return rc;
-    if (bs && !Bv) {
-        // the cost kernel could not write the planes (a launch shape without
-        // the D = 128 register-ring kernel): the packed kernels on C
-        if ((rc = ensure(ctx, ctx->agg, nib ? (size_t)nplanes * n * vol / 2
-                                            : (size_t)nplanes * n * vol * (u8 ? 1 : 2),
-                         "sgbm path-delta accumulator")))
-            return rc;
-        Sv = ctx->agg.ptr;
-    }
-
-    if (Bv) {
+    if ((rc = launch_cost(ctx, plan, n, W, H, e, pre, Cv, Rv, Mv, Bv))) return rc;
+    if (bits) {
         // bit-sliced layouts (MODE_SGBM: copied rows / column 0; MODE_HH: pinned
         // by the cost kernel)
         if ((rc = bsgm_cost_fixup(ctx, n, H, e, Cv, Bv, Mv))) return rc;
-    } else if (H > 1 && !pinned_hh) {
-        // OpenCV 3.4's never-recomputed rows and column 0 (mvsv_cost.hip)
+    } else if (H > 1 && !(plan.cost2 && e.fullDP)) {
+        // OpenCV 3.4's never-recomputed rows and column 0 (mvsv_cost.hip; the
+        // register-ring kernel pins MODE_HH's itself)
         if ((rc = launch_cost_fixup(ctx, n, H, e, Cv, Rv, Mv))) return rc;
     }
 
-    const int np = (e.D + 127) / 128;
-    const bool wide = ctx->opt.path16 && (e.D == 32 || e.D == 64 || e.D == 128 || e.D == 256);
-    if (Bv) {
-        rc = bsgm_paths(ctx, n, H, W, e, Cv, Bv, Mv, raw, sched == 2);
-    } else if (e.D == 16 && sched == 2) {
-        rc = launch_paths_d16(ctx, n, H, W, e, Cv, Sv, raw);
-    } else if (wide) {
+    switch (plan.family) {
+    case kFamBitslice: rc = bsgm_paths(ctx, plan, n, H, W, e, Cv, Bv, Mv, raw); break;
+    case kFamPacked8: rc = launch_packed8(ctx, plan, n, H, W, e, Cv, Sv, raw); break;
+    case kFamPacked16:
         switch (e.D) {
-        case 32: rc = launch_paths16_acc<1>(ctx, n, H, W, e, Cv, Rv, Mv, Sv, raw); break;
-        case 64: rc = launch_paths16_acc<2>(ctx, n, H, W, e, Cv, Rv, Mv, Sv, raw); break;
-        case 128: rc = launch_paths16_acc<4>(ctx, n, H, W, e, Cv, Rv, Mv, Sv, raw); break;
-        default: rc = launch_paths16_acc<8>(ctx, n, H, W, e, Cv, nullptr, nullptr, Sv, raw); break;
+        case 32: rc = launch_packed16<1>(ctx, plan, n, H, W, e, Cv, Rv, Mv, Sv, raw); break;
+        case 64: rc = launch_packed16<2>(ctx, plan, n, H, W, e, Cv, Rv, Mv, Sv, raw); break;
+        case 128: rc = launch_packed16<4>(ctx, plan, n, H, W, e, Cv, Rv, Mv, Sv, raw); break;
+        default: rc = launch_packed16<8>(ctx, plan, n, H, W, e, Cv, nullptr, nullptr, Sv, raw); break;
         }
-    } else if (np == 1) rc = launch_paths_acc<1>(ctx, n, H, W, e, Cv, Sv, raw);
-    else if (np == 2) rc = launch_paths_acc<2>(ctx, n, H, W, e, Cv, Sv, raw);
-    else rc = launch_paths_acc<4>(ctx, n, H, W, e, Cv, Sv, raw);
+        break;
+    default:
+        rc = e.D <= 128   ? launch_generic<1>(ctx, plan, n, H, W, e, Cv, Sv, raw)
+             : e.D <= 256 ? launch_generic<2>(ctx, plan, n, H, W, e, Cv, Sv, raw)
+                          : launch_generic<4>(ctx, plan, n, H, W, e, Cv, Sv, raw);
+    }
     if (rc) return rc;
 
     // a strip launch of this call that gave up a wait poisons the median's output
-    const bool strips_ran = ctx->tri_epoch != epoch0;
     StageTimer tm(ctx, kStagePost);
-    const int* poison = strips_ran ? (const int*)ctx->status.ptr : nullptr;
-    if ((rc = median3x3_device(ctx, n, raw, W, plane, out, os, ofs, W, H, poison, ctx->tri_epoch, e.invalid)))
+    const int* poison = plan.sched == 1 ? (const int*)ctx->status.ptr : nullptr;
+    if ((rc = median3x3_device(ctx, n, raw, W, (size_t)W * H, out, os, ofs, W, H, poison, ctx->tri_epoch, e.invalid)))
         return rc;
     if (e.speckle_window > 0)
         return speckle_device(ctx, n, out, os, ofs, W, H, e.invalid, e.speckle_window, e.speckle_diff);

@@ -71,16 +71,29 @@ def test_d16_batch_matches_frames(gpu, mvsv, oracle, mode):
         assert np.array_equal(out[i], want), f"frame {i}: " + report(out[i], want)
 
 
-@pytest.mark.parametrize("site", ["capture", "live"])
+# (n, H, W, create arguments, two-sided)
+WORKSPACE_SITES = {
+    "capture": (1, 480, 640, (0, 16, 5, 200, 800), False),
+    "live": (1, 960, 1280, (0, 64, 9, 648, 2592), False),
+    # D = 16 MODE_HH on nibble planes (P2 <= 15): seven planes of half a byte per cost
+    "d16_hh_nibble": (1, 480, 640, (0, 16, 5, 2, 5, 0, 0, 0, 0, 0, 1), True),
+    # config 5, two frames: packed strips on two u16 planes and their boundary granules
+    "config5_x2": (2, 960, 1280, (0, 256, 9, 648, 2592), True),
+}
+
+
+@pytest.mark.parametrize("site", list(WORKSPACE_SITES))
 def test_call_site_workspace_bound(gpu, mvsv, site):
     """mvsv_sgbm_workspace_bytes bounds what a fresh context allocates for one frame of
-    the reference's call sites (directions side by side on u16 planes, R->L included)."""
+    the reference's call sites (directions side by side on u16 planes, R->L included);
+    for the nibble-plane D = 16 frame and two config-5 frames it is also no more than
+    what the context allocates plus the same slack (the estimate is the launch plan's
+    buffer sizes)."""
     import ctypes
     from mvstereovision3_amd import _lib
     torch = gpu
-    n, H, W = (1, 480, 640) if site == "capture" else (1, 960, 1280)
-    m = mvsv.StereoSGBM.create(0, 16, 5, 200, 800) if site == "capture" else \
-        mvsv.StereoSGBM.create(0, 64, 9, 648, 2592)
+    n, H, W, args, two_sided = WORKSPACE_SITES[site]
+    m = mvsv.StereoSGBM.create(*args)
     est = _lib.lib().mvsv_sgbm_workspace_bytes(n, W, H, ctypes.byref(m._params))
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(5400)
@@ -97,7 +110,10 @@ def test_call_site_workspace_bound(gpu, mvsv, site):
         used = free0 - torch.cuda.mem_get_info()[0]
     finally:
         ctx.close()
+    print(f"{site}: context used {used} B, workspace estimate {est} B")
     assert used <= est + (64 << 20), f"context used {used} B, workspace estimate {est} B"
+    if two_sided:
+        assert est <= used + (64 << 20), f"workspace estimate {est} B, context used {used} B"
 
 
 @pytest.mark.parametrize("split", ["1", "0"])
