@@ -24,6 +24,9 @@
  *                                     src/MeanDisparityDetection.cpp:159-206 +
  *                                     Utility::calcMeanDisparity src/utility.cpp:265-285
  *   mvsv_mean_disparity_grid          same, host map (MeanDisparityDetection::build)
+ *   mvsv_median_blur3_device /        cv::medianBlur(.., 3) and cv::filterSpeckles on CV_16S
+ *   mvsv_filter_speckles_device       maps: the post filters of cv::StereoSGBM::compute /
+ *                                     cv::StereoBM::compute, callable on their own
  *   mvsv_samplepoint_layout /         SamplepointDetection::init / build /
  *   _values(_device) / _detect_device detectObstacles src/SamplePointDetection.cpp:29-178,
  *                                     Samplepoint inc/Samplepoint.h:17-40
@@ -325,6 +328,30 @@ MVSV_API int mvsv_sgbm_plan_cn(mvsv_ctx* ctx, int n, int width, int height, cons
 MVSV_API int mvsv_mean_disparity_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap,
                                              size_t stride, size_t frame_stride, int width,
                                              int height, float* means);
+
+/* The post filters of the disparity path on their own, on device maps.
+ *
+ * mvsv_median_blur3_device: cv::medianBlur(src, dst, 3) for CV_16S (replicate
+ * border), what StereoSGBM::compute applies after its core.  n frames, strides
+ * in int16 elements (stride >= width), any 2-byte-aligned views: an even width
+ * with even strides and 4-byte-aligned views takes the packed kernel, every
+ * other form the scalar one.  The extents of src and dst ([first, last] element
+ * of the n frames) must not intersect: MVSV_E_INVALID_ARG, there is no in-place
+ * form.
+ *
+ * mvsv_filter_speckles_device: cv::filterSpeckles(img, new_val,
+ * max_speckle_size, max_diff) for CV_16S, in place on n frames; the frames are
+ * filtered independently.  new_val must be an int16 value.  max_speckle_size
+ * <= 0 removes nothing and max_diff < 0 makes every pixel a component of its
+ * own, as in OpenCV.  StereoSGBM passes ((minDisparity - 1) * 16,
+ * speckleWindowSize, 16 * speckleRange), StereoBM the same new_val and window
+ * with speckleRange unscaled. */
+MVSV_API int mvsv_median_blur3_device(mvsv_ctx* ctx, int n, const int16_t* src, size_t src_stride,
+                                      size_t src_frame_stride, int16_t* dst, size_t dst_stride,
+                                      size_t dst_frame_stride, int width, int height);
+MVSV_API int mvsv_filter_speckles_device(mvsv_ctx* ctx, int n, int16_t* img, size_t stride,
+                                         size_t frame_stride, int width, int height, int new_val,
+                                         int max_speckle_size, int max_diff);
 
 /* Same grid for a host map (synchronous). means: 81 floats, row-major 9x9. */
 MVSV_API int mvsv_mean_disparity_grid(mvsv_ctx* ctx, const int16_t* dmap, size_t stride,

@@ -11,9 +11,9 @@ from ._lib import (GRAY_Q14, GRAY_Q15, MATCHER_BM, MATCHER_SGBM, MODE_HH, MODE_S
                    OPT_STRIP_SPIN_LIMIT, OPT_STRIP_WAVES,
                    PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, VARIANT_FIRSTCOL_FIX,
                    VARIANT_WTA_MIN_D, MvsvError, set_option, synchronize)
-from .disparity import (SAMPLE_HIT_DTYPE, Disparity, StereoBM, StereoSGBM, Stereopair, mean_disparity_grid,
-                        samplepoint_detect, samplepoint_layout, samplepoint_values, sgbmParameters, synth_pair, tm,
-                        tm_validate)
+from .disparity import (SAMPLE_HIT_DTYPE, Disparity, StereoBM, StereoSGBM, Stereopair, filter_speckles,
+                        mean_disparity_grid, median_blur3, samplepoint_detect, samplepoint_layout,
+                        samplepoint_values, sgbmParameters, synth_pair, tm, tm_validate)
 from .detection import (DisparityStream, MeanDisparityDetection, Samplepoint, SamplepointDetection, Subimage,
                         create_dmap_rois)
 from .calibration import Stereosystem, read_matrix, stereo_rectify, write_matrices
@@ -25,7 +25,7 @@ from .utility import (CLOUD_DTYPE, VIEW_FOUND_POINTS, VIEW_FOUND_TILES, VIEW_OBS
 
 __all__ = [
     "Disparity", "StereoBM", "StereoSGBM", "Stereopair", "sgbmParameters", "MvsvError",
-    "synth_pair", "mean_disparity_grid", "MODE_SGBM", "MODE_HH", "PREFILTER_XSOBEL",
+    "synth_pair", "mean_disparity_grid", "median_blur3", "filter_speckles", "MODE_SGBM", "MODE_HH", "PREFILTER_XSOBEL",
     "PREFILTER_NORMALIZED_RESPONSE", "VARIANT_FIRSTCOL_FIX", "VARIANT_WTA_MIN_D",
     "DisparityStream", "MeanDisparityDetection", "Subimage", "create_dmap_rois", "Utility",
     "dMapValues", "ply", "reproject", "init_undistort_rectify_map", "rectify_pair", "remap",

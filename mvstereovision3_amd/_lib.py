@@ -154,6 +154,8 @@ def _declare(lib, strict=True):
         "mvsv_sgbm_workspace_bytes_cn": ([I, I, I, P, I], Z),
         "mvsv_sgbm_plan_cn": ([P, I, I, I, P, I, P], I),
         "mvsv_mean_disparity_grid_device": ([P, I, P, Z, Z, I, I, P], I),
+        "mvsv_median_blur3_device": ([P, I, P, Z, Z, P, Z, Z, I, I], I),
+        "mvsv_filter_speckles_device": ([P, I, P, Z, Z, I, I, I, I, I], I),
         "mvsv_load_sgbm_yaml": ([ctypes.c_char_p, P, P], I),
         "mvsv_load_bm_yaml": ([ctypes.c_char_p, P], I),
         "mvsv_synth_pair": ([ctypes.c_uint32, I, I, I, I, P, P], I),

@@ -707,6 +707,33 @@ int mvsv_mean_disparity_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, s
     return mark_last_use(ctx, mean_grid_device(ctx, n, dmap, st, fs, W, H, means));
 }
 
+int mvsv_median_blur3_device(mvsv_ctx* ctx, int n, const int16_t* src, size_t ss, size_t sfs, int16_t* dst,
+                             size_t ds, size_t dfs, int W, int H)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0 || !src || !dst || W <= 0 || H <= 0 || ss < (size_t)W || ds < (size_t)W)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad median arguments");
+    // one element past the last one the n frames of a view reach
+    auto extent = [&](size_t st, size_t fs) { return (size_t)(n - 1) * fs + (size_t)(H - 1) * st + (size_t)W; };
+    const uintptr_t s0 = (uintptr_t)src, s1 = (uintptr_t)(src + extent(ss, sfs));
+    const uintptr_t d0 = (uintptr_t)dst, d1 = (uintptr_t)(dst + extent(ds, dfs));
+    if (s0 < d1 && d0 < s1) return set_error(ctx, MVSV_E_INVALID_ARG, "median: src and dst overlap");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, median3x3_device(ctx, n, src, ss, sfs, dst, ds, dfs, W, H, nullptr, 0u, 0));
+}
+
+int mvsv_filter_speckles_device(mvsv_ctx* ctx, int n, int16_t* img, size_t st, size_t fs, int W, int H, int new_val,
+                                int max_speckle_size, int max_diff)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0 || !img || W <= 0 || H <= 0 || st < (size_t)W)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad speckle filter arguments");
+    if (new_val < -32768 || new_val > 32767)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "speckle filter: new_val is not an int16 value");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, speckle_device(ctx, n, img, st, fs, W, H, new_val, max_speckle_size, max_diff));
+}
+
 int mvsv_samplepoint_layout(int W, int H, int* step_x, int* step_y, int* nx, int* ny)
 {
     if (!step_x || !step_y || !nx || !ny) return MVSV_E_INVALID_ARG;

@@ -439,6 +439,56 @@ def mean_disparity_grid(dmap):
     return out if batched else out[0]
 
 
+def _post_map(t, what):
+    """(N, H, W) view of an (H, W) or (N, H, W) int16 device map, and whether it was batched; the
+    callers check the column stride."""
+    import torch
+    if not _is_torch(t) or not t.is_cuda or t.dtype != torch.int16 or t.dim() not in (2, 3):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: (H, W) or (N, H, W) int16 device tensor expected")
+    return (t if t.dim() == 3 else t.unsqueeze(0)), t.dim() == 3
+
+
+def median_blur3(dmap, out=None):
+    """cv::medianBlur(dmap, out, 3) on device: the 3x3 median (replicate border) of an
+    (H, W) or (N, H, W) int16 device tensor.  Views reach the kernels as views (row and
+    frame strides, storage offset); `out`, if given, is a tensor of the same shape that
+    does not overlap `dmap` and may be a view too."""
+    import torch
+    s, batched = _post_map(dmap, "median_blur3")
+    if s.stride(2) != 1:
+        s = s.contiguous()
+    n, H, W = s.shape
+    if out is None:
+        out = torch.empty(dmap.shape, dtype=torch.int16, device=dmap.device)
+    d, _ = _post_map(out, "median_blur3")
+    if out.shape != dmap.shape or out.device != dmap.device or d.stride(2) != 1:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "median_blur3: out must match the map and have unit column stride")
+    ctx = context(dmap.device.index or 0)
+    check(lib().mvsv_set_stream(ctx.handle,
+                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
+          ctx.handle)
+    check(lib().mvsv_median_blur3_device(ctx.handle, n, s.data_ptr(), s.stride(1), s.stride(0), d.data_ptr(),
+                                         d.stride(1), d.stride(0), W, H), ctx.handle)
+    return out
+
+
+def filter_speckles(dmap, new_val, max_size, max_diff):
+    """cv::filterSpeckles(dmap, new_val, max_size, max_diff) on device, in place on an
+    (H, W) or (N, H, W) int16 device tensor (a view is filtered as a view); returns dmap."""
+    import torch
+    d, _ = _post_map(dmap, "filter_speckles")
+    if d.stride(2) != 1:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "filter_speckles: unit column stride expected (in place)")
+    n, H, W = d.shape
+    ctx = context(dmap.device.index or 0)
+    check(lib().mvsv_set_stream(ctx.handle,
+                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
+          ctx.handle)
+    check(lib().mvsv_filter_speckles_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
+                                            int(new_val), int(max_size), int(max_diff)), ctx.handle)
+    return dmap
+
+
 # mvsv_sample_hit (include/mvsv.h): a lattice point inside the range and its calcCoordinate
 SAMPLE_HIT_DTYPE = np.dtype([("index", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
 

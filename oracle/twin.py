@@ -254,8 +254,9 @@ def median3x3(img: np.ndarray) -> np.ndarray:
     return np.sort(stack, axis=0)[4].astype(np.int16)
 
 
-def filter_speckles(img: np.ndarray, new_val: int, max_size: int, max_diff: int) -> np.ndarray:
-    """Union-find over 4-neighbours (order independent), then size test."""
+def speckle_components(img: np.ndarray, new_val: int, max_diff: int):
+    """Union-find over 4-neighbours (order independent): (valid, size of its component)
+    per pixel, both (H, W); the size of an invalid pixel is 0."""
     H, W = img.shape
     a = img.astype(np.int32).ravel()
     parent = np.arange(H * W)
@@ -281,10 +282,15 @@ def filter_speckles(img: np.ndarray, new_val: int, max_size: int, max_diff: int)
                         parent[max(ri, rj)] = min(ri, rj)
     roots = np.array([find(i) for i in range(H * W)])
     sizes = np.bincount(roots[ok], minlength=H * W)
-    out = a.copy()
-    small = ok & (sizes[roots] <= max_size)
-    out[small] = new_val
-    return out.reshape(H, W).astype(np.int16)
+    return ok.reshape(H, W), np.where(ok, sizes[roots], 0).reshape(H, W)
+
+
+def filter_speckles(img: np.ndarray, new_val: int, max_size: int, max_diff: int) -> np.ndarray:
+    """Components of speckle_components, then the size test."""
+    ok, size = speckle_components(img, new_val, max_diff)
+    out = img.astype(np.int32)
+    out[ok & (size <= max_size)] = new_val
+    return out.astype(np.int16)
 
 
 def sgbm_compute(L, R, p: dict, flags: int = 0) -> np.ndarray:
