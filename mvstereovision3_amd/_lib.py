@@ -352,6 +352,22 @@ def context(device: int = 0) -> Context:
     return c
 
 
+def device_context(tensor) -> Context:
+    """This thread's context on a device tensor's device, bound to that device's current torch stream."""
+    import torch
+    c = context(tensor.device.index or 0)
+    check(lib().mvsv_set_stream(c.handle, ctypes.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)),
+          c.handle)
+    return c
+
+
+def host_context() -> Context:
+    """This thread's context on device 0, on its own stream: what the calls on host arrays run on."""
+    c = context(0)
+    check(lib().mvsv_use_own_stream(c.handle), c.handle)
+    return c
+
+
 def synchronize(device: int = 0) -> None:
     """Wait for the device work of this thread's context on `device` and raise
     MvsvError(MVSV_E_TIMEOUT) if an SGBM launch since the last check gave up a

@@ -1,19 +1,18 @@
 // mvsv_host.cpp — host side of libmvsv: parameter resolution (OpenCV's
-// defaulting + assert rules), context / stream / buffer management, the
-// host-pointer entry points, the YAML loaders and the synthetic generator.
+// defaulting + assert rules), context / stream / buffer management, and the
+// one-shot entry points: each _device call next to its host-pointer twin, which
+// stages one frame through the context's arena (mvsv_stage.hpp): check the
+// arguments, reserve, upload, the _device call, download, finish.
 #include <algorithm>
-#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <functional>
-#include <map>
-#include <sstream>
 #include <string>
 
 #include "mvsv_internal.hpp"
+#include "mvsv_stage.hpp"
 
 namespace mvsv {
 
@@ -410,8 +409,8 @@ int mvsv_trim(mvsv_ctx* ctx)
     DevBuf* all[] = {&ctx->pre, &ctx->cost, &ctx->cres, &ctx->agg, &ctx->raw, &ctx->uf_parent, &ctx->uf_size, &ctx->uf_lroot, &ctx->uf_list,
                      &ctx->uf_tile, &ctx->tri_bnd, &ctx->bs_bnd, &ctx->status,
                      &ctx->dummy, &ctx->keys,
-                     &ctx->bm_lf, &ctx->bm_rf, &ctx->bm_cost, &ctx->bm_sad, &ctx->h_left, &ctx->h_right,
-                     &ctx->h_out, &ctx->mm_part, &ctx->cl_rows, &ctx->sh_part, &ctx->ud_maps};
+                     &ctx->bm_lf, &ctx->bm_rf, &ctx->bm_cost, &ctx->bm_sad, &ctx->stage,
+                     &ctx->mm_part, &ctx->cl_rows, &ctx->sh_part, &ctx->ud_maps};
     for (DevBuf* b : all) free_buf(*b);
     ctx->ud_key.clear();
     return MVSV_OK;
@@ -707,6 +706,25 @@ int mvsv_mean_disparity_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, s
     return mark_last_use(ctx, mean_grid_device(ctx, n, dmap, st, fs, W, H, means));
 }
 
+int mvsv_mean_disparity_grid(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, float* means)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (!dmap || !means || W <= 0 || H <= 0 || st < (size_t)W)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "bad mean-grid arguments");
+    DeviceGuard dev_guard(ctx->device);
+    const MapFloatsStage s(W, H, 81);
+    return staged_call(ctx, s, "grid staging", [&](Staging& sg) -> int {
+        int rc;
+        int16_t* d = sg.at<int16_t>(s.map);
+        float* m = sg.at<float>(s.floats);
+        if ((rc = sg.up(d, s.map.pitch, dmap, st * 2, (size_t)W * 2, H, "H2D map")) ||
+            (rc = mean_grid_device(ctx, 1, d, W, s.map.bytes / 2, W, H, m)) ||
+            (rc = sg.down(means, m, s.floats.bytes, "D2H means")))
+            return rc;
+        return sg.finish();
+    });
+}
+
 int mvsv_median_blur3_device(mvsv_ctx* ctx, int n, const int16_t* src, size_t ss, size_t sfs, int16_t* dst,
                              size_t ds, size_t dfs, int W, int H)
 {
@@ -740,16 +758,27 @@ int mvsv_samplepoint_layout(int W, int H, int* step_x, int* step_y, int* nx, int
     return sample_layout(W, H, step_x, step_y, nx, ny);
 }
 
+// What both sample point calls ask of their arguments; *npts: the lattice's points, and
+// a map without one (narrower or lower than 16) asks for nothing: the call has nothing to do
+static bool sample_args_ok(const int16_t* dmap, size_t st, int W, int H, const float* values, int* min_step, size_t* npts)
+{
+    if (!dmap || W <= 0 || H <= 0 || st < (size_t)W) return false;
+    int sx, sy, nx, ny;
+    sample_layout(W, H, &sx, &sy, &nx, &ny);
+    *min_step = std::min(sx, sy);
+    *npts = (size_t)nx * ny;
+    return *npts == 0 || values;
+}
+
 int mvsv_samplepoint_values_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
                                    int radius, float* values)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
-    if (n <= 0 || !dmap || W <= 0 || H <= 0 || st < (size_t)W)
+    int min_step;
+    size_t npts;
+    if (n <= 0 || !sample_args_ok(dmap, st, W, H, values, &min_step, &npts))
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point arguments");
-    int sx, sy, nx, ny;
-    sample_layout(W, H, &sx, &sy, &nx, &ny);
-    if (nx == 0 || ny == 0) return MVSV_OK;
-    if (!values) return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point arguments");
+    if (npts == 0) return MVSV_OK;
     DeviceGuard dev_guard(ctx->device);
     return mark_last_use(ctx, sample_grid_device(ctx, n, dmap, st, fs, W, H, radius, values));
 }
@@ -757,30 +786,25 @@ int mvsv_samplepoint_values_device(mvsv_ctx* ctx, int n, const int16_t* dmap, si
 int mvsv_samplepoint_values(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, int radius, float* values)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
-    if (!dmap || W <= 0 || H <= 0 || st < (size_t)W)
+    int min_step;
+    size_t npts;
+    if (!sample_args_ok(dmap, st, W, H, values, &min_step, &npts))
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point arguments");
-    int sx, sy, nx, ny;
-    sample_layout(W, H, &sx, &sy, &nx, &ny);
-    if (nx == 0 || ny == 0) return MVSV_OK;
-    if (!values) return set_error(ctx, MVSV_E_INVALID_ARG, "bad sample point arguments");
-    if (radius < 0 || radius >= std::min(sx, sy))
+    if (npts == 0) return MVSV_OK;
+    if (radius < 0 || radius >= min_step)
         return set_error(ctx, MVSV_E_INVALID_ARG, "sample point radius must be 0 .. min(step_x, step_y) - 1");
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {  // every exit after an enqueue
-    const size_t px = (size_t)W * H, npts = (size_t)nx * ny;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_out, px * 2 + 4 + npts * sizeof(float), "sample point staging"))) return rc;
-    int16_t* d = (int16_t*)ctx->h_out.ptr;
-    float* v = (float*)(d + px + (px & 1));
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, (size_t)W * 2, dmap, st * 2, (size_t)W * 2, H,
-                                              hipMemcpyHostToDevice, s), "H2D map")) ||
-        (rc = sample_grid_device(ctx, 1, d, W, px, W, H, radius, v)) ||
-        (rc = check_hip(ctx, hipMemcpyAsync(values, v, npts * sizeof(float), hipMemcpyDeviceToHost, s),
-                        "D2H sample point values")))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
+    const MapFloatsStage s(W, H, npts);
+    return staged_call(ctx, s, "sample point staging", [&](Staging& sg) -> int {
+        int rc;
+        int16_t* d = sg.at<int16_t>(s.map);
+        float* v = sg.at<float>(s.floats);
+        if ((rc = sg.up(d, s.map.pitch, dmap, st * 2, (size_t)W * 2, H, "H2D map")) ||
+            (rc = sample_grid_device(ctx, 1, d, W, s.map.bytes / 2, W, H, radius, v)) ||
+            (rc = sg.down(values, v, s.floats.bytes, "D2H sample point values")))
+            return rc;
+        return sg.finish();
+    });
 }
 
 int mvsv_samplepoint_detect_device(mvsv_ctx* ctx, int n, const float* values, int W, int H, const float* Q,
@@ -807,12 +831,18 @@ int mvsv_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, siz
     return mark_last_use(ctx, minmax_device(ctx, n, dmap, st, fs, W, H, positive_only != 0, minmax));
 }
 
+static bool normalize_args_ok(const int16_t* dmap, size_t st, int W, int H, double alpha, double beta, const uint8_t* out,
+                              size_t os)
+{
+    return dmap && out && W > 0 && H > 0 && st >= (size_t)W && os >= (size_t)W && std::isfinite(alpha) &&
+           std::isfinite(beta);
+}
+
 int mvsv_normalize_minmax_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
                                  double alpha, double beta, uint8_t* out, size_t os, size_t ofs, int16_t* minmax)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
-    if (n <= 0 || !dmap || !out || W <= 0 || H <= 0 || st < (size_t)W || os < (size_t)W || !std::isfinite(alpha) ||
-        !std::isfinite(beta))
+    if (n <= 0 || !normalize_args_ok(dmap, st, W, H, alpha, beta, out, os))
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad normalize arguments");
     DeviceGuard dev_guard(ctx->device);
     return mark_last_use(ctx, normalize_minmax_device(ctx, n, dmap, st, fs, W, H, alpha, beta, out, os, ofs, minmax));
@@ -822,28 +852,23 @@ int mvsv_normalize_minmax(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, 
                           uint8_t* out, size_t os, int16_t* minmax)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
-    if (!dmap || !out || W <= 0 || H <= 0 || st < (size_t)W || os < (size_t)W || !std::isfinite(alpha) ||
-        !std::isfinite(beta))
+    if (!normalize_args_ok(dmap, st, W, H, alpha, beta, out, os))
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad normalize arguments");
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {  // every exit after an enqueue
-    // staged rows are a multiple of 8 elements apart: the packed path for any width
-    const size_t ws = ((size_t)W + 7) & ~(size_t)7, px = ws * H;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_out, px * 3 + 4, "normalize staging"))) return rc;
-    int16_t* d = (int16_t*)ctx->h_out.ptr;
-    uint8_t* o = (uint8_t*)(d + px);
-    int16_t* mm = (int16_t*)(o + px);
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, ws * 2, dmap, st * 2, (size_t)W * 2, H, hipMemcpyHostToDevice, s),
-                        "H2D map")) ||
-        (rc = normalize_minmax_device(ctx, 1, d, ws, px, W, H, alpha, beta, o, ws, px, mm)) ||
-        (rc = check_hip(ctx, hipMemcpy2DAsync(out, os, o, ws, (size_t)W, H, hipMemcpyDeviceToHost, s),
-                        "D2H display map")) ||
-        (minmax && (rc = check_hip(ctx, hipMemcpyAsync(minmax, mm, 4, hipMemcpyDeviceToHost, s), "D2H min / max"))))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
+    const NormalizeStage s(W, H);
+    return staged_call(ctx, s, "normalize staging", [&](Staging& sg) -> int {
+        int rc;
+        int16_t* d = sg.at<int16_t>(s.map);
+        uint8_t* o = sg.at<uint8_t>(s.out);
+        int16_t* mm = sg.at<int16_t>(s.minmax);
+        if ((rc = sg.up(d, s.map.pitch, dmap, st * 2, (size_t)W * 2, H, "H2D map")) ||
+            (rc = normalize_minmax_device(ctx, 1, d, s.map.pitch / 2, s.map.bytes / 2, W, H, alpha, beta, o, s.out.pitch,
+                                          s.out.bytes, mm)) ||
+            (rc = sg.down(out, os, o, s.out.pitch, (size_t)W, H, "D2H display map")) ||
+            (minmax && (rc = sg.down(minmax, mm, 4, "D2H min / max"))))
+            return rc;
+        return sg.finish();
+    });
 }
 
 // the rules of a one-shot view call that need no device; a message, or nullptr
@@ -880,41 +905,30 @@ int mvsv_view(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, const
     if (!ctx) return MVSV_E_INVALID_ARG;
     if (const char* why = view_call_check(dmap, st, W, H, spec, out, os)) return set_error(ctx, MVSV_E_INVALID_ARG, why);
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {  // every exit after an enqueue
-    // staged rows are a multiple of 8 elements apart: the packed path for any width
-    const size_t ws = ((size_t)W + 7) & ~(size_t)7, px = ws * H, ob = (3 * (size_t)W * H + 15) & ~(size_t)15;
     int sx, sy, nx, ny;
     sample_layout(W, H, &sx, &sy, &nx, &ny);
-    const size_t npts = (spec->layers & MVSV_VIEW_FOUND_POINTS) ? (size_t)nx * ny : 0;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_out, px * 2 + ob + 16 + (81 + npts) * sizeof(float), "view staging"))) return rc;
-    int16_t* d = (int16_t*)ctx->h_out.ptr;
-    uint8_t* o = (uint8_t*)(d + px);
-    int16_t* mm = (int16_t*)(o + ob);
-    float* means = (float*)(o + ob + 16);
-    float* values = means + 81;
-    mvsv_view_spec dspec = *spec;
-    dspec.means = means;
-    dspec.values = values;
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, ws * 2, dmap, st * 2, (size_t)W * 2, H, hipMemcpyHostToDevice, s),
-                        "H2D map")) ||
-        ((spec->layers & MVSV_VIEW_FOUND_TILES) &&
-         (rc = check_hip(ctx, hipMemcpyAsync(means, spec->means, 81 * sizeof(float), hipMemcpyHostToDevice, s),
-                         "H2D means"))) ||
-        (npts && (rc = check_hip(ctx, hipMemcpyAsync(values, spec->values, npts * sizeof(float),
-                                                     hipMemcpyHostToDevice, s), "H2D sample values"))) ||
-        (rc = view_device(ctx, 1, d, ws, px, W, H, dspec, o, 3 * (size_t)W, ob, mm)) ||
-        (rc = check_hip(ctx, hipMemcpy2DAsync(out, os, o, 3 * (size_t)W, 3 * (size_t)W, H, hipMemcpyDeviceToHost, s),
-                        "D2H view")) ||
-        (minmax && (rc = check_hip(ctx, hipMemcpyAsync(minmax, mm, 4, hipMemcpyDeviceToHost, s), "D2H min / max"))))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
+    const ViewStage s(W, H, (spec->layers & MVSV_VIEW_FOUND_POINTS) ? (size_t)nx * ny : 0);
+    return staged_call(ctx, s, "view staging", [&](Staging& sg) -> int {
+        int rc;
+        int16_t* d = sg.at<int16_t>(s.map);
+        uint8_t* o = sg.at<uint8_t>(s.out);
+        int16_t* mm = sg.at<int16_t>(s.minmax);
+        mvsv_view_spec dspec = *spec;
+        dspec.means = sg.at<float>(s.means);
+        dspec.values = sg.at<float>(s.values);
+        if ((rc = sg.up(d, s.map.pitch, dmap, st * 2, (size_t)W * 2, H, "H2D map")) ||
+            ((spec->layers & MVSV_VIEW_FOUND_TILES) &&
+             (rc = sg.up(sg.at<float>(s.means), spec->means, s.means.bytes, "H2D means"))) ||
+            (s.values.bytes && (rc = sg.up(sg.at<float>(s.values), spec->values, s.values.bytes, "H2D sample values"))) ||
+            (rc = view_device(ctx, 1, d, s.map.pitch / 2, s.map.bytes / 2, W, H, dspec, o, s.out.pitch, s.out.bytes, mm)) ||
+            (rc = sg.down(out, os, o, s.out.pitch, 3 * (size_t)W, H, "D2H view")) ||
+            (minmax && (rc = sg.down(minmax, mm, 4, "D2H min / max"))))
+            return rc;
+        return sg.finish();
+    });
 }
 
-// Host-pointer path: stage through cached device buffers, run, copy back, sync.
-// cn: bytes per input pixel (3: mvsv_sgbm_bgr)
+// One host pair through either matcher; cn: bytes per input pixel (3: mvsv_sgbm_bgr)
 static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs,
                      int W, int H, int16_t* out, size_t os, bool sgbm, const void* params, int cn = 1)
 {
@@ -933,30 +947,22 @@ static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* 
     if (sgbm) se.cn = cn;
     if (sgbm && (rc = check_report(ctx))) return rc;  // an earlier device call's give-up
     DeviceGuard dev_guard(ctx->device);
-    // every exit after the first enqueue records the context's last-use event,
-    // so a later stream switch waits for whatever this call left queued
-    return mark_last_use(ctx, [&]() -> int {
-    int rc;
-    size_t fb = (size_t)W * H;
-    const size_t rb = (size_t)W * cn, ib = rb * H;  // input row / frame bytes
-    if ((rc = ensure(ctx, ctx->h_left, ib, "left staging"))) return rc;
-    if ((rc = ensure(ctx, ctx->h_right, ib, "right staging"))) return rc;
-    if ((rc = ensure(ctx, ctx->h_out, fb * 2, "output staging"))) return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_left.ptr, rb, L, ls, rb, H, hipMemcpyHostToDevice, s), "H2D left"))) return rc;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_right.ptr, rb, R, rs, rb, H, hipMemcpyHostToDevice, s), "H2D right"))) return rc;
-    int16_t* dout = (int16_t*)ctx->h_out.ptr;
-    rc = sgbm ? sgbm_device(ctx, 1, (const uint8_t*)ctx->h_left.ptr, rb, ib,
-                            (const uint8_t*)ctx->h_right.ptr, rb, ib, W, H, se, dout, W, fb)
-              : bm_device(ctx, 1, (const uint8_t*)ctx->h_left.ptr, W, fb,
-                          (const uint8_t*)ctx->h_right.ptr, W, fb, W, H, be, dout, W, fb);
-    if (rc) return rc;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(out, os * 2, dout, (size_t)W * 2, (size_t)W * 2, H, hipMemcpyDeviceToHost, s), "D2H out"))) return rc;
-    if ((rc = check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
-    // only an SGBM call reads the sticky give-up word: a BM call's valid map is
-    // returned and the word waits for the next SGBM call or mvsv_synchronize
-    return sgbm ? check_report(ctx) : MVSV_OK;
-    }());
+    const PairStage s(W, H, cn, 2);
+    return staged_call(ctx, s, "matcher staging", [&](Staging& sg) -> int {
+        int rc;
+        uint8_t* dl = sg.at<uint8_t>(s.left);
+        uint8_t* dr = sg.at<uint8_t>(s.right);
+        int16_t* dout = sg.at<int16_t>(s.out);
+        const size_t rb = s.left.pitch, ib = s.left.bytes, fb = (size_t)W * H;  // input row / frame bytes
+        if ((rc = sg.up(dl, rb, L, ls, rb, H, "H2D left")) || (rc = sg.up(dr, rb, R, rs, rb, H, "H2D right")) ||
+            (rc = sgbm ? sgbm_device(ctx, 1, dl, rb, ib, dr, rb, ib, W, H, se, dout, W, fb)
+                       : bm_device(ctx, 1, dl, rb, ib, dr, rb, ib, W, H, be, dout, W, fb)) ||
+            (rc = sg.down(out, os * 2, dout, s.out.pitch, (size_t)W * 2, H, "D2H out")) || (rc = sg.finish()))
+            return rc;
+        // only an SGBM call reads the sticky give-up word: a BM call's valid map is
+        // returned and the word waits for the next SGBM call or mvsv_synchronize
+        return sgbm ? check_report(ctx) : MVSV_OK;
+    });
 }
 
 int mvsv_sgbm(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs, int W,
@@ -991,67 +997,64 @@ int mvsv_reproject_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, 
     return mark_last_use(ctx, reproject_device(ctx, n, dmap, st, fs, W, H, Q, xyzw, xs, xfs));
 }
 
+// what every point cloud call asks of its map
+static bool cloud_args_ok(const int16_t* dmap, size_t st, int W, int H, const float* Q)
+{
+    return dmap && Q && W > 0 && H > 0 && st >= (size_t)W && (size_t)W * H <= (size_t)INT32_MAX;
+}
+
 int mvsv_point_cloud_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st, size_t fs, int W, int H,
                             const float* Q, mvsv_cloud_point* records, int capacity, int* counts, int32_t* minmax)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
-    if (n <= 0 || !dmap || !Q || !records || !counts || W <= 0 || H <= 0 || st < (size_t)W || capacity < 1 ||
-        (size_t)W * H > (size_t)INT32_MAX || ((uintptr_t)records & 15) != 0)
+    if (n <= 0 || !cloud_args_ok(dmap, st, W, H, Q) || !records || !counts || capacity < 1 ||
+        ((uintptr_t)records & 15) != 0)
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad point cloud arguments");
     DeviceGuard dev_guard(ctx->device);
     return mark_last_use(ctx, point_cloud_device(ctx, n, dmap, st, fs, W, H, Q, records, capacity, counts, 1, minmax, 2));
 }
 
-// One host map through the device: the map staged with rows a multiple of 8
-// elements apart (the packed path for any width), a (count, min, max) header behind
-// it; the header comes back first, then the records that exist.  *dev_records: the
-// staged records (up to capacity of them), *hdr: the header on the host.
-static int host_cloud(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, const float* Q, int capacity,
+// One host map through the device, up to the header (count, min, max) on the host:
+// it comes back first, so that a caller copies only the records that exist, from
+// *dev_records.
+static int host_cloud(Staging& sg, const CloudStage& s, const int16_t* dmap, size_t st, int W, int H, const float* Q,
                       int hdr[3], const mvsv_cloud_point** dev_records)
 {
-    const size_t ws = ((size_t)W + 7) & ~(size_t)7, px = ws * H;
-    const int cap = (int)std::min((size_t)capacity, (size_t)W * H);
+    int16_t* d = sg.at<int16_t>(s.map);
+    int* dh = sg.at<int>(s.header);
+    mvsv_cloud_point* rec = sg.at<mvsv_cloud_point>(s.records);
+    *dev_records = rec;
     int rc;
-    if ((rc = ensure(ctx, ctx->h_out, px * 2 + 3 * sizeof(int), "dmap staging"))) return rc;
-    if ((rc = ensure(ctx, ctx->h_left, (size_t)cap * sizeof(mvsv_cloud_point), "point staging"))) return rc;
-    int16_t* d = (int16_t*)ctx->h_out.ptr;
-    int* dh = (int*)(d + px);  // px * 2 is a multiple of 16
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, ws * 2, dmap, st * 2, (size_t)W * 2, H, hipMemcpyHostToDevice, s),
-                        "H2D dmap")) ||
-        (rc = point_cloud_device(ctx, 1, d, ws, px, W, H, Q, (mvsv_cloud_point*)ctx->h_left.ptr, cap, dh, 3, dh + 1,
-                                 3)) ||
-        (rc = check_hip(ctx, hipMemcpyAsync(hdr, dh, 3 * sizeof(int), hipMemcpyDeviceToHost, s), "D2H cloud header")) ||
-        (rc = check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize")))
+    if ((rc = sg.up(d, s.map.pitch, dmap, st * 2, (size_t)W * 2, H, "H2D dmap")) ||
+        (rc = point_cloud_device(sg.ctx, 1, d, s.map.pitch / 2, s.map.bytes / 2, W, H, Q, rec,
+                                 (int)(s.records.bytes / sizeof *rec), dh, 3, dh + 1, 3)) ||
+        (rc = sg.down(hdr, dh, s.header.bytes, "D2H cloud header")))
         return rc;
-    *dev_records = (const mvsv_cloud_point*)ctx->h_left.ptr;
-    return MVSV_OK;
+    return sg.finish();
 }
 
 int mvsv_point_cloud(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, const float* Q,
                      mvsv_cloud_point* records, int capacity, int* count, int32_t* minmax)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
-    if (!dmap || !Q || !records || !count || W <= 0 || H <= 0 || st < (size_t)W || capacity < 1 ||
-        (size_t)W * H > (size_t)INT32_MAX)
+    if (!cloud_args_ok(dmap, st, W, H, Q) || !records || !count || capacity < 1)
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad point cloud arguments");
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {  // every exit after an enqueue
-    int rc, hdr[3];
-    const mvsv_cloud_point* dev = nullptr;
-    if ((rc = host_cloud(ctx, dmap, st, W, H, Q, capacity, hdr, &dev))) return rc;
-    *count = hdr[0];
-    if (minmax) {
-        minmax[0] = hdr[1];
-        minmax[1] = hdr[2];
-    }
-    const size_t k = (size_t)std::min(hdr[0], capacity);
-    if (k == 0) return MVSV_OK;
-    if ((rc = check_hip(ctx, hipMemcpyAsync(records, dev, k * sizeof(mvsv_cloud_point), hipMemcpyDeviceToHost,
-                                            ctx->stream), "D2H points")))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }());
+    const CloudStage s(W, H, capacity);
+    return staged_call(ctx, s, "point cloud staging", [&](Staging& sg) -> int {
+        int rc, hdr[3];
+        const mvsv_cloud_point* dev = nullptr;
+        if ((rc = host_cloud(sg, s, dmap, st, W, H, Q, hdr, &dev))) return rc;
+        *count = hdr[0];
+        if (minmax) {
+            minmax[0] = hdr[1];
+            minmax[1] = hdr[2];
+        }
+        const size_t k = (size_t)std::min(hdr[0], capacity);
+        if (k == 0) return MVSV_OK;
+        if ((rc = sg.down(records, dev, k * sizeof(mvsv_cloud_point), "D2H points"))) return rc;
+        return sg.finish();
+    });
 }
 
 // [Utility::dmap2pcl] src/utility.cpp:242-262
@@ -1059,26 +1062,24 @@ int mvsv_dmap2pcl(mvsv_ctx* ctx, const char* path, const int16_t* dmap, size_t s
                   const float* Q)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
-    if (!path || !dmap || !Q || W <= 0 || H <= 0 || st < (size_t)W || (size_t)W * H > (size_t)INT32_MAX)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "bad dmap2pcl arguments");
+    if (!path || !cloud_args_ok(dmap, st, W, H, Q)) return set_error(ctx, MVSV_E_INVALID_ARG, "bad dmap2pcl arguments");
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {
-    int rc, hdr[3];
-    const mvsv_cloud_point* dev = nullptr;
-    if ((rc = host_cloud(ctx, dmap, st, W, H, Q, INT32_MAX, hdr, &dev))) return rc;
-    // the records are (x, y, z, grey): vertices 4 floats apart; the writer prints its own grey
-    const size_t k = (size_t)hdr[0];
-    std::vector<float> pts(k * 4);
-    if (k && ((rc = check_hip(ctx, hipMemcpyAsync(pts.data(), dev, k * sizeof(mvsv_cloud_point),
-                                                  hipMemcpyDeviceToHost, ctx->stream), "D2H points")) ||
-              (rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))))
-        return rc;
-    rc = mvsv_write_ply(path, "Hagen Hiller", "disparity pointcloud", pts.data(), k, 4,
-                        MVSV_PLY_WITH_COLOR, dmap, st, W, H);
-    if (rc == MVSV_E_IO) return set_error(ctx, rc, std::string("cannot write ") + path);
-    if (rc) return set_error(ctx, rc, "dmap2pcl: map has no positive disparity");
-    return MVSV_OK;
-    }());
+    const CloudStage s(W, H, INT32_MAX);
+    return staged_call(ctx, s, "point cloud staging", [&](Staging& sg) -> int {
+        int rc, hdr[3];
+        const mvsv_cloud_point* dev = nullptr;
+        if ((rc = host_cloud(sg, s, dmap, st, W, H, Q, hdr, &dev))) return rc;
+        // the records are (x, y, z, grey): vertices 4 floats apart; the writer prints its own grey
+        const size_t k = (size_t)hdr[0];
+        std::vector<float> pts(k * 4);
+        if (k && ((rc = sg.down(pts.data(), dev, k * sizeof(mvsv_cloud_point), "D2H points")) || (rc = sg.finish())))
+            return rc;
+        rc = mvsv_write_ply(path, "Hagen Hiller", "disparity pointcloud", pts.data(), k, 4,
+                            MVSV_PLY_WITH_COLOR, dmap, st, W, H);
+        if (rc == MVSV_E_IO) return set_error(ctx, rc, std::string("cannot write ") + path);
+        if (rc) return set_error(ctx, rc, "dmap2pcl: map has no positive disparity");
+        return MVSV_OK;
+    });
 }
 
 // ---- rectification ------------------------------------------
@@ -1101,13 +1102,19 @@ int mvsv_resize_size(int sw, int sh, double fx, double fy, int* dw, int* dh)
     return resize_size(sw, sh, fx, fy, dw, dh);
 }
 
+static bool resize_args_ok(const uint8_t* src, size_t ss, int sw, int sh, double fx, double fy, const uint8_t* dst,
+                           int* dw, int* dh)
+{
+    return src && dst && ss >= (size_t)std::max(sw, 0) && !resize_size(sw, sh, fx, fy, dw, dh);
+}
+
 // [cv::resize in Stereosystem::getRectifiedImagepair(Stereopair&, float)] src/Stereosystem.cpp:279-315
 int mvsv_resize_device(mvsv_ctx* ctx, int n, const uint8_t* src, size_t ss, size_t sfs, int sw, int sh,
                        double fx, double fy, uint8_t* dst, size_t ds, size_t dfs)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     int dw, dh;
-    if (n <= 0 || !src || !dst || ss < (size_t)std::max(sw, 0) || resize_size(sw, sh, fx, fy, &dw, &dh))
+    if (n <= 0 || !resize_args_ok(src, ss, sw, sh, fx, fy, dst, &dw, &dh))
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad resize arguments");
     DeviceGuard dev_guard(ctx->device);
     return mark_last_use(ctx, resize_device(ctx, n, src, ss, sfs, sw, sh, fx, fy, dst, ds, dfs));
@@ -1118,26 +1125,20 @@ int mvsv_resize(mvsv_ctx* ctx, const uint8_t* src, size_t ss, int sw, int sh, do
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     int dw, dh;
-    if (!src || !dst || ss < (size_t)std::max(sw, 0) || resize_size(sw, sh, fx, fy, &dw, &dh) ||
-        ds < (size_t)dw)
+    if (!resize_args_ok(src, ss, sw, sh, fx, fy, dst, &dw, &dh) || ds < (size_t)dw)
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad resize arguments");
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {
-    const size_t in = (size_t)sw * sh, outb = (size_t)dw * dh;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_left, in, "resize staging")) ||
-        (rc = ensure(ctx, ctx->h_right, outb, "resize staging")))
-        return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_left.ptr, sw, src, ss, sw, sh, hipMemcpyHostToDevice, s),
-                        "H2D image")) ||
-        (rc = resize_device(ctx, 1, (const uint8_t*)ctx->h_left.ptr, sw, in, sw, sh, fx, fy,
-                            (uint8_t*)ctx->h_right.ptr, dw, outb)) ||
-        (rc = check_hip(ctx, hipMemcpy2DAsync(dst, ds, ctx->h_right.ptr, dw, dw, dh, hipMemcpyDeviceToHost, s),
-                        "D2H image")))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
+    const ImageStage s(sh, sw, kRowTight, dw, dh);
+    return staged_call(ctx, s, "resize staging", [&](Staging& sg) -> int {
+        int rc;
+        uint8_t* in = sg.at<uint8_t>(s.in);
+        uint8_t* out = sg.at<uint8_t>(s.out);
+        if ((rc = sg.up(in, s.in.pitch, src, ss, sw, sh, "H2D image")) ||
+            (rc = resize_device(ctx, 1, in, s.in.pitch, s.in.bytes, sw, sh, fx, fy, out, s.out.pitch, s.out.bytes)) ||
+            (rc = sg.down(dst, ds, out, s.out.pitch, dw, dh, "D2H image")))
+            return rc;
+        return sg.finish();
+    });
 }
 
 int mvsv_prepare_size(int sw, int sh, int halve, int* dw, int* dh)
@@ -1146,14 +1147,20 @@ int mvsv_prepare_size(int sw, int sh, int halve, int* dw, int* dh)
     return prepare_size(sw, sh, halve, dw, dh);
 }
 
+static bool prepare_args_ok(const uint8_t* bgr, size_t ss, int sw, int sh, int halve, int variant, const uint8_t* dst,
+                            size_t ds, int* dw, int* dh)
+{
+    return bgr && dst && !prepare_size(sw, sh, halve, dw, dh) && ss >= 3 * (size_t)sw && ds >= (size_t)*dw &&
+           (variant == MVSV_GRAY_Q14 || variant == MVSV_GRAY_Q15);
+}
+
 // [cv::resize INTER_AREA 0.5 + cv::cvtColor BGR2GRAY] trgt/disparityTest.cpp:201-211
 int mvsv_prepare_gray_device(mvsv_ctx* ctx, int n, const uint8_t* bgr, size_t ss, size_t sfs, int sw, int sh,
                              int halve, int variant, uint8_t* dst, size_t ds, size_t dfs)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     int dw, dh;
-    if (n <= 0 || !bgr || !dst || prepare_size(sw, sh, halve, &dw, &dh) || ss < 3 * (size_t)sw || ds < (size_t)dw ||
-        (variant != MVSV_GRAY_Q14 && variant != MVSV_GRAY_Q15))
+    if (n <= 0 || !prepare_args_ok(bgr, ss, sw, sh, halve, variant, dst, ds, &dw, &dh))
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad prepare arguments");
     DeviceGuard dev_guard(ctx->device);
     return mark_last_use(ctx, prepare_gray_device(ctx, n, bgr, ss, sfs, sw, sh, halve, variant, dst, ds, dfs));
@@ -1164,27 +1171,21 @@ int mvsv_prepare_gray(mvsv_ctx* ctx, const uint8_t* bgr, size_t ss, int sw, int 
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     int dw, dh;
-    if (!bgr || !dst || prepare_size(sw, sh, halve, &dw, &dh) || ss < 3 * (size_t)sw || ds < (size_t)dw ||
-        (variant != MVSV_GRAY_Q14 && variant != MVSV_GRAY_Q15))
+    if (!prepare_args_ok(bgr, ss, sw, sh, halve, variant, dst, ds, &dw, &dh))
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad prepare arguments");
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {
-    // device rows padded to 4 bytes: the kernel's packed loads
-    const size_t row = 3 * (size_t)sw, drow = (row + 3) & ~(size_t)3, in = drow * sh, outb = (size_t)dw * dh;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_left, in, "prepare staging")) ||
-        (rc = ensure(ctx, ctx->h_right, outb, "prepare staging")))
-        return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_left.ptr, drow, bgr, ss, row, sh, hipMemcpyHostToDevice, s),
-                        "H2D image")) ||
-        (rc = prepare_gray_device(ctx, 1, (const uint8_t*)ctx->h_left.ptr, drow, in, sw, sh, halve, variant,
-                                  (uint8_t*)ctx->h_right.ptr, dw, outb)) ||
-        (rc = check_hip(ctx, hipMemcpy2DAsync(dst, ds, ctx->h_right.ptr, dw, dw, dh, hipMemcpyDeviceToHost, s),
-                        "D2H image")))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
+    const ImageStage s(sh, 3 * (size_t)sw, kRow4, dw, dh);
+    return staged_call(ctx, s, "prepare staging", [&](Staging& sg) -> int {
+        int rc;
+        uint8_t* in = sg.at<uint8_t>(s.in);
+        uint8_t* out = sg.at<uint8_t>(s.out);
+        if ((rc = sg.up(in, s.in.pitch, bgr, ss, s.in.row_bytes, sh, "H2D image")) ||
+            (rc = prepare_gray_device(ctx, 1, in, s.in.pitch, s.in.bytes, sw, sh, halve, variant, out, s.out.pitch,
+                                      s.out.bytes)) ||
+            (rc = sg.down(dst, ds, out, s.out.pitch, dw, dh, "D2H image")))
+            return rc;
+        return sg.finish();
+    });
 }
 
 // [Stereosystem::getRectifiedImagepair] src/Stereosystem.cpp:243-262
@@ -1201,43 +1202,29 @@ int mvsv_rectify_pair(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t*
     for (int i = 0; i < 4; i++)
         if (!maps[i]) return set_error(ctx, MVSV_E_INVALID_ARG, "null map");
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {
     const size_t px = (size_t)W * H;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_left, 2 * px, "rectify staging")) ||
-        (rc = ensure(ctx, ctx->h_right, 2 * px, "rectify staging")) ||
-        (rc = ensure(ctx, ctx->h_out, 4 * px * sizeof(float), "rectify maps")))
-        return rc;
-    uint8_t* dsrc = (uint8_t*)ctx->h_left.ptr;   // [2][H][W] inputs
-    uint8_t* ddst = (uint8_t*)ctx->h_right.ptr;  // [2][H][W] outputs
-    float* dmap = (float*)ctx->h_out.ptr;         // [4][H][W]
-    hipStream_t s = ctx->stream;
-    const uint8_t* ins[2] = {L, R};
-    const size_t istr[2] = {ls, rs};
-    for (int i = 0; i < 2; i++)
-        if ((rc = check_hip(ctx, hipMemcpy2DAsync(dsrc + i * px, W, ins[i], istr[i], W, H,
-                                                  hipMemcpyHostToDevice, s), "H2D image")))
+    const RemapStage s(W, H, 4 * px);
+    return staged_call(ctx, s, "rectify staging", [&](Staging& sg) -> int {
+        int rc;
+        uint8_t* dsrc = sg.at<uint8_t>(s.src);  // [2][H][W] inputs
+        uint8_t* ddst = sg.at<uint8_t>(s.dst);  // [2][H][W] outputs
+        float* dmap = sg.at<float>(s.maps);     // [4][H][W]
+        if ((rc = sg.up(dsrc, W, L, ls, W, H, "H2D image")) || (rc = sg.up(dsrc + px, W, R, rs, W, H, "H2D image")))
             return rc;
-    for (int i = 0; i < 4; i++)
-        if ((rc = check_hip(ctx, hipMemcpyAsync(dmap + i * px, maps[i], px * sizeof(float),
-                                                hipMemcpyHostToDevice, s), "H2D map")))
+        for (int i = 0; i < 4; i++)
+            if ((rc = sg.up(dmap + i * px, maps[i], px * sizeof(float), "H2D map"))) return rc;
+        for (int i = 0; i < 2; i++)
+            if ((rc = remap_device(ctx, 1, dsrc + i * px, W, px, W, H, dmap + (2 * i) * px, dmap + (2 * i + 1) * px, W,
+                                   ddst + i * px, W, px, W, H)))
+                return rc;
+        const int cw = roi->x1 - roi->x0, ch = roi->y1 - roi->y0;
+        const uint8_t* crop = ddst + (size_t)roi->y0 * W + roi->x0;
+        if ((rc = sg.down(oL, ols, crop, W, cw, ch, "D2H image")) ||
+            (rc = sg.down(oR, ors, crop + px, W, cw, ch, "D2H image")))
             return rc;
-    for (int i = 0; i < 2; i++)
-        if ((rc = remap_device(ctx, 1, dsrc + i * px, W, px, W, H, dmap + (2 * i) * px,
-                               dmap + (2 * i + 1) * px, W, ddst + i * px, W, px, W, H)))
-            return rc;
-    const int cw = roi->x1 - roi->x0, ch = roi->y1 - roi->y0;
-    uint8_t* outs[2] = {oL, oR};
-    const size_t ostr[2] = {ols, ors};
-    for (int i = 0; i < 2; i++)
-        if ((rc = check_hip(ctx, hipMemcpy2DAsync(outs[i], ostr[i],
-                                                  ddst + i * px + (size_t)roi->y0 * W + roi->x0, W, cw,
-                                                  ch, hipMemcpyDeviceToHost, s), "D2H image")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
+        return sg.finish();
+    });
 }
-
 
 // ---- camera set-up: focus measure and undistorted pairs ---------------------------
 
@@ -1246,14 +1233,18 @@ static bool rect_inside(const mvsv_rect& q, int W, int H)
     return q.x0 >= 0 && q.y0 >= 0 && q.x1 <= W && q.y1 <= H && q.x1 > q.x0 && q.y1 > q.y0;
 }
 
+static bool sharpness_args_ok(const uint8_t* img, size_t st, int W, int H, const mvsv_rect& q)
+{
+    return img && W > 0 && H > 0 && st >= (size_t)W && rect_inside(q, W, H) && (size_t)W * H <= (size_t)INT32_MAX;
+}
+
 // [Utility::checkSharpness] src/utility.cpp:163-174: the integer sum S4
 int mvsv_sharpness_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t st, size_t fs, int W, int H,
                           const mvsv_rect* roi, int64_t* sums)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, W, H};
-    if (n <= 0 || !img || !sums || W <= 0 || H <= 0 || st < (size_t)W || !rect_inside(q, W, H) ||
-        (size_t)W * H > (size_t)INT32_MAX)
+    if (n <= 0 || !sums || !sharpness_args_ok(img, st, W, H, q))
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad sharpness arguments");
     DeviceGuard dev_guard(ctx->device);
     return mark_last_use(ctx, sharpness_device(ctx, n, img, st, fs, W, H, q, sums, 1));
@@ -1264,24 +1255,20 @@ int mvsv_sharpness(mvsv_ctx* ctx, const uint8_t* img, size_t st, int W, int H, c
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     const mvsv_rect q = roi ? *roi : mvsv_rect{0, 0, W, H};
-    if (!img || W <= 0 || H <= 0 || st < (size_t)W || !rect_inside(q, W, H) || (size_t)W * H > (size_t)INT32_MAX)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "bad sharpness arguments");
+    if (!sharpness_args_ok(img, st, W, H, q)) return set_error(ctx, MVSV_E_INVALID_ARG, "bad sharpness arguments");
     DeviceGuard dev_guard(ctx->device);
     int64_t s4 = 0;
-    const int rc = mark_last_use(ctx, [&]() -> int {
-    // staged rows are a multiple of 4 bytes apart: packed loads for any width; the sum sits behind them
-    const size_t ws = ((size_t)W + 3) & ~(size_t)3, sum_at = (ws * H + 7) & ~(size_t)7;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_left, sum_at + sizeof(int64_t), "sharpness staging"))) return rc;
-    uint8_t* d = (uint8_t*)ctx->h_left.ptr;
-    int64_t* ds = (int64_t*)(d + sum_at);
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, ws, img, st, (size_t)W, H, hipMemcpyHostToDevice, s), "H2D image")) ||
-        (rc = sharpness_device(ctx, 1, d, ws, ws * H, W, H, q, ds, 1)) ||
-        (rc = check_hip(ctx, hipMemcpyAsync(&s4, ds, sizeof s4, hipMemcpyDeviceToHost, s), "D2H sharpness")))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
+    const SharpnessStage s(W, H);
+    const int rc = staged_call(ctx, s, "sharpness staging", [&](Staging& sg) -> int {
+        int rc;
+        uint8_t* d = sg.at<uint8_t>(s.img);
+        int64_t* ds = sg.at<int64_t>(s.sum);
+        if ((rc = sg.up(d, s.img.pitch, img, st, (size_t)W, H, "H2D image")) ||
+            (rc = sharpness_device(ctx, 1, d, s.img.pitch, s.img.bytes, W, H, q, ds, 1)) ||
+            (rc = sg.down(&s4, ds, sizeof s4, "D2H sharpness")))
+            return rc;
+        return sg.finish();
+    });
     if (rc) return rc;
     if (sum4) *sum4 = s4;
     // cv::mean: sum * (1.0 / N), a reciprocal and a product, each rounded
@@ -1314,58 +1301,47 @@ int mvsv_undistort_pair(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_
         (size_t)W * H > (size_t)INT32_MAX)
         return set_error(ctx, MVSV_E_INVALID_ARG, "bad undistortion arguments");
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {
     const size_t px = (size_t)W * H;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_left, 2 * px, "undistort staging")) ||
-        (rc = ensure(ctx, ctx->h_right, 2 * px, "undistort staging")))
-        return rc;
-    hipStream_t s = ctx->stream;
-    // the maps of a calibration are built and uploaded once: the key is all they depend on
-    std::vector<double> key = {(double)W, (double)H, (double)nL, (double)nR};
-    key.insert(key.end(), KL, KL + 9);
-    key.insert(key.end(), KR, KR + 9);
-    key.insert(key.end(), DL, DL + nL);
-    key.insert(key.end(), DR, DR + nR);
-    const bool cached = ctx->ud_maps.ptr && key.size() == ctx->ud_key.size() &&
-                        std::memcmp(key.data(), ctx->ud_key.data(), key.size() * sizeof(double)) == 0;
-    if (!cached) {
-        ctx->ud_key.clear();
-        if ((rc = ensure(ctx, ctx->ud_maps, 2 * px * 6, "undistort maps"))) return rc;
-        std::vector<int16_t> xy(2 * px * 2);
-        std::vector<uint16_t> fr(2 * px);
-        if (mvsv_undistort_maps(KL, DL, nL, nullptr, W, H, xy.data(), W, fr.data(), W) ||
-            mvsv_undistort_maps(KR, DR, nR, nullptr, W, H, xy.data() + 2 * px, W, fr.data() + px, W))
-            return set_error(ctx, MVSV_E_INVALID_ARG, "singular camera matrix");
-        // synchronous copies: the host vectors end with this scope
-        if ((rc = check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize")) ||
-            (rc = check_hip(ctx, hipMemcpy(ctx->ud_maps.ptr, xy.data(), 4 * px * sizeof(int16_t),
-                                           hipMemcpyHostToDevice), "H2D map")) ||
-            (rc = check_hip(ctx, hipMemcpy((uint8_t*)ctx->ud_maps.ptr + 8 * px, fr.data(), 2 * px * sizeof(uint16_t),
-                                           hipMemcpyHostToDevice), "H2D map")))
+    const RemapStage s(W, H, 0);
+    return staged_call(ctx, s, "undistort staging", [&](Staging& sg) -> int {
+        int rc;
+        // the maps of a calibration are built and uploaded once: the key is all they depend on
+        std::vector<double> key = {(double)W, (double)H, (double)nL, (double)nR};
+        key.insert(key.end(), KL, KL + 9);
+        key.insert(key.end(), KR, KR + 9);
+        key.insert(key.end(), DL, DL + nL);
+        key.insert(key.end(), DR, DR + nR);
+        const bool cached = ctx->ud_maps.ptr && key.size() == ctx->ud_key.size() &&
+                            std::memcmp(key.data(), ctx->ud_key.data(), key.size() * sizeof(double)) == 0;
+        if (!cached) {
+            ctx->ud_key.clear();
+            if ((rc = ensure(ctx, ctx->ud_maps, 2 * px * 6, "undistort maps"))) return rc;
+            std::vector<int16_t> xy(2 * px * 2);
+            std::vector<uint16_t> fr(2 * px);
+            if (mvsv_undistort_maps(KL, DL, nL, nullptr, W, H, xy.data(), W, fr.data(), W) ||
+                mvsv_undistort_maps(KR, DR, nR, nullptr, W, H, xy.data() + 2 * px, W, fr.data() + px, W))
+                return set_error(ctx, MVSV_E_INVALID_ARG, "singular camera matrix");
+            // synchronous copies: the host vectors end with this scope
+            if ((rc = sg.finish()) ||
+                (rc = check_hip(ctx, hipMemcpy(ctx->ud_maps.ptr, xy.data(), 4 * px * sizeof(int16_t),
+                                               hipMemcpyHostToDevice), "H2D map")) ||
+                (rc = check_hip(ctx, hipMemcpy((uint8_t*)ctx->ud_maps.ptr + 8 * px, fr.data(),
+                                               2 * px * sizeof(uint16_t), hipMemcpyHostToDevice), "H2D map")))
+                return rc;
+            ctx->ud_key = key;
+        }
+        const int16_t* dxy = (const int16_t*)ctx->ud_maps.ptr;
+        const uint16_t* dfr = (const uint16_t*)((const uint8_t*)ctx->ud_maps.ptr + 8 * px);
+        uint8_t* dsrc = sg.at<uint8_t>(s.src);  // [2][H][W] inputs
+        uint8_t* ddst = sg.at<uint8_t>(s.dst);  // [2][H][W] outputs: in-place calls are safe
+        if ((rc = sg.up(dsrc, W, L, ls, W, H, "H2D image")) || (rc = sg.up(dsrc + px, W, R, rs, W, H, "H2D image")))
             return rc;
-        ctx->ud_key = key;
-    }
-    const int16_t* dxy = (const int16_t*)ctx->ud_maps.ptr;
-    const uint16_t* dfr = (const uint16_t*)((const uint8_t*)ctx->ud_maps.ptr + 8 * px);
-    uint8_t* dsrc = (uint8_t*)ctx->h_left.ptr;   // [2][H][W] inputs
-    uint8_t* ddst = (uint8_t*)ctx->h_right.ptr;  // [2][H][W] outputs: in-place calls are safe
-    const uint8_t* ins[2] = {L, R};
-    const size_t istr[2] = {ls, rs};
-    uint8_t* outs[2] = {oL, oR};
-    const size_t ostr[2] = {ols, ors};
-    for (int i = 0; i < 2; i++)
-        if ((rc = check_hip(ctx, hipMemcpy2DAsync(dsrc + i * px, W, ins[i], istr[i], W, H, hipMemcpyHostToDevice, s),
-                            "H2D image")))
+        for (int i = 0; i < 2; i++)
+            if ((rc = remap_fixed_device(ctx, 1, dsrc + i * px, W, px, W, H, dxy + i * 2 * px, W, dfr + i * px, W,
+                                         ddst + i * px, W, px, W, H)))
+                return rc;
+        if ((rc = sg.down(oL, ols, ddst, W, W, H, "D2H image")) || (rc = sg.down(oR, ors, ddst + px, W, W, H, "D2H image")))
             return rc;
-    for (int i = 0; i < 2; i++)
-        if ((rc = remap_fixed_device(ctx, 1, dsrc + i * px, W, px, W, H, dxy + i * 2 * px, W, dfr + i * px, W,
-                                     ddst + i * px, W, px, W, H)))
-            return rc;
-    for (int i = 0; i < 2; i++)
-        if ((rc = check_hip(ctx, hipMemcpy2DAsync(outs[i], ostr[i], ddst + i * px, W, W, H, hipMemcpyDeviceToHost, s),
-                            "D2H image")))
-            return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
+        return sg.finish();
+    });
 }

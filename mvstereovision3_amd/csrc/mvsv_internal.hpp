@@ -119,8 +119,8 @@ struct mvsv_ctx {
     hipStream_t cap = nullptr;  // capture stream
     // BM
     mvsv::DevBuf bm_lf, bm_rf, bm_cost, bm_sad;
-    // host-pointer staging
-    mvsv::DevBuf h_left, h_right, h_out;
+    // the host-pointer calls' staging arena (mvsv_stage.hpp)
+    mvsv::DevBuf stage;
     // display maps: one (min, max) pair per block of minmax_kernel, [n][blocks][2] ints
     mvsv::DevBuf mm_part;
     // point clouds: (min, max) per frame, then (first record, min | max) per row, int pairs

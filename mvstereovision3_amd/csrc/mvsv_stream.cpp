@@ -1623,27 +1623,3 @@ void mvsv_stream_destroy(mvsv_stream* st)
     (void)hipStreamSynchronize(st->down);
     delete st;
 }
-
-int mvsv_mean_disparity_grid(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H,
-                             float* means)
-{
-    if (!ctx) return MVSV_E_INVALID_ARG;
-    if (!dmap || !means || W <= 0 || H <= 0 || st < (size_t)W)
-        return set_error(ctx, MVSV_E_INVALID_ARG, "bad mean-grid arguments");
-    DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {  // every exit after an enqueue
-    const size_t px = (size_t)W * H;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_out, px * 2 + 4 + 81 * sizeof(float), "grid staging"))) return rc;
-    int16_t* d = (int16_t*)ctx->h_out.ptr;
-    float* m = (float*)(d + px + (px & 1));
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(d, (size_t)W * 2, dmap, st * 2, (size_t)W * 2, H,
-                                              hipMemcpyHostToDevice, s), "H2D map")) ||
-        (rc = mean_grid_device(ctx, 1, d, W, px, W, H, m)) ||
-        (rc = check_hip(ctx, hipMemcpyAsync(means, m, 81 * sizeof(float), hipMemcpyDeviceToHost, s),
-                        "D2H means")))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
-}

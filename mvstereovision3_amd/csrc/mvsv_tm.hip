@@ -28,6 +28,7 @@
 // bounded by W.
 #include "mvsv_device.hpp"
 #include "mvsv_internal.hpp"
+#include "mvsv_stage.hpp"
 
 namespace mvsv {
 namespace {
@@ -271,24 +272,18 @@ int mvsv_tm(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t
     if (ls < (size_t)W || rs < (size_t)W || ds < (size_t)W)
         return set_error(ctx, MVSV_E_INVALID_ARG, "tm: stride smaller than the row");
     DeviceGuard dev_guard(ctx->device);
-    return mark_last_use(ctx, [&]() -> int {
-    const size_t px = (size_t)W * H;
-    int rc;
-    if ((rc = ensure(ctx, ctx->h_left, px, "tm staging")) || (rc = ensure(ctx, ctx->h_right, px, "tm staging")) ||
-        (rc = ensure(ctx, ctx->h_out, px, "tm staging")))
-        return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_left.ptr, W, L, ls, W, H, hipMemcpyHostToDevice, s),
-                        "H2D image")) ||
-        (rc = check_hip(ctx, hipMemcpy2DAsync(ctx->h_right.ptr, W, R, rs, W, H, hipMemcpyHostToDevice, s),
-                        "H2D image")) ||
-        (rc = tm_device(ctx, 1, (const uint8_t*)ctx->h_left.ptr, W, px, (const uint8_t*)ctx->h_right.ptr, W, px, W,
-                        H, k, ctx->h_out.ptr, W, px, 1)) ||
-        (rc = check_hip(ctx, hipMemcpy2DAsync(dst, ds, ctx->h_out.ptr, W, W, H, hipMemcpyDeviceToHost, s),
-                        "D2H image")))
-        return rc;
-    return check_hip(ctx, hipStreamSynchronize(s), "hipStreamSynchronize");
-    }());
+    const PairStage s(W, H, 1, 1);
+    return staged_call(ctx, s, "tm staging", [&](Staging& sg) -> int {
+        int rc;
+        uint8_t* dl = sg.at<uint8_t>(s.left);
+        uint8_t* dr = sg.at<uint8_t>(s.right);
+        uint8_t* dout = sg.at<uint8_t>(s.out);
+        if ((rc = sg.up(dl, W, L, ls, W, H, "H2D image")) || (rc = sg.up(dr, W, R, rs, W, H, "H2D image")) ||
+            (rc = tm_device(ctx, 1, dl, W, s.left.bytes, dr, W, s.right.bytes, W, H, k, dout, W, s.out.bytes, 1)) ||
+            (rc = sg.down(dst, ds, dout, W, W, H, "D2H image")))
+            return rc;
+        return sg.finish();
+    });
 }
 
 }  // extern "C"

@@ -20,8 +20,8 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import MvsvError, Rect, check, context, lib
-from .utility import PLY_WITH_COLOR, Utility, dMapValues, ply
+from ._lib import MvsvError, Rect, check, context, host_context, lib
+from .utility import PLY_WITH_COLOR, Utility, _host_map, dMapValues, ply
 
 MEAN_DISTANCE = 0
 MEAN_VALUE = 1
@@ -156,14 +156,9 @@ class MeanDisparityDetection:
         if type(dMap).__module__.startswith("torch"):
             from .disparity import mean_disparity_grid
             return mean_disparity_grid(dMap).cpu().numpy()
-        d = np.asarray(dMap)
-        if d.dtype != np.int16 or d.ndim != 2:
-            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "build: 2-D int16 map expected")
-        if d.strides[1] != 2:
-            d = np.ascontiguousarray(d)
+        d = _host_map(dMap, "build")
         out = np.empty(81, np.float32)
-        ctx = context(0)
-        check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+        ctx = host_context()
         check(lib().mvsv_mean_disparity_grid(ctx.handle, d.ctypes.data, d.strides[0] // 2,
                                              d.shape[1], d.shape[0], out.ctypes.data), ctx.handle)
         return out
@@ -324,15 +319,10 @@ class SamplepointDetection:
         if type(dMap).__module__.startswith("torch"):
             from .disparity import samplepoint_values
             return samplepoint_values(dMap, self.RADIUS).cpu().numpy()
-        d = np.asarray(dMap)
-        if d.dtype != np.int16 or d.ndim != 2:
-            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "build: 2-D int16 map expected")
-        if d.strides[1] != 2:
-            d = np.ascontiguousarray(d)
+        d = _host_map(dMap, "build")
         out = np.empty(n, np.float32)
         if n:
-            ctx = context(0)
-            check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+            ctx = host_context()
             check(lib().mvsv_samplepoint_values(ctx.handle, d.ctypes.data, d.strides[0] // 2, d.shape[1],
                                                 d.shape[0], self.RADIUS, out.ctypes.data), ctx.handle)
         return out

@@ -32,7 +32,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (MODE_HH, MODE_SGBM, PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL,
-                   BmParams, MvsvError, SgbmParams, SgbmYamlValues, check, context, lib)
+                   BmParams, MvsvError, SgbmParams, SgbmYamlValues, check, device_context, host_context, lib)
+from .utility import _device_frames
 
 log = logging.getLogger("mvsv.disparity")
 
@@ -66,23 +67,42 @@ def _is_torch(a) -> bool:
     return type(a).__module__.startswith("torch")
 
 
-def _run_host(fn, params, left, right, out, what):
-    L = np.asarray(left)
-    R = np.asarray(right)
+def _host_pair(left, right, what):
+    """Two 2-D uint8 arrays of one size, with unit column stride."""
+    L, R = np.asarray(left), np.asarray(right)
     if L.ndim != 2 or R.ndim != 2 or L.dtype != np.uint8 or R.dtype != np.uint8:
         raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be 2-D CV_8UC1 (uint8)")
     if L.shape != R.shape:
         raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: left and right sizes differ")
-    if L.strides[1] != 1:
-        L = np.ascontiguousarray(L)
-    if R.strides[1] != 1:
-        R = np.ascontiguousarray(R)
+    return tuple(a if a.strides[1] == 1 else np.ascontiguousarray(a) for a in (L, R))
+
+
+def _device_pair(left, right, what, channels=1):
+    """Two uint8 device tensors of one shape, (H, W) or (N, H, W) -- with channels = 3 a
+    last dimension of 3 behind it -- as frames (N, ...) with dense rows:
+    (left, right, whether they came as a batch)."""
+    import torch
+    nd, c = (2, "") if channels == 1 else (3, ",3")
+    if left.dtype != torch.uint8 or right.dtype != torch.uint8:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be uint8")
+    if left.shape != right.shape or left.dim() not in (nd, nd + 1) or (channels == 3 and left.shape[-1] != 3):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be (H,W{c}) or (N,H,W{c}), equal")
+    if not left.is_cuda or not right.is_cuda or left.device != right.device:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: device tensors on one GPU expected")
+    batched = left.dim() == nd + 1
+    frames = [t if batched else t.unsqueeze(0) for t in (left, right)]
+    dense = (lambda t: t.stride(2) == 1) if channels == 1 else (lambda t: t.stride(3) == 1 and t.stride(2) == 3)
+    Lt, Rt = (t if dense(t) else t.contiguous() for t in frames)
+    return Lt, Rt, batched
+
+
+def _run_host(fn, params, left, right, out, what):
+    L, R = _host_pair(left, right, what)
     H, W = L.shape
     if out is None or not isinstance(out, np.ndarray) or out.shape != (H, W) \
             or out.dtype != np.int16 or out.strides[1] != 2:
         out = np.empty((H, W), np.int16)  # cv::Mat::create semantics: reallocate
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     rc = fn(ctx.handle, L.ctypes.data, L.strides[0], R.ctypes.data, R.strides[0], W, H,
             ctypes.byref(params), out.ctypes.data, out.strides[0] // 2)
     check(rc, ctx.handle)
@@ -91,28 +111,13 @@ def _run_host(fn, params, left, right, out, what):
 
 def _run_device(fn, params, left, right, out, what):
     import torch
-    if left.dtype != torch.uint8 or right.dtype != torch.uint8:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be uint8")
-    if left.shape != right.shape or left.dim() not in (2, 3):
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be (H,W) or (N,H,W), equal")
-    if not left.is_cuda or not right.is_cuda or left.device != right.device:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: device tensors on one GPU expected")
-    batched = left.dim() == 3
-    Lt = left if batched else left.unsqueeze(0)
-    Rt = right if batched else right.unsqueeze(0)
-    if Lt.stride(2) != 1:
-        Lt = Lt.contiguous()
-    if Rt.stride(2) != 1:
-        Rt = Rt.contiguous()
+    Lt, Rt, batched = _device_pair(left, right, what)
     n, H, W = Lt.shape
     if out is None or tuple(out.shape) != tuple(left.shape) or out.dtype != torch.int16 \
             or out.device != left.device or out.stride(-1) != 1:
         out = torch.empty(left.shape, dtype=torch.int16, device=left.device)
     Ot = out if batched else out.unsqueeze(0)
-    dev = left.device.index or 0
-    ctx = context(dev)
-    stream = torch.cuda.current_stream(left.device).cuda_stream
-    check(lib().mvsv_set_stream(ctx.handle, ctypes.c_void_p(stream)), ctx.handle)
+    ctx = device_context(left)
     rc = fn(ctx.handle, n, Lt.data_ptr(), Lt.stride(1), Lt.stride(0), Rt.data_ptr(), Rt.stride(1),
             Rt.stride(0), W, H, ctypes.byref(params), Ot.data_ptr(), Ot.stride(1), Ot.stride(0))
     check(rc, ctx.handle)
@@ -136,8 +141,7 @@ def _run_host_bgr(fn, params, left, right, out, what):
     if out is None or not isinstance(out, np.ndarray) or out.shape != L.shape[:-1] \
             or out.dtype != np.int16 or out.strides[-1] != 2:
         out = np.empty(L.shape[:-1], np.int16)  # cv::Mat::create semantics: reallocate
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     for Lf, Rf, Of in (zip(L, R, out) if batched else ((L, R, out),)):
         rc = fn(ctx.handle, Lf.ctypes.data, Lf.strides[0], Rf.ctypes.data, Rf.strides[0], W, H,
                 ctypes.byref(params), Of.ctypes.data, Of.strides[0] // 2)
@@ -148,28 +152,14 @@ def _run_host_bgr(fn, params, left, right, out, what):
 def _run_device_bgr(fn, params, left, right, out, what):
     """(H, W, 3) or (N, H, W, 3) uint8 device tensors on the current torch stream."""
     import torch
-    if left.dtype != torch.uint8 or right.dtype != torch.uint8:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be uint8")
-    if left.shape != right.shape or left.dim() not in (3, 4) or left.shape[-1] != 3:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be (H,W,3) or (N,H,W,3), equal")
-    if not left.is_cuda or not right.is_cuda or left.device != right.device:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: device tensors on one GPU expected")
-    batched = left.dim() == 4
-    Lt = left if batched else left.unsqueeze(0)
-    Rt = right if batched else right.unsqueeze(0)
-    if Lt.stride(3) != 1 or Lt.stride(2) != 3:
-        Lt = Lt.contiguous()
-    if Rt.stride(3) != 1 or Rt.stride(2) != 3:
-        Rt = Rt.contiguous()
+    Lt, Rt, batched = _device_pair(left, right, what, channels=3)
     n, H, W, _ = Lt.shape
     oshape = tuple(left.shape[:-1])
     if out is None or tuple(out.shape) != oshape or out.dtype != torch.int16 \
             or out.device != left.device or out.stride(-1) != 1:
         out = torch.empty(oshape, dtype=torch.int16, device=left.device)
     Ot = out if batched else out.unsqueeze(0)
-    ctx = context(left.device.index or 0)
-    stream = torch.cuda.current_stream(left.device).cuda_stream
-    check(lib().mvsv_set_stream(ctx.handle, ctypes.c_void_p(stream)), ctx.handle)
+    ctx = device_context(left)
     rc = fn(ctx.handle, n, Lt.data_ptr(), Lt.stride(1), Lt.stride(0), Rt.data_ptr(), Rt.stride(1),
             Rt.stride(0), W, H, ctypes.byref(params), Ot.data_ptr(), Ot.stride(1), Ot.stride(0))
     check(rc, ctx.handle)
@@ -362,49 +352,25 @@ def tm(left, right, kernel_size: int, wide: bool = False):
         raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: left and right must both be numpy or both torch")
     if _is_torch(left):
         import torch
-        if left.dtype != torch.uint8 or right.dtype != torch.uint8:
-            raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be uint8")
-        if left.shape != right.shape or left.dim() not in (2, 3):
-            raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be (H,W) or (N,H,W), equal")
-        if not left.is_cuda or not right.is_cuda or left.device != right.device:
-            raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: device tensors on one GPU expected")
-        batched = left.dim() == 3
-        Lt = left if batched else left.unsqueeze(0)
-        Rt = right if batched else right.unsqueeze(0)
-        if Lt.stride(2) != 1:
-            Lt = Lt.contiguous()
-        if Rt.stride(2) != 1:
-            Rt = Rt.contiguous()
+        Lt, Rt, batched = _device_pair(left, right, what)
         n, H, W = Lt.shape
         if not tm_validate(k, W, H):
             raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: kernel size {k} not within 1..31 and below min(W, H)")
         eb = 2 if wide else 1
         out = torch.empty((n, H, W), dtype=torch.uint16 if wide else torch.uint8, device=left.device)
-        ctx = context(left.device.index or 0)
-        stream = torch.cuda.current_stream(left.device).cuda_stream
-        check(lib().mvsv_set_stream(ctx.handle, ctypes.c_void_p(stream)), ctx.handle)
+        ctx = device_context(left)
         check(lib().mvsv_tm_device(ctx.handle, n, Lt.data_ptr(), Lt.stride(1), Lt.stride(0), Rt.data_ptr(),
                                    Rt.stride(1), Rt.stride(0), W, H, k, out.data_ptr(), W * eb, H * W * eb, eb),
               ctx.handle)
         return out if batched else out[0]
-    L = np.asarray(left)
-    R = np.asarray(right)
-    if L.ndim != 2 or R.ndim != 2 or L.dtype != np.uint8 or R.dtype != np.uint8:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: inputs must be 2-D CV_8UC1 (uint8)")
-    if L.shape != R.shape:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: left and right sizes differ")
+    L, R = _host_pair(left, right, what)
     if wide:
         raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: the 16-bit map is for device tensors (the host entry is 8 bit)")
     H, W = L.shape
     if not tm_validate(k, W, H):
         raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: kernel size {k} not within 1..31 and below min(W, H)")
-    if L.strides[1] != 1:
-        L = np.ascontiguousarray(L)
-    if R.strides[1] != 1:
-        R = np.ascontiguousarray(R)
     out = np.empty((H, W), np.uint8)
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     check(lib().mvsv_tm(ctx.handle, L.ctypes.data, L.strides[0], R.ctypes.data, R.strides[0], W, H, k,
                         out.ctypes.data, out.strides[0]), ctx.handle)
     return out
@@ -422,18 +388,9 @@ def synth_pair(seed: int, width: int, height: int, min_disparity: int, num_dispa
 def mean_disparity_grid(dmap):
     """MeanDisparityDetection::build(MEAN_VALUE) on device: (N,81) or (81,) float32."""
     import torch
-    if not _is_torch(dmap) or not dmap.is_cuda or dmap.dtype != torch.int16:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "mean_disparity_grid: int16 device tensor expected")
-    batched = dmap.dim() == 3
-    d = dmap if batched else dmap.unsqueeze(0)
-    if d.stride(2) != 1:
-        d = d.contiguous()
+    d, batched, ctx = _device_frames(dmap, "mean_disparity_grid", any_rank=True)
     n, H, W = d.shape
     out = torch.empty((n, 81), dtype=torch.float32, device=dmap.device)
-    ctx = context(dmap.device.index or 0)
-    check(lib().mvsv_set_stream(ctx.handle,
-                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
-          ctx.handle)
     check(lib().mvsv_mean_disparity_grid_device(ctx.handle, n, d.data_ptr(), d.stride(1),
                                                 d.stride(0), W, H, out.data_ptr()), ctx.handle)
     return out if batched else out[0]
@@ -463,10 +420,7 @@ def median_blur3(dmap, out=None):
     d, _ = _post_map(out, "median_blur3")
     if out.shape != dmap.shape or out.device != dmap.device or d.stride(2) != 1:
         raise MvsvError(_lib.MVSV_E_INVALID_ARG, "median_blur3: out must match the map and have unit column stride")
-    ctx = context(dmap.device.index or 0)
-    check(lib().mvsv_set_stream(ctx.handle,
-                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
-          ctx.handle)
+    ctx = device_context(dmap)
     check(lib().mvsv_median_blur3_device(ctx.handle, n, s.data_ptr(), s.stride(1), s.stride(0), d.data_ptr(),
                                          d.stride(1), d.stride(0), W, H), ctx.handle)
     return out
@@ -475,15 +429,11 @@ def median_blur3(dmap, out=None):
 def filter_speckles(dmap, new_val, max_size, max_diff):
     """cv::filterSpeckles(dmap, new_val, max_size, max_diff) on device, in place on an
     (H, W) or (N, H, W) int16 device tensor (a view is filtered as a view); returns dmap."""
-    import torch
     d, _ = _post_map(dmap, "filter_speckles")
     if d.stride(2) != 1:
         raise MvsvError(_lib.MVSV_E_INVALID_ARG, "filter_speckles: unit column stride expected (in place)")
     n, H, W = d.shape
-    ctx = context(dmap.device.index or 0)
-    check(lib().mvsv_set_stream(ctx.handle,
-                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
-          ctx.handle)
+    ctx = device_context(dmap)
     check(lib().mvsv_filter_speckles_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
                                             int(new_val), int(max_size), int(max_diff)), ctx.handle)
     return dmap
@@ -507,19 +457,10 @@ def samplepoint_values(dmap, radius=2):
     an int16 device map, (N, nx * ny) or (nx * ny,) float32 in the reference's
     (column-major) point order."""
     import torch
-    if not _is_torch(dmap) or not dmap.is_cuda or dmap.dtype != torch.int16:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "samplepoint_values: int16 device tensor expected")
-    batched = dmap.dim() == 3
-    d = dmap if batched else dmap.unsqueeze(0)
-    if d.stride(2) != 1:
-        d = d.contiguous()
+    d, batched, ctx = _device_frames(dmap, "samplepoint_values", any_rank=True)
     n, H, W = d.shape
     _, _, nx, ny = samplepoint_layout(W, H)
     out = torch.empty((n, nx * ny), dtype=torch.float32, device=dmap.device)
-    ctx = context(dmap.device.index or 0)
-    check(lib().mvsv_set_stream(ctx.handle,
-                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
-          ctx.handle)
     check(lib().mvsv_samplepoint_values_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
                                                int(radius), out.data_ptr()), ctx.handle)
     return out if batched else out[0]
@@ -547,10 +488,7 @@ def samplepoint_detect(values, shape, Q, range_disparity, max_hits=None):
     counts = torch.zeros((n,), dtype=torch.int32, device=values.device)
     hits = torch.zeros((n, cap, 16), dtype=torch.uint8, device=values.device)
     q = np.ascontiguousarray(np.asarray(Q, np.float32).reshape(16))
-    ctx = context(values.device.index or 0)
-    check(lib().mvsv_set_stream(ctx.handle,
-                                ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)),
-          ctx.handle)
+    ctx = device_context(values)
     check(lib().mvsv_samplepoint_detect_device(ctx.handle, n, v.data_ptr(), W, H, q.ctypes.data,
                                                float(range_disparity[0]), float(range_disparity[1]), cap,
                                                counts.data_ptr(), hits.data_ptr() if cap else None),

@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import MvsvError, Rect, check, context, lib
+from ._lib import MvsvError, Rect, check, device_context, host_context, lib
 
 
 def init_undistort_rectify_map(K, dist, R, P, size):
@@ -55,10 +55,7 @@ def remap(src, map_x, map_y):
     n, sh, sw = s.shape
     dh, dw = mx.shape
     out = torch.empty((n, dh, dw), dtype=torch.uint8, device=src.device)
-    ctx = context(src.device.index or 0)
-    check(lib().mvsv_set_stream(ctx.handle,
-                                ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)),
-          ctx.handle)
+    ctx = device_context(src)
     check(lib().mvsv_remap_device(ctx.handle, n, s.data_ptr(), s.stride(1), s.stride(0), sw, sh,
                                   mx.data_ptr(), my.data_ptr(), dw, out.data_ptr(), dw, dh * dw,
                                   dw, dh), ctx.handle)
@@ -106,8 +103,7 @@ def rectify_pair(left, right, maps, roi):
     oR = np.empty_like(oL)
     arr = (ctypes.c_void_p * 4)(*[m.ctypes.data for m in ms])
     r = Rect(x0, y0, x1, y1)
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     check(lib().mvsv_rectify_pair(ctx.handle, L.ctypes.data, W, R.ctypes.data, W, W, H, arr,
                                   ctypes.byref(r), oL.ctypes.data, oL.shape[1], oR.ctypes.data,
                                   oR.shape[1]), ctx.handle)
@@ -142,10 +138,7 @@ def resize(src, fx, fy=None):
         n, sh, sw = s.shape
         dw, dh = resize_size(sw, sh, fx, fy)
         out = torch.empty((n, dh, dw), dtype=torch.uint8, device=src.device)
-        ctx = context(src.device.index or 0)
-        check(lib().mvsv_set_stream(ctx.handle,
-                                    ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)),
-              ctx.handle)
+        ctx = device_context(src)
         check(lib().mvsv_resize_device(ctx.handle, n, s.data_ptr(), s.stride(1), s.stride(0), sw, sh,
                                        float(fx), float(fy), out.data_ptr(), dw, dh * dw), ctx.handle)
         return out if batched else out[0]
@@ -155,8 +148,7 @@ def resize(src, fx, fy=None):
     sh, sw = a.shape
     dw, dh = resize_size(sw, sh, fx, fy)
     out = np.empty((dh, dw), np.uint8)
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     check(lib().mvsv_resize(ctx.handle, a.ctypes.data, sw, sw, sh, float(fx), float(fy),
                             out.ctypes.data, dw), ctx.handle)
     return out
@@ -205,10 +197,7 @@ def remap_fixed(src, xy, frac):
     n, sh, sw = s.shape
     dh, dw = frac.shape
     out = torch.empty((n, dh, dw), dtype=torch.uint8, device=src.device)
-    ctx = context(src.device.index or 0)
-    check(lib().mvsv_set_stream(ctx.handle,
-                                ctypes.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)),
-          ctx.handle)
+    ctx = device_context(src)
     check(lib().mvsv_remap_fixed_device(ctx.handle, n, s.data_ptr(), s.stride(1), s.stride(0), sw, sh,
                                         xy.data_ptr(), xy.stride(0) // 2, frac.data_ptr(), frac.stride(0),
                                         out.data_ptr(), dw, dh * dw, dw, dh), ctx.handle)
@@ -235,8 +224,7 @@ def undistort_pair(left, right, K_left, dist_left, K_right, dist_right, out=None
     KR = np.ascontiguousarray(np.asarray(K_right, np.float64).reshape(3, 3))
     dl = np.ascontiguousarray(np.asarray(dist_left if dist_left is not None else [], np.float64).reshape(-1))
     dr = np.ascontiguousarray(np.asarray(dist_right if dist_right is not None else [], np.float64).reshape(-1))
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     check(lib().mvsv_undistort_pair(ctx.handle, L.ctypes.data, L.strides[0], R.ctypes.data, R.strides[0], W, H,
                                     KL.ctypes.data, dl.ctypes.data if dl.size else None, int(dl.size),
                                     KR.ctypes.data, dr.ctypes.data if dr.size else None, int(dr.size),

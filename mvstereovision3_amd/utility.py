@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import MvsvError, check, context, lib
+from ._lib import MvsvError, check, device_context, host_context, lib
 
 PLY_PLAIN = 0
 PLY_WITH_COLOR = 1
@@ -83,14 +83,9 @@ class Utility:
             if not w.write(filename, xyzg[:, :3], ply.WITH_COLOR):
                 raise MvsvError(_lib.MVSV_E_IO, f"cannot write {filename}")
             return
-        d = np.asarray(dMap)
-        if d.ndim != 2 or d.dtype != np.int16:
-            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "dmap2pcl: 2-D int16 map expected")
-        if d.strides[1] != 2:
-            d = np.ascontiguousarray(d)
+        d = _host_map(dMap, "dmap2pcl")
         q = _q16(Q)
-        ctx = context(0)
-        check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+        ctx = host_context()
         check(lib().mvsv_dmap2pcl(ctx.handle, os.fsencode(filename), d.ctypes.data, d.strides[0] // 2,
                                   d.shape[1], d.shape[0], q.ctypes.data), ctx.handle)
 
@@ -161,10 +156,7 @@ def sharpness(frames, roi=None, return_sums=False):
         if d.stride(2) != 1:
             d = d.contiguous()
         n, H, W = d.shape
-        ctx = context(frames.device.index or 0)
-        check(lib().mvsv_set_stream(ctx.handle,
-                                    ctypes.c_void_p(torch.cuda.current_stream(frames.device).cuda_stream)),
-              ctx.handle)
+        ctx = device_context(frames)
         out = torch.empty((n,), dtype=torch.int64, device=frames.device)
         check(lib().mvsv_sharpness_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
                                           ctypes.byref(r) if r is not None else None, out.data_ptr()), ctx.handle)
@@ -177,8 +169,7 @@ def sharpness(frames, roi=None, return_sums=False):
             a = np.ascontiguousarray(a)
         batched = a.ndim == 3
         H, W = a.shape[-2:]
-        ctx = context(0)
-        check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+        ctx = host_context()
         sums = np.empty(len(a) if batched else 1, np.int64)
         for i, f in enumerate(a if batched else a[None]):
             s4 = ctypes.c_int64(0)
@@ -223,9 +214,7 @@ def prepare_gray(bgr, halve=True, variant=_lib.GRAY_Q14):
             d = d.contiguous()
         n, H, W, _ = d.shape
         w, h = prepare_size(W, H, halve)
-        ctx = context(bgr.device.index or 0)
-        check(lib().mvsv_set_stream(ctx.handle, ctypes.c_void_p(torch.cuda.current_stream(bgr.device).cuda_stream)),
-              ctx.handle)
+        ctx = device_context(bgr)
         out = torch.empty((n, h, w), dtype=torch.uint8, device=bgr.device)
         check(lib().mvsv_prepare_gray_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H, hv,
                                              int(variant), out.data_ptr(), w, h * w), ctx.handle)
@@ -240,8 +229,7 @@ def prepare_gray(bgr, halve=True, variant=_lib.GRAY_Q14):
     w, h = prepare_size(W, H, halve)
     frames = a if batched else a[None]
     out = np.empty((len(frames), h, w), np.uint8)
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     for f, o in zip(frames, out):
         check(lib().mvsv_prepare_gray(ctx.handle, f.ctypes.data, f.strides[0], W, H, hv, int(variant), o.ctypes.data,
                                       w), ctx.handle)
@@ -255,19 +243,10 @@ def reproject(dmap, Q):
     float32 tensor (..., H, W, 4) = (X, Y, Z, valid) with valid = (d > 0).
     """
     import torch
-    if not (type(dmap).__module__.startswith("torch") and dmap.is_cuda and dmap.dtype == torch.int16):
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "reproject: int16 device tensor expected")
-    batched = dmap.dim() == 3
-    d = dmap if batched else dmap.unsqueeze(0)
-    if d.stride(2) != 1:
-        d = d.contiguous()
+    d, batched, ctx = _device_frames(dmap, "reproject", any_rank=True)
     n, H, W = d.shape
     out = torch.empty((n, H, W, 4), dtype=torch.float32, device=dmap.device)
     q = _q16(Q)
-    ctx = context(dmap.device.index or 0)
-    check(lib().mvsv_set_stream(ctx.handle,
-                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
-          ctx.handle)
     check(lib().mvsv_reproject_device(ctx.handle, n, d.data_ptr(), d.stride(1), d.stride(0), W, H,
                                       q.ctypes.data, out.data_ptr(), W, H * W), ctx.handle)
     return out if batched else out[0]
@@ -280,20 +259,26 @@ def _is_device_map(d) -> bool:
     return d.is_cuda and d.dtype == torch.int16 and d.dim() in (2, 3)
 
 
-def _device_frames(dmap, what):
-    """(frames view (N, H, W) with unit column stride, batched, context) of an int16 device map."""
+def _host_map(dmap, what, dims=(2,)):
+    """An int16 host map, 2-D (or a batch, with dims=(2, 3)), as an array with unit column stride."""
+    d = np.asarray(dmap)
+    if d.ndim not in dims or d.dtype != np.int16:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: {'2-D or 3-D' if 3 in dims else '2-D'} int16 map expected")
+    return d if d.strides[-1] == 2 else np.ascontiguousarray(d)
+
+
+def _device_frames(dmap, what, any_rank=False):
+    """(frames view (N, H, W) with unit column stride, batched, context bound to the
+    current stream) of an int16 device map, 2-D or 3-D; any_rank: the rank is not checked."""
     import torch
-    if not _is_device_map(dmap):
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: 2-D or 3-D int16 device tensor expected")
+    ok = type(dmap).__module__.startswith("torch") and dmap.is_cuda and dmap.dtype == torch.int16
+    if not (ok and (any_rank or dmap.dim() in (2, 3))):
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, f"{what}: {'' if any_rank else '2-D or 3-D '}int16 device tensor expected")
     batched = dmap.dim() == 3
     d = dmap if batched else dmap.unsqueeze(0)
     if d.stride(2) != 1:
         d = d.contiguous()
-    ctx = context(dmap.device.index or 0)
-    check(lib().mvsv_set_stream(ctx.handle,
-                                ctypes.c_void_p(torch.cuda.current_stream(dmap.device).cuda_stream)),
-          ctx.handle)
-    return d, batched, ctx
+    return d, batched, device_context(dmap)
 
 
 def minmax(dmap, positive_only=False):
@@ -338,11 +323,7 @@ def normalize_minmax(dmap, alpha=0, beta=255, out=None, return_minmax=False):
         if return_minmax:
             return out, (mm if batched else mm[0])
         return out
-    d = np.asarray(dmap)
-    if d.ndim not in (2, 3) or d.dtype != np.int16:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "normalize_minmax: 2-D or 3-D int16 map expected")
-    if d.strides[-1] != 2:
-        d = np.ascontiguousarray(d)
+    d = _host_map(dmap, "normalize_minmax", dims=(2, 3))
     if out is None:
         out = np.empty(d.shape, np.uint8)
     elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.shape == d.shape and out.strides[-1] == 1):
@@ -351,8 +332,7 @@ def normalize_minmax(dmap, alpha=0, beta=255, out=None, return_minmax=False):
     frames = d if d.ndim == 3 else d[None]
     outs = out if d.ndim == 3 else out[None]
     mm = np.empty((len(frames), 2), np.int16)
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     for f, o, m in zip(frames, outs, mm):
         check(lib().mvsv_normalize_minmax(ctx.handle, f.ctypes.data, f.strides[0] // 2, f.shape[1], f.shape[0],
                                           float(alpha), float(beta), o.ctypes.data, o.strides[0], m.ctypes.data),
@@ -448,11 +428,7 @@ def detection_view(dmap, layers, means=None, mean_range=None, values=None, sampl
         if return_minmax:
             return out, (mm if batched else mm[0])
         return out
-    d = np.asarray(dmap)
-    if d.ndim not in (2, 3) or d.dtype != np.int16:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "detection_view: 2-D or 3-D int16 map expected")
-    if d.strides[-1] != 2:
-        d = np.ascontiguousarray(d)
+    d = _host_map(dmap, "detection_view", dims=(2, 3))
     if out is None:
         out = np.empty(d.shape + (3,), np.uint8)
     elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.shape == d.shape + (3,) and
@@ -472,8 +448,7 @@ def detection_view(dmap, layers, means=None, mean_range=None, values=None, sampl
         if hv.shape[1] == 0:
             hv = np.zeros((n, 1), np.float32)  # no lattice: a pointer that is never read
     mm = np.empty((n, 2), np.int16)
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     for k, (f, o, m) in enumerate(zip(frames, outs, mm)):
         spec.means = hm[k].ctypes.data if hm is not None else None
         spec.values = hv[k].ctypes.data if hv is not None else None
@@ -553,11 +528,7 @@ def point_cloud(dmap, Q, max_points=None, return_minmax=False, out=None):
         if return_minmax:
             return out, c, (mm if batched else mm[0])
         return out, c
-    d = np.asarray(dmap)
-    if d.ndim != 2 or d.dtype != np.int16:
-        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "point_cloud: 2-D int16 map expected")
-    if d.strides[1] != 2:
-        d = np.ascontiguousarray(d)
+    d = _host_map(dmap, "point_cloud")
     cap = d.size if max_points is None else int(max_points)
     if cap < 1:
         raise MvsvError(_lib.MVSV_E_INVALID_ARG, "point_cloud: max_points must be at least 1")
@@ -565,8 +536,7 @@ def point_cloud(dmap, Q, max_points=None, return_minmax=False, out=None):
     rec = np.empty(cap, CLOUD_DTYPE)
     count = ctypes.c_int(0)
     mm = np.zeros(2, np.int32)
-    ctx = context(0)
-    check(lib().mvsv_use_own_stream(ctx.handle), ctx.handle)
+    ctx = host_context()
     check(lib().mvsv_point_cloud(ctx.handle, d.ctypes.data, d.strides[0] // 2, d.shape[1], d.shape[0],
                                  q.ctypes.data, rec.ctypes.data, cap, ctypes.byref(count), mm.ctypes.data),
           ctx.handle)
