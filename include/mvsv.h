@@ -7,7 +7,9 @@
  *   mvsv_sgbm / mvsv_sgbm_device      Disparity::sgbm        src/disparity.cpp:6-10,
  *                                     decl inc/disparity.h:29 (forwards to
  *                                     cv::StereoSGBM::compute, also called
- *                                     directly at trgt/liveDisparity.cpp:91)
+ *                                     directly at trgt/liveDisparity.cpp:91);
+ *                                     modes MODE_SGBM, MODE_HH and MODE_HH4
+ *                                     (MODE_SGBM_3WAY is refused by name)
  *   mvsv_bm / mvsv_bm_device          Disparity::bm          src/disparity.cpp:18-22,
  *                                     decl inc/disparity.h:31
  *   mvsv_load_sgbm_yaml               Disparity::loadSGBMParameters
@@ -152,7 +154,11 @@ enum {
      * size -- all line directions side by side for launches that would fill
      * at most half the GPU with sheared strips (one camera frame; needs
      * P2 <= 15),
-     * sheared strips otherwise; 1 = strips; 2 = directions side by side */
+     * sheared strips otherwise; 1 = strips; 2 = directions side by side.
+     * MODE_HH4 has no diagonal path and never runs strips: 0 = side by side
+     * (nibble planes for P2 <= 15, byte / u16 planes while the three planes
+     * stay small), else one launch per direction; 1 = one launch per
+     * direction on byte / u16 planes; 2 = side by side */
     MVSV_OPT_PATH_SCHEDULE = 4,
     /* which strip a block of the sheared-strip kernel runs: 1 (default) = a
      * ticket drawn on arrival, so a strip only waits on a strip already
@@ -173,8 +179,13 @@ enum {
     MVSV_OPT_BITSLICE = 7
 };
 
-/* StereoSGBM modes (cv::StereoSGBM::MODE_SGBM / MODE_HH). */
-enum { MVSV_MODE_SGBM = 0, MVSV_MODE_HH = 1 };
+/* StereoSGBM modes (cv::StereoSGBM::MODE_SGBM / MODE_HH / MODE_HH4).
+ * MODE_HH4: four paths (L->R, R->L, down, up) on the cost volume without
+ * OpenCV 3.4's cost-row quirks (MVSV_VARIANT_FIRSTCOL_FIX has no effect); the
+ * WTA tie rule is MODE_SGBM's.  MVSV_MODE_SGBM_3WAY is named only so that it
+ * can be refused by name: its result depends on OpenCV's stripe split, which
+ * this library does not restate (MVSV_E_INVALID_ARG). */
+enum { MVSV_MODE_SGBM = 0, MVSV_MODE_HH = 1, MVSV_MODE_SGBM_3WAY = 2, MVSV_MODE_HH4 = 3 };
 /* StereoBM prefilter types (cv::StereoBM::PREFILTER_*). */
 enum { MVSV_PREFILTER_NORMALIZED_RESPONSE = 0, MVSV_PREFILTER_XSOBEL = 1 };
 
@@ -195,7 +206,7 @@ typedef struct {
     int uniqueness_ratio;    /* setUniquenessRatio (< 0 -> 10) */
     int speckle_window_size; /* setSpeckleWindowSize (0 disables speckle filter) */
     int speckle_range;       /* setSpeckleRange (multiplied by 16) */
-    int mode;                /* MVSV_MODE_SGBM (5 paths) or MVSV_MODE_HH (8 paths) */
+    int mode;                /* MVSV_MODE_SGBM (5 paths), MVSV_MODE_HH (8) or MVSV_MODE_HH4 (4) */
     int variant;             /* MVSV_VARIANT_* bits, 0 = OpenCV 3.4 */
 } mvsv_sgbm_params;
 

@@ -20,13 +20,27 @@
 
 namespace mvsv_cv {
 
+// cv::StereoSGBM's mode as an MVSV_MODE_* value.  The two enumerations have the
+// same values (MODE_SGBM 0, MODE_HH 1, MODE_SGBM_3WAY 2, MODE_HH4 3), so a mode
+// this library does not run -- MODE_SGBM_3WAY, or a value of a later release --
+// reaches mvsv_sgbm as it is and compute() throws its message; no mode is run
+// as another one.
+inline int mode_of(const cv::StereoSGBM& m)
+{
+    const int mode = m.getMode();
+    if (mode == cv::StereoSGBM::MODE_HH) return MVSV_MODE_HH;
+    if (mode == cv::StereoSGBM::MODE_SGBM) return MVSV_MODE_SGBM;
+    static_assert(MVSV_MODE_SGBM_3WAY == 2 && MVSV_MODE_HH4 == 3, "cv::StereoSGBM's mode values");
+    return mode;
+}
+
 inline mvsv_sgbm_params params_of(const cv::StereoSGBM& m)
 {
     mvsv_sgbm_params p;
     mvsv_sgbm_params_create(&p, m.getMinDisparity(), m.getNumDisparities(), m.getBlockSize(),
                             m.getP1(), m.getP2(), m.getDisp12MaxDiff(), m.getPreFilterCap(),
                             m.getUniquenessRatio(), m.getSpeckleWindowSize(), m.getSpeckleRange(),
-                            m.getMode() == cv::StereoSGBM::MODE_HH ? MVSV_MODE_HH : MVSV_MODE_SGBM);
+                            mode_of(m));
     return p;
 }
 

@@ -145,7 +145,8 @@ inline void check_sgbm_pair(const Mat& L, const Mat& R)
 
 class StereoSGBM {
 public:
-    enum { MODE_SGBM = MVSV_MODE_SGBM, MODE_HH = MVSV_MODE_HH };
+    // (MODE_SGBM_3WAY is not offered: mvsv_sgbm refuses it by name)
+    enum { MODE_SGBM = MVSV_MODE_SGBM, MODE_HH = MVSV_MODE_HH, MODE_HH4 = MVSV_MODE_HH4 };
     static Ptr<StereoSGBM> create(int minDisparity = 0, int numDisparities = 16,
                                   int blockSize = 3, int P1 = 0, int P2 = 0,
                                   int disp12MaxDiff = 0, int preFilterCap = 0,

@@ -6,7 +6,7 @@ src/disparity.cpp:6-108).  Compute lives in hand-written HIP kernels for
 gfx950 behind the C ABI of libmvsv.so (include/mvsv.h); this package is the
 host-side mirror of the reference interface.
 """
-from ._lib import (GRAY_Q14, GRAY_Q15, MATCHER_BM, MATCHER_SGBM, MODE_HH, MODE_SGBM, MVSV_E_TIMEOUT, MVSV_HOST_ALL,
+from ._lib import (GRAY_Q14, GRAY_Q15, MATCHER_BM, MATCHER_SGBM, MODE_HH, MODE_HH4, MODE_SGBM, MVSV_E_TIMEOUT, MVSV_HOST_ALL,
                    MVSV_HOST_DISPLAY, MVSV_HOST_MAP, MVSV_HOST_RECTIFIED, MVSV_HOST_VIEW, OPT_BITSLICE, OPT_BM_TILE_ROWS, OPT_PATH_SCHEDULE,
                    OPT_STRIP_SPIN_LIMIT, OPT_STRIP_WAVES,
                    PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, VARIANT_FIRSTCOL_FIX,
@@ -25,7 +25,7 @@ from .utility import (CLOUD_DTYPE, VIEW_FOUND_POINTS, VIEW_FOUND_TILES, VIEW_OBS
 
 __all__ = [
     "Disparity", "StereoBM", "StereoSGBM", "Stereopair", "sgbmParameters", "MvsvError",
-    "synth_pair", "mean_disparity_grid", "median_blur3", "filter_speckles", "MODE_SGBM", "MODE_HH", "PREFILTER_XSOBEL",
+    "synth_pair", "mean_disparity_grid", "median_blur3", "filter_speckles", "MODE_SGBM", "MODE_HH", "MODE_HH4", "PREFILTER_XSOBEL",
     "PREFILTER_NORMALIZED_RESPONSE", "VARIANT_FIRSTCOL_FIX", "VARIANT_WTA_MIN_D",
     "DisparityStream", "MeanDisparityDetection", "Subimage", "create_dmap_rois", "Utility",
     "dMapValues", "ply", "reproject", "init_undistort_rectify_map", "rectify_pair", "remap",

@@ -35,6 +35,8 @@ OPT_BITSLICE = 7
 
 MODE_SGBM = 0
 MODE_HH = 1
+MODE_SGBM_3WAY = 2  # refused by name (mvsv_sgbm_validate)
+MODE_HH4 = 3
 PREFILTER_NORMALIZED_RESPONSE = 0
 PREFILTER_XSOBEL = 1
 VARIANT_FIRSTCOL_FIX = 1

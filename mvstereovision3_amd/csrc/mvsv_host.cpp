@@ -136,8 +136,12 @@ int resolve_sgbm(const mvsv_sgbm_params* p, int W, int H, SgbmEff* e, std::strin
         *why = "numDisparities must be positive and divisible by 16";
         return MVSV_E_INVALID_ARG;
     }
-    if (p->mode != MVSV_MODE_SGBM && p->mode != MVSV_MODE_HH) {
-        *why = "mode must be MODE_SGBM (0) or MODE_HH (1)";
+    if (p->mode == MVSV_MODE_SGBM_3WAY) {
+        *why = "MODE_SGBM_3WAY (2) is not supported: mode must be MODE_SGBM (0), MODE_HH (1) or MODE_HH4 (3)";
+        return MVSV_E_INVALID_ARG;
+    }
+    if (p->mode != MVSV_MODE_SGBM && p->mode != MVSV_MODE_HH && p->mode != MVSV_MODE_HH4) {
+        *why = "mode must be MODE_SGBM (0), MODE_HH (1) or MODE_HH4 (3)";
         return MVSV_E_INVALID_ARG;
     }
     int bs = p->block_size > 0 ? p->block_size : 5;
@@ -156,6 +160,7 @@ int resolve_sgbm(const mvsv_sgbm_params* p, int W, int H, SgbmEff* e, std::strin
     e->W1 = e->maxX1 - e->minX1;
     e->invalid = (e->minD - 1) * kDispScale;
     e->fullDP = p->mode == MVSV_MODE_HH;
+    e->hh4 = p->mode == MVSV_MODE_HH4;
     e->variant = p->variant;
     e->speckle_window = p->speckle_window_size;
     e->speckle_diff = kDispScale * p->speckle_range;

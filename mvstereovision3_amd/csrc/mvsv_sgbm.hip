@@ -1535,7 +1535,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NP >= 8 ? 1 
     const uint32_t p2x2 = (uint32_t)(e.P2 & 0xffff) * 0x10001u;
     // S = min(ndir*(C - P2) + sum of deltas, MAX_COST) = min((ndir-1)*cb + L + acc, MAX_COST)
     // with cb = C - P2, L = cb + delta of the R->L direction computed here
-    const uint32_t ndm1 = (uint32_t)(e.fullDP ? 7 : 4) * 0x10001u;
+    const uint32_t ndm1 = (uint32_t)(sgbm_ndir(e) - 1) * 0x10001u;
     const int uq = e.uniq;
     // tie order of the WTA key: d, or OpenCV's SIMD lane order for MODE_SGBM
     uint32_t subk[2 * NP];
@@ -1698,7 +1698,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NP >= 8 ? 1 
     int pend_s0 = 0, pend_cnt = 0;
     const int16_t* crow = C + f * frame + (size_t)y * W1 * D;
     const uint16_t* mrowp = RESF ? Mv + ((size_t)f * H + y) * W1 : nullptr;
-    const int ndir = e.fullDP ? 8 : 5;
+    const int ndir = sgbm_ndir(e);
     const int clampS = ndir * 2 * e.P2;  // S'' >= this: C'' may be the clamp value
     auto rec_best = [&](uint32_t kK) {
         const int sub = (int)(kK & 0xffffu);
@@ -1839,7 +1839,7 @@ __global__ __launch_bounds__(64) void sgbm_final_kernel(const int16_t* __restric
     }
     const uint32_t p1x2 = (uint32_t)(e.P1 & 0xffff) * 0x10001u;
     const uint32_t p2x2 = (uint32_t)(e.P2 & 0xffff) * 0x10001u;
-    const bool eight = e.fullDP != 0;
+    const int ndir = sgbm_ndir(e);  // 8, 5 or 4
     int minp = 0;
     const int uq = e.uniq;
 
@@ -1869,8 +1869,9 @@ __global__ __launch_bounds__(64) void sgbm_final_kernel(const int16_t* __restric
             u16x2 cbv = __builtin_bit_cast(u16x2, c[p]) - __builtin_bit_cast(u16x2, p2x2);
             u16x2 x2 = __builtin_elementwise_add_sat(cbv, cbv);
             u16x2 x4 = __builtin_elementwise_add_sat(x2, x2);
-            u16x2 t = eight ? __builtin_elementwise_add_sat(x4, x4)
-                            : __builtin_elementwise_add_sat(x4, cbv);
+            u16x2 t = ndir == 8   ? __builtin_elementwise_add_sat(x4, x4)
+                      : ndir == 5 ? __builtin_elementwise_add_sat(x4, cbv)
+                                  : x4;
             u16x2 acc = __builtin_elementwise_add_sat(
                 __builtin_bit_cast(u16x2, sb[j][p]),
                 __builtin_bit_cast(u16x2, path_delta(ln[p], c[p], p2x2)));
@@ -2026,7 +2027,7 @@ __global__ __launch_bounds__(kWtaThreads) void sgbm_wta_planes_kernel(const int1
     __threadfence_block();
     __syncthreads();
     const bool lane_rule = !e.fullDP && !(e.variant & MVSV_VARIANT_WTA_MIN_D);
-    const int ndir = e.fullDP ? 8 : 5;
+    const int ndir = sgbm_ndir(e);
     const size_t row0 = ((size_t)f * H + y) * W1;
     const int sl = threadIdx.x % LPP, gbase = (int)(threadIdx.x & 63) - sl;  // lane in the pixel, its first lane
     const int d0 = 8 * sl;
@@ -2164,7 +2165,8 @@ void launch_final16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, const 
 }
 
 // the line directions: the first four are MODE_SGBM's, the first seven
-// MODE_HH's; the last is R->L as a chain set of its own (the split WTA form)
+// MODE_HH's, MODE_HH4's are L->R, down and up (sgbm_pass_dir picks a mode's
+// k-th); the last is R->L as a chain set of its own (the split WTA form)
 constexpr int kPathDirs[8][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}, {1, -1}, {0, -1}, {-1, -1}, {-1, 0}};
 
 template <int NP, int WV, int LPC, typename AccT, bool NW, bool RES>
@@ -2306,9 +2308,10 @@ int launch_paths_lines16(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, i
 {
     hipStream_t s = ctx->stream;
     AccT* dummy = (AccT*)ctx->dummy.ptr;
-    const int ndir = e.fullDP ? 7 : 4;
+    const int ndir = sgbm_ndir(e) - 1;
     for (int k = 0; k < ndir; k++) {
-        const int dx = kPathDirs[k][0], dy = kPathDirs[k][1];
+        const int* dir = kPathDirs[sgbm_pass_dir(e, k)];
+        const int dx = dir[0], dy = dir[1];
         dim3 grid((num_lines(dx, dy, e.W1, H) + 15) / 16, n);
         StageTimer tm(ctx, kStagePath);
         if (k == 0)
@@ -2329,9 +2332,10 @@ int launch_paths(mvsv_ctx* ctx, int n, int H, int W, const SgbmEff& e, int16_t* 
                  int16_t* raw)
 {
     hipStream_t s = ctx->stream;
-    const int ndir = e.fullDP ? 7 : 4;
+    const int ndir = sgbm_ndir(e) - 1;
     for (int k = 0; k < ndir; k++) {
-        const int dx = kPathDirs[k][0], dy = kPathDirs[k][1];
+        const int* dir = kPathDirs[sgbm_pass_dir(e, k)];
+        const int dx = dir[0], dy = dir[1];
         int nl = num_lines(dx, dy, e.W1, H);
         dim3 grid((nl + 3) / 4, n);
         StageTimer tm(ctx, kStagePath);
@@ -2374,7 +2378,7 @@ int launch_paths_dirs(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, 
     PathDirs pd{};
     int maxnl = 0;
     for (int k = 0; k < ndir; k++) {
-        const int* d = kPathDirs[plan.split && k == ndir - 1 ? 7 : k];
+        const int* d = kPathDirs[plan.split && k == ndir - 1 ? kPathDirRL : sgbm_pass_dir(e, k)];
         pd.dx[k] = d[0];
         pd.dy[k] = d[1];
         maxnl = std::max(maxnl, num_lines(pd.dx[k], pd.dy[k], e.W1, H));
@@ -2402,6 +2406,8 @@ int launch_paths_dirs(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, 
     }
     if (ndir == 7)
         launch_final16<NP, 7, AccT, NW, RES, LPC>(ctx, n, H, W, e, Cv, Av, plane, raw, Cin, Mv);
+    else if (ndir == 3)
+        launch_final16<NP, 3, AccT, NW, RES, LPC>(ctx, n, H, W, e, Cv, Av, plane, raw, Cin, Mv);
     else
         launch_final16<NP, 4, AccT, NW, RES, LPC>(ctx, n, H, W, e, Cv, Av, plane, raw, Cin, Mv);
     return check_hip(ctx, hipGetLastError(), "sgbm path kernels (directions side by side)");
@@ -2578,9 +2584,10 @@ int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, c
         // bit-sliced layouts (MODE_SGBM: copied rows / column 0; MODE_HH: pinned
         // by the cost kernel)
         if ((rc = bsgm_cost_fixup(ctx, n, H, e, Cv, Bv, Mv))) return rc;
-    } else if (H > 1 && !(plan.cost2 && e.fullDP)) {
+    } else if (H > 1 && !e.hh4 && !(plan.cost2 && e.fullDP)) {
         // OpenCV 3.4's never-recomputed rows and column 0 (mvsv_cost.hip; the
-        // register-ring kernel pins MODE_HH's itself)
+        // register-ring kernel pins MODE_HH's itself).  MODE_HH4 keeps the clean
+        // volume both cost kernels compute.
         if ((rc = launch_cost_fixup(ctx, n, H, e, Cv, Rv, Mv))) return rc;
     }
 

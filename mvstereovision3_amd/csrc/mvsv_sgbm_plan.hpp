@@ -37,7 +37,21 @@ struct SgbmEff {
     // colour channels of the pair: 1 (grey; resolve_sgbm) or 3 (interleaved BGR,
     // set by the colour entry points).  A pixel cost is <= cn * (2*ftzero + 63).
     int cn;
+    // MODE_HH4: the four axis directions L->R, R->L, down, up on the clean cost
+    // volume (no 3.4 cost-row quirk).  0 for MODE_SGBM / MODE_HH; fullDP stays 0
+    // (the WTA is fused with the R->L pass, so MODE_SGBM's tie rule applies).
+    int hh4;
 };
+
+// The path directions of a mode, counted with R->L (which the final kernels
+// run): 5 (MODE_SGBM), 8 (MODE_HH), 4 (MODE_HH4).  The direction passes run
+// the other sgbm_ndir - 1; sgbm_pass_dir names the k-th of them as a row of
+// kPathDirs (mvsv_sgbm.hip): {(1,0) (1,1) (0,1) (-1,1) (1,-1) (0,-1) (-1,-1)
+// (-1,0)} -- the first four are MODE_SGBM's, the first seven MODE_HH's, and
+// MODE_HH4 takes L->R, down and up.
+MVSV_HD inline int sgbm_ndir(const SgbmEff& e) { return e.hh4 ? 4 : e.fullDP ? 8 : 5; }
+MVSV_HD inline int sgbm_pass_dir(const SgbmEff& e, int k) { return !e.hh4 ? k : k == 0 ? 0 : k == 1 ? 2 : 5; }
+constexpr int kPathDirRL = 7;  // R->L as a chain set of its own (the split WTA form)
 
 // Default number of polls a strip-boundary wait of the sheared-strip kernel
 // makes before it gives up (each poll = one s_sleep + one L2 load of the
@@ -115,7 +129,7 @@ inline bool sgbm_no_wrap(const SgbmEff& e)
 }
 
 // u8 accumulator when the summed path deltas (each <= P2) fit a byte
-MVSV_HD inline bool acc_is_u8(const SgbmEff& e) { return (e.fullDP ? 8 : 5) * e.P2 <= 255; }
+MVSV_HD inline bool acc_is_u8(const SgbmEff& e) { return sgbm_ndir(e) * e.P2 <= 255; }
 // 4-bit accumulator planes: the sheared-strip schedule writes one plane per
 // group of at most three directions (3 strip directions, or the L->R line),
 // so each plane holds sums <= 3 * P2; with P2 <= 5 (OpenCV's default P2 = 5,
@@ -158,7 +172,7 @@ inline bool cost2_runs(const KernelOptions& o, const SgbmEff& e)
 // test, no int16 wrap) and int32 word offsets cover the C' planes
 inline bool bsgm_eligible(const KernelOptions& o, const SgbmEff& e, int n, int H)
 {
-    return e.cn == 1 && o.bitslice && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && sgbm_no_wrap(e) &&
+    return e.cn == 1 && !e.hh4 && o.bitslice && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && sgbm_no_wrap(e) &&
            e.W1 > 0 && (size_t)n * H * bs::padq(e.W1) * 16 < ((size_t)1 << 31);
 }
 
@@ -192,8 +206,37 @@ inline bool use_strips(const KernelOptions& o, const SgbmEff& e, int H)
 // per direction, P2 <= 15) -- the latency shape for launches too small to fill
 // the chip with strips (one camera frame); 1 = sheared strips (batches).
 // path_sched: 0 = by launch size, 1 / 2 force (tests, A/B).
+//
+// MODE_HH4 has no diagonal direction, so every launch is a set of independent
+// chains and schedule 1 (strips) never runs: side by side (2) on nibble planes
+// (P2 <= 15), on byte / u16 planes while the three planes stay within
+// kHh4SidePlaneBytes, else one launch per direction into one plane (0).
+// path_sched 1 forces that last shape (there are no strips to force).
+//
+// The plane-byte bound: MODE_SGBM / MODE_HH leave side by side at 1.4 GB of
+// planes because the strip chain overtakes it there.  MODE_HH4's alternative is
+// one launch per direction, which reads and writes its single plane three times
+// and never overtook the three planes: measured (MI355X, tools/hh4_bench.py,
+// create(0, 64, 9, 648, 2592) at 1280x960, forced schedule 1 against 2, ms):
+// x 1 0.76 / 0.55, x 2 0.97 / 0.83, x 3 1.23 / 1.20, x 4 1.82 / 1.64, x 8 (3.59 GB
+// of planes) 3.33 / 3.16.  No crossover up to the largest launch measured, so the
+// bound sits there: beyond it nothing is measured and the per-direction schedule
+// keeps the planes at a third of the bytes.
+constexpr double kHh4SidePlaneBytes = 3.6e9;
+inline int path_schedule_hh4(const KernelOptions& o, const SgbmEff& e, int H, int n)
+{
+    if (e.D == 16 && o.path16 && o.path_sched != 1) return 2;
+    if (!o.path16 || !(e.D == 32 || e.D == 64 || e.D == 128 || e.D == 256)) return 0;
+    if (o.path_sched == 2) return 2;
+    if (o.path_sched == 1) return 0;
+    if (e.P2 <= 15) return 2;
+    const double bytes = (double)n * e.W1 * H * e.D * (sgbm_ndir(e) - 1) * (acc_is_u8(e) ? 1 : 2);
+    return bytes <= kHh4SidePlaneBytes ? 2 : 0;
+}
+
 inline int path_schedule(const KernelOptions& o, int cus, const SgbmEff& e, int H, int n)
 {
+    if (e.hh4) return path_schedule_hh4(o, e, H, n);
     // D = 16 (captureDisparity's create(0, 16, 5, 200, 800)): the directions
     // side by side at 8 lanes per line in every launch shape -- the per-pixel
     // work is small enough that the planes' traffic never outweighs the
@@ -393,7 +436,7 @@ inline SgbmPlan sgbm_make_plan(const KernelOptions& o, int cus, const SgbmEff& e
     // per strip pass + lines (sums <= 3 * P2); bytes when all directions' sum
     // fits, else u16
     p.split = p.sched == 2 && wta_split(o, e);
-    p.nplanes = p.sched == 2 ? (e.fullDP ? 7 : 4) + (p.split ? 1 : 0) : p.sched == 1 ? p.passes + 1 : 1;
+    p.nplanes = p.sched == 2 ? sgbm_ndir(e) - 1 + (p.split ? 1 : 0) : p.sched == 1 ? p.passes + 1 : 1;
     p.acc = ((p.sched == 2 && e.P2 <= 15) || (p.sched == 1 && acc_is_nib(e))) ? kAccNib
             : acc_is_u8(e)                                                   ? kAccU8
                                                                              : kAccU16;

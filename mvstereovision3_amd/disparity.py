@@ -31,7 +31,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (MODE_HH, MODE_SGBM, PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL,
+from ._lib import (MODE_HH, MODE_HH4, MODE_SGBM, PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL,
                    BmParams, MvsvError, SgbmParams, SgbmYamlValues, check, device_context, host_context, lib)
 from .utility import _device_frames
 
@@ -200,6 +200,7 @@ class StereoSGBM(StereoMatcher):
     """cv::StereoSGBM (OpenCV 3.4 semantics) backed by the MI355X kernels."""
     MODE_SGBM = MODE_SGBM
     MODE_HH = MODE_HH
+    MODE_HH4 = MODE_HH4
 
     def __init__(self, params: SgbmParams):
         self._params = params
