@@ -1,6 +1,6 @@
 // mvsv_bsgm.hip — bit-sliced MODE_HH path aggregation (round 5).
 //
-// The same eight SGM directions as the packed-int16 kernels of mvsv_sgbm.hip
+// The same eight SGM directions as the packed-int16 kernels of mvsv_sgbm_*.hpp
 // (OpenCV 3.4 computeDisparitySGBM, reached through Disparity::sgbm /
 // loadSGBMParameters, /root/reference/src/disparity.cpp:6-10,92-95; semantics in
 // SURVEY.md Appendix A.4-A.5), restated on bit planes (mvsv_bitslice.hpp): in
@@ -1070,7 +1070,7 @@ __global__ __launch_bounds__(kBsFinThreads) void bsgm_rl_final_kernel(const uint
 
 // ---------------------------------------------------------------------------
 // MODE_SGBM's cost-row quirks on the bit-sliced layouts (OpenCV 3.4, SURVEY
-// Appendix A.3; the int16 form is sgbm_cost_fixup_*_kernel in mvsv_sgbm.hip):
+// Appendix A.3; the int16 form is sgbm_cost_fixup_*_kernel in mvsv_cost.hip):
 // rows y >= ybot = H - SH2 are never recomputed and keep row ylast, and
 // (without MVSV_VARIANT_FIRSTCOL_FIX) column 0 of every row y >= 1 keeps C(0, 0).
 // A pixel's C' words, its pixel-quad C and its minimum m move together.  MODE_HH

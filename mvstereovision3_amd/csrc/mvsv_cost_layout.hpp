@@ -1,5 +1,5 @@
 // mvsv_cost_layout.hpp — tile geometry and staging address arithmetic of the
-// register-ring cost-volume kernel (sgbm_cost2_kernel, mvsv_sgbm.hip).  The
+// register-ring cost-volume kernel (sgbm_cost2_kernel, mvsv_cost.hip).  The
 // kernel computes every global staging offset and LDS slot through these
 // functions, and tests/cpp/cost_layout_check.cpp runs the same functions on the
 // host over every tile of every (D, blockSize, tile height, image) shape the

@@ -205,6 +205,13 @@ int launch_cost_fixup(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, int16_t* Cv
 // computes raw disparities from them, on the plan's schedule, strip width and planes.
 int bsgm_paths(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, const int16_t* Cv,
                const uint32_t* Bv, const uint16_t* Mv, int16_t* raw);
+// The packed-int16 path kernels + WTA at 16 lanes per line, D = 32 NP (NP = 1, 2, 4, 8):
+// launches the template instance for the plan's schedule, plane element, recurrence and
+// cost input (Rv: the residual plane).  Each NP is instantiated in an object of its own
+// (mvsv_sgbm_packed.hip, compiled with -DMVSV_SGBM_NP=NP).
+template <int NP>
+int launch_packed16(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int H, int W, const SgbmEff& e, int16_t* Cv,
+                    const uint8_t* Rv, const uint16_t* Mv, void* Av, int16_t* raw);
 // The second stream and its fork / join events (the L->R lines beside the strips)
 int ensure_aux(mvsv_ctx* ctx);
 // The preamble of a strip launch, packed or bit-sliced (one launch counter for both).

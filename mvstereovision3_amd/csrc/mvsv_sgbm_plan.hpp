@@ -46,7 +46,7 @@ struct SgbmEff {
 // The path directions of a mode, counted with R->L (which the final kernels
 // run): 5 (MODE_SGBM), 8 (MODE_HH), 4 (MODE_HH4).  The direction passes run
 // the other sgbm_ndir - 1; sgbm_pass_dir names the k-th of them as a row of
-// kPathDirs (mvsv_sgbm.hip): {(1,0) (1,1) (0,1) (-1,1) (1,-1) (0,-1) (-1,-1)
+// kPathDirs (mvsv_sgbm_lines.hpp): {(1,0) (1,1) (0,1) (-1,1) (1,-1) (0,-1) (-1,-1)
 // (-1,0)} -- the first four are MODE_SGBM's, the first seven MODE_HH's, and
 // MODE_HH4 takes L->R, down and up.
 MVSV_HD inline int sgbm_ndir(const SgbmEff& e) { return e.hh4 ? 4 : e.fullDP ? 8 : 5; }
@@ -184,7 +184,7 @@ inline bool bsgm_eligible(const KernelOptions& o, const SgbmEff& e, int n, int H
 // the chain-free WTA saves); MODE_HH D 64 1.01 either way
 inline bool wta_split(const KernelOptions& o, const SgbmEff& e) { return o.final_split && e.P2 > 15 && e.D <= 32; }
 
-// The direction passes read the residual plane (mvsv_sgbm.hip) when it is
+// The direction passes read the residual plane (CostIn, mvsv_sgbm_common.hpp) when it is
 // exact and smaller: no-wrap regime, residuals <= 3 * P2 in a nibble, a
 // 16-lane path schedule (1 = strips + lines, 2 = side by side) and D <= 128
 // (one cost kernel wave segment holds a pixel's D costs).  Written by the

@@ -337,7 +337,7 @@ static void check_transpose(std::mt19937& rng)
             ref[q] = 0;
             for (int p = 0; p < 32; p++) ref[q] |= (uint32_t)((cv[k][2 * p + e] >> b) & 1) << p;
         }
-        // stages s = 16, 8, 4, 2, 1 (mirrors bs_transpose32 in mvsv_sgbm.hip)
+        // stages s = 16, 8, 4, 2, 1 (mirrors bs_transpose32 in mvsv_cost.hip)
         static const uint32_t Mk[5] = {0x55555555u, 0x33333333u, 0x0F0F0F0Fu, 0x00FF00FFu, 0x0000FFFFu};
         for (int j = 4; j >= 0; j--) {
             const int s = 1 << j;
@@ -356,7 +356,7 @@ static void check_transpose(std::mt19937& rng)
 }
 
 // The grouped plane layouts: the cost kernel's store word for transpose lane
-// p of the wave's four columns (mvsv_sgbm.hip) is cq_word's (column c, q =
+// p of the wave's four columns (mvsv_cost.hip) is cq_word's (column c, q =
 // 2 h + e) word + bit b, and both layouts tile a row of groups exactly.
 static void check_layouts()
 {

@@ -1,5 +1,5 @@
 // cost_layout_check.cpp — exhaustive bounds check of the register-ring cost
-// kernel's addresses (sgbm_cost2_kernel, mvsv_sgbm.hip) on the host.
+// kernel's addresses (sgbm_cost2_kernel, mvsv_cost.hip) on the host.
 //
 // The kernel takes its tile geometry, global staging offsets and LDS slots from
 // mvsv_cost_layout.hpp; this program runs the same functions for every tile,

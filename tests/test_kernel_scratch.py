@@ -15,10 +15,10 @@ create(0, 16, 5, 200, 800)) dispatch at batches of 1, 2 and 8 frames --
 recorded on the GPU by tools/gpu_census.sh into tests/golden/dispatch_census.json
 -- must carry no scratch either.
 """
+import importlib.util
 import json
 import os
 import re
-import struct
 import subprocess
 import tempfile
 
@@ -32,39 +32,25 @@ HEADLINE = [r"bsgm_", r"sgbm_cost2_kernelILi13ELi1ELi64E", r"sgbm_prefilter_kern
             r"median3x3_pk_kernel", r"speckle_"]
 
 
+def _kernel_diff():
+    """tools/kernel_diff.py: the fat-binary walk and the metadata reader live there."""
+    spec = importlib.util.spec_from_file_location("kernel_diff", os.path.join(ROOT, "tools", "kernel_diff.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def kernel_scratch():
     """{mangled kernel name: private segment bytes} over every gfx950 code object."""
+    kd = _kernel_diff()
+    out = {}
     with tempfile.TemporaryDirectory() as td:
-        fat = os.path.join(td, "fat.bin")
-        subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", LIB,
-                        os.path.join(td, "x.so")], check=True, capture_output=True)
-        b = open(fat, "rb").read()
-        out = {}
-        magic = b"__CLANG_OFFLOAD_BUNDLE__"
-        i = b.find(magic)
-        while i >= 0:
-            n = struct.unpack_from("<Q", b, i + len(magic))[0]
-            p = i + len(magic) + 8
-            for _ in range(n):
-                off, size, tl = struct.unpack_from("<QQQ", b, p)
-                p += 24
-                triple = b[p:p + tl].decode()
-                p += tl
-                if "gfx950" in triple and size:
-                    co = os.path.join(td, "dev.co")
-                    open(co, "wb").write(b[i + off:i + off + size])
-                    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True,
-                                           capture_output=True, text=True).stdout
-                    name = None
-                    for line in notes.splitlines():
-                        m = re.match(r"\s+\.name:\s+(\S+)", line)
-                        if m:
-                            name = m.group(1)
-                        m = re.match(r"\s+\.private_segment_fixed_size:\s+(\d+)", line)
-                        if m and name:
-                            out[name] = int(m.group(1))
-            i = b.find(magic, i + 1)
-        return out
+        co = os.path.join(td, "dev.co")
+        for image in kd.code_objects(LIB):
+            open(co, "wb").write(image)
+            for name, meta in kd.kernel_metadata(co):
+                out[name] = meta[".private_segment_fixed_size"]
+    return out
 
 
 @pytest.mark.skipif(not os.path.exists(LIB) or not os.path.exists(f"{LLVM}/llvm-readelf"),

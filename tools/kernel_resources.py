@@ -5,9 +5,11 @@ spilled VGPRs and scratch bytes per lane (a spilled kernel sends its spills
 through the vector memory path: scratch loads park the wave, and evicted
 scratch lines reach HBM as WRITE_SIZE the algorithm does not account for).
 
-    python tools/kernel_resources.py [--filter REGEX] [--all] [-D NAME=VAL ...] [FILES...]
+    python tools/kernel_resources.py [--filter REGEX] [--all] [-D NAME=VAL ...] [FILE[:NAME=VAL]...]
 
-Without --all only kernels with scratch are listed.
+Without --all only kernels with scratch are listed.  FILE:NAME=VAL compiles FILE
+with that define on top of the -D ones: mvsv_sgbm_packed.hip holds one disparity
+count per MVSV_SGBM_NP, and the default list takes one pass for each.
 """
 import argparse
 import os
@@ -18,7 +20,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mvstereovision3_amd", "csrc")
-DEFAULT = ["mvsv_cost.hip", "mvsv_sgbm.hip", "mvsv_bsgm.hip", "mvsv_bm.hip", "mvsv_post.hip"]
+DEFAULT = (["mvsv_cost.hip", "mvsv_sgbm.hip"] + [f"mvsv_sgbm_packed.hip:MVSV_SGBM_NP={n}" for n in (1, 2, 4, 8)] +
+           ["mvsv_bsgm.hip", "mvsv_bm.hip", "mvsv_post.hip"])
 
 
 def demangle(names):
@@ -67,7 +70,8 @@ def main():
     ap.add_argument("-D", dest="defines", action="append", default=[])
     a = ap.parse_args()
     for f in a.files:
-        for r in audit(f, a.defines):
+        src, _, define = f.partition(":")
+        for r in audit(src, a.defines + ([define] if define else [])):
             if a.filter and not re.search(a.filter, r["name"]):
                 continue
             if a.all or r.get("scratch", 0) > 0:
