@@ -10,6 +10,10 @@
  *                                     directly at trgt/liveDisparity.cpp:91);
  *                                     modes MODE_SGBM, MODE_HH and MODE_HH4
  *                                     (MODE_SGBM_3WAY is refused by name)
+ *   mvsv_sgbm_census(_device) /       Disparity::binary_sgbm src/disparity.cpp:12-15,
+ *   mvsv_census(_device)              decl inc/disparity.h:30 (commented out in the
+ *                                     reference, "currently not working"): SGBM on a
+ *                                     census cost, on this engine's own contract
  *   mvsv_bm / mvsv_bm_device          Disparity::bm          src/disparity.cpp:18-22,
  *                                     decl inc/disparity.h:31
  *   mvsv_load_sgbm_yaml               Disparity::loadSGBMParameters
@@ -332,6 +336,54 @@ MVSV_API size_t mvsv_sgbm_workspace_bytes_cn(int n, int width, int height,
                                              const mvsv_sgbm_params* p, int channels);
 MVSV_API int mvsv_sgbm_plan_cn(mvsv_ctx* ctx, int n, int width, int height, const mvsv_sgbm_params* p,
                                int channels, int* plan);
+
+/* StereoSGBM on a census matching cost: Disparity::binary_sgbm (inc/disparity.h:30,
+ * src/disparity.cpp:12-15, commented out in the reference as "currently not working").
+ * The contract is this engine's own, not opencv_contrib's
+ * StereoBinarySGBM.
+ *
+ * Census transform of an 8-bit image I (height x width) with an odd
+ * census_width x census_height window, 3 <= census_width * census_height <= 65:
+ * the window offsets run dy = -ch/2 .. ch/2 (outer) and dx = -cw/2 .. cw/2 (inner),
+ * the centre is skipped and the others are numbered k = 0 .. cw*ch - 2 in that order;
+ * bit k of T(y, x) is 1 iff I(clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1)) < I(y, x).
+ * T is a uint64 whose bits above cw*ch - 1 are 0.
+ *
+ * Pixel cost: popcount(T_left(y, x) ^ T_right(y, x - d)).  Everything after the
+ * pixel cost is mvsv_sgbm's for the same parameters and mode (box sum, + P2, the
+ * OpenCV 3.4 cost rows in modes 0 and 1, paths, WTA, uniqueness, sub-pixel fit, LR
+ * check, medianBlur(3), speckle filter).  pre_filter_cap has no effect.
+ *
+ * mvsv_sgbm_census_validate: mvsv_sgbm_validate's rules, the window rule above, and
+ * P2 + blockSize^2 * (cw*ch - 1) <= 32767 with the effective values (no cost leaves
+ * int16).  Grey pairs only.  The calls return MVSV_E_INVALID_ARG with a message that
+ * names the broken rule.  Other arguments as mvsv_sgbm / mvsv_sgbm_device. */
+MVSV_API int mvsv_sgbm_census_validate(const mvsv_sgbm_params* p, int W, int H, int census_width,
+                                       int census_height);
+MVSV_API int mvsv_sgbm_census(mvsv_ctx* ctx, const uint8_t* left, size_t left_stride,
+                              const uint8_t* right, size_t right_stride, int width, int height,
+                              const mvsv_sgbm_params* p, int16_t* out, size_t out_stride,
+                              int census_width, int census_height);
+MVSV_API int mvsv_sgbm_census_device(mvsv_ctx* ctx, int n, const uint8_t* left, size_t left_stride,
+                                     size_t left_frame_stride, const uint8_t* right,
+                                     size_t right_stride, size_t right_frame_stride, int width,
+                                     int height, const mvsv_sgbm_params* p, int16_t* out,
+                                     size_t out_stride, size_t out_frame_stride, int census_width,
+                                     int census_height);
+/* mvsv_sgbm_workspace_bytes / mvsv_sgbm_plan of a census call: it always takes the
+ * LDS-ring cost kernel and never the bit-sliced or residual pipelines. */
+MVSV_API size_t mvsv_sgbm_workspace_bytes_census(int n, int width, int height, const mvsv_sgbm_params* p,
+                                                 int census_width, int census_height);
+MVSV_API int mvsv_sgbm_plan_census(mvsv_ctx* ctx, int n, int width, int height, const mvsv_sgbm_params* p,
+                                   int census_width, int census_height, int* plan);
+/* The census transform alone.  stride / frame_stride in bytes, out_stride /
+ * out_frame_stride in uint64 elements (>= width); only the width descriptors of a
+ * row are written. */
+MVSV_API int mvsv_census(mvsv_ctx* ctx, const uint8_t* img, size_t stride, int width, int height,
+                         int census_width, int census_height, uint64_t* out, size_t out_stride);
+MVSV_API int mvsv_census_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t stride, size_t frame_stride,
+                                int width, int height, int census_width, int census_height, uint64_t* out,
+                                size_t out_stride, size_t out_frame_stride);
 
 /* MeanDisparityDetection post-pass on device: 9x9 tile means of an int16 map
  * (tile = (W/9)x(H/9), remainder ignored; mean over values > 1 with integer
@@ -809,6 +861,14 @@ MVSV_API int mvsv_stream_push_bgr(mvsv_stream* s, const uint8_t* left, size_t le
  * together (a frame of the other kind sends the pending ones off first, as a parameter
  * change does).  mvsv_stream_disable_bgr and a new mvsv_stream_enable_bgr switch it off. */
 MVSV_API int mvsv_stream_set_bgr_match(mvsv_stream* s, int on);
+/* mvsv_stream_set_census: every frame pushed from now on is matched on the census cost
+ * (mvsv_sgbm_census_device) with this window; 0, 0 switches back to the Birchfield-Tomasi
+ * cost.  Valid while no frame is pending, with the SGBM matcher and without colour
+ * matching (MVSV_E_INVALID_ARG otherwise, also for a window or parameters that
+ * mvsv_sgbm_census_validate refuses); while it is on, mvsv_stream_set_bgr_match(1) and
+ * a switch to StereoBM are refused, and mvsv_stream_set_params validates against the
+ * census rules.  Every stage computed from the map follows the census map. */
+MVSV_API int mvsv_stream_set_census(mvsv_stream* s, int census_width, int census_height);
 
 /* ---- device ends of a stream: frames from device memory, maps handed back there ------
  * mvsv_stream_push_device / _push_raw_device / _push_bgr_device: n >= 1 frames (strides in

@@ -175,6 +175,19 @@ public:
                         reinterpret_cast<int16_t*>(disparity.data), disparity.step / 2),
               c);
     }
+    // CV_8UC1 pairs on the census cost (mvsv_sgbm_census): the Hamming distance of the
+    // census descriptors over a census_width x census_height window in place of the BT
+    // cost; everything after the pixel cost is compute()'s
+    void computeCensus(const Mat& left, const Mat& right, Mat& disparity, int census_width = 9, int census_height = 7)
+    {
+        check_pair(left, right);
+        disparity.create(left.rows, left.cols, MAT_16SC1);
+        mvsv_ctx* c = thread_context();
+        check(mvsv_sgbm_census(c, left.data, left.step, right.data, right.step, left.cols, left.rows, &p,
+                               reinterpret_cast<int16_t*>(disparity.data), disparity.step / 2, census_width,
+                               census_height),
+              c);
+    }
     void setMinDisparity(int v) { p.min_disparity = v; }
     int getMinDisparity() const { return p.min_disparity; }
     void setNumDisparities(int v) { p.num_disparities = v; }
@@ -200,6 +213,42 @@ public:
     const mvsv_sgbm_params& params() const { return p; }
     mvsv_sgbm_params p{};
 };
+
+// The matcher of Disparity::binary_sgbm (the reference names cv::stereo::StereoBinarySGBM,
+// inc/disparity.h:30): a StereoSGBM that carries its census window.  The matching is
+// this engine's own census contract (include/mvsv.h), not opencv_contrib's.
+namespace stereo {
+class StereoBinarySGBM : public StereoSGBM {
+public:
+    static Ptr<StereoBinarySGBM> create(int minDisparity = 0, int numDisparities = 16, int blockSize = 3, int P1 = 0,
+                                        int P2 = 0, int disp12MaxDiff = 0, int preFilterCap = 0,
+                                        int uniquenessRatio = 0, int speckleWindowSize = 0, int speckleRange = 0,
+                                        int mode = MODE_SGBM)
+    {
+        auto m = std::make_shared<StereoBinarySGBM>();
+        mvsv_sgbm_params_create(&m->p, minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap,
+                                uniquenessRatio, speckleWindowSize, speckleRange, mode);
+        return m;
+    }
+    void setCensusWindow(int width, int height)
+    {
+        census_width = width;
+        census_height = height;
+    }
+    int getCensusWidth() const { return census_width; }
+    int getCensusHeight() const { return census_height; }
+    // whether compute() accepts the parameters and the window for a width x height pair
+    bool validate(int width, int height) const
+    {
+        return mvsv_sgbm_census_validate(&p, width, height, census_width, census_height) == MVSV_OK;
+    }
+    void compute(const Mat& left, const Mat& right, Mat& disparity)
+    {
+        computeCensus(left, right, disparity, census_width, census_height);
+    }
+    int census_width = 9, census_height = 7;
+};
+}  // namespace stereo
 
 class StereoBM {
 public:
@@ -273,6 +322,22 @@ struct sgbmParameters {
 // src/disparity.cpp:6-10 — output (re)allocated CV_16S, disparity * 16
 template <class Pair>
 inline void sgbm(Pair const& inputImages, mvsv::Mat& output, mvsv::Ptr<mvsv::StereoSGBM> dispCompute)
+{
+    dispCompute->compute(inputImages.mLeft, inputImages.mRight, output);
+}
+
+// inc/disparity.h:30, src/disparity.cpp:12-15 (commented out there: "currently not working") --
+// SGBM on a census cost.  With a StereoSGBM the window is an argument; a
+// stereo::StereoBinarySGBM, the reference's signature, carries its own.
+template <class Pair>
+inline void binary_sgbm(Pair const& inputImages, mvsv::Mat& output, mvsv::Ptr<mvsv::StereoSGBM> dispCompute,
+                        int census_width = 9, int census_height = 7)
+{
+    dispCompute->computeCensus(inputImages.mLeft, inputImages.mRight, output, census_width, census_height);
+}
+template <class Pair>
+inline void binary_sgbm(Pair const& inputImages, mvsv::Mat& output,
+                        mvsv::Ptr<mvsv::stereo::StereoBinarySGBM> dispCompute)
 {
     dispCompute->compute(inputImages.mLeft, inputImages.mRight, output);
 }

@@ -11,7 +11,7 @@ from ._lib import (GRAY_Q14, GRAY_Q15, MATCHER_BM, MATCHER_SGBM, MODE_HH, MODE_H
                    OPT_STRIP_SPIN_LIMIT, OPT_STRIP_WAVES,
                    PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, VARIANT_FIRSTCOL_FIX,
                    VARIANT_WTA_MIN_D, MvsvError, set_option, synchronize)
-from .disparity import (SAMPLE_HIT_DTYPE, Disparity, StereoBM, StereoSGBM, Stereopair, filter_speckles,
+from .disparity import (SAMPLE_HIT_DTYPE, Disparity, StereoBM, StereoSGBM, Stereopair, census_transform, filter_speckles,
                         mean_disparity_grid, median_blur3, samplepoint_detect, samplepoint_layout,
                         samplepoint_values, sgbmParameters, synth_pair, tm, tm_validate)
 from .detection import (DisparityStream, MeanDisparityDetection, Samplepoint, SamplepointDetection, Subimage,
@@ -37,6 +37,6 @@ __all__ = [
     "sharpness", "undistort_maps", "remap_fixed", "undistort_pair",
     "detection_view", "View", "VIEW_SUBIMAGE_GRID", "VIEW_OBSTACLE_GRID", "VIEW_FOUND_TILES", "VIEW_FOUND_POINTS",
     "prepare_gray", "prepare_size", "GRAY_Q14", "GRAY_Q15", "MATCHER_SGBM", "MATCHER_BM",
-    "tm", "tm_validate", "MVSV_HOST_MAP", "MVSV_HOST_RECTIFIED", "MVSV_HOST_DISPLAY", "MVSV_HOST_VIEW", "MVSV_HOST_ALL",
+    "tm", "tm_validate", "census_transform", "MVSV_HOST_MAP", "MVSV_HOST_RECTIFIED", "MVSV_HOST_DISPLAY", "MVSV_HOST_VIEW", "MVSV_HOST_ALL",
 ]
 __version__ = "1.0.0"

@@ -155,6 +155,14 @@ def _declare(lib, strict=True):
         "mvsv_sgbm_bgr_device": ([P, I, P, Z, Z, P, Z, Z, I, I, P, P, Z, Z], I),
         "mvsv_sgbm_workspace_bytes_cn": ([I, I, I, P, I], Z),
         "mvsv_sgbm_plan_cn": ([P, I, I, I, P, I, P], I),
+        "mvsv_sgbm_census_validate": ([P, I, I, I, I], I),
+        "mvsv_sgbm_census": ([P, P, Z, P, Z, I, I, P, P, Z, I, I], I),
+        "mvsv_sgbm_census_device": ([P, I, P, Z, Z, P, Z, Z, I, I, P, P, Z, Z, I, I], I),
+        "mvsv_sgbm_workspace_bytes_census": ([I, I, I, P, I, I], Z),
+        "mvsv_sgbm_plan_census": ([P, I, I, I, P, I, I, P], I),
+        "mvsv_census": ([P, P, Z, I, I, I, I, P, Z], I),
+        "mvsv_census_device": ([P, I, P, Z, Z, I, I, I, I, P, Z, Z], I),
+        "mvsv_stream_set_census": ([P, I, I], I),
         "mvsv_mean_disparity_grid_device": ([P, I, P, Z, Z, I, I, P], I),
         "mvsv_median_blur3_device": ([P, I, P, Z, Z, P, Z, Z, I, I], I),
         "mvsv_filter_speckles_device": ([P, I, P, Z, Z, I, I, I, I, I], I),
@@ -403,12 +411,16 @@ def profile_read(ctx: Context) -> dict:
 PLAN_BITSLICE, PLAN_SIDE, PLAN_STRIPS, PLAN_RESIDUAL = 1, 2, 4, 8
 
 
-def sgbm_plan(ctx, n, width, height, params, channels=1) -> int:
+def sgbm_plan(ctx, n, width, height, params, channels=1, census=None) -> int:
     """MVSV_PLAN_* bits of the pipeline ``ctx`` runs for an SGBM call of this
     shape (mvsv_sgbm_plan): bit-sliced, side by side / strips, residual plane.
-    channels=3: a colour (BGR) launch (mvsv_sgbm_plan_cn)."""
+    channels=3: a colour (BGR) launch (mvsv_sgbm_plan_cn); census=(width, height):
+    a launch on the census cost with that window (mvsv_sgbm_plan_census)."""
     out = ctypes.c_int(0)
-    if channels == 1:
+    if census is not None:
+        check(lib().mvsv_sgbm_plan_census(ctx.handle, n, width, height, ctypes.byref(params), int(census[0]),
+                                          int(census[1]), ctypes.byref(out)), ctx.handle)
+    elif channels == 1:
         check(lib().mvsv_sgbm_plan(ctx.handle, n, width, height, ctypes.byref(params), ctypes.byref(out)), ctx.handle)
     else:
         check(lib().mvsv_sgbm_plan_cn(ctx.handle, n, width, height, ctypes.byref(params), int(channels),

@@ -209,14 +209,58 @@ __device__ __forceinline__ uint32_t bt_pair(uint32_t u, uint32_t u0, uint32_t u1
     return pk_min_u16(c0, c1);
 }
 
+// Pixel cost of one left column (l0: Sobel channel, l1: raw channel) against the
+// right columns of a disparity pair, rr = (d: .x .y, d + 1: .z .w), the pair's
+// costs in the u16 halves: BT on the clipped Sobel channel plus a quarter of BT
+// on the raw channel
+__device__ __forceinline__ uint32_t bt_pix_pair(uint32_t l0, uint32_t l1, uint4 rr)
+{
+    uint32_t acc;
+    {
+        const uint32_t a = rr.x, b = rr.z;  // channel 0 of d, d+1
+        uint32_t U = __builtin_amdgcn_perm(l0, l0, 0x0c040c00u);
+        uint32_t U0 = __builtin_amdgcn_perm(l0, l0, 0x0c050c01u);
+        uint32_t U1 = __builtin_amdgcn_perm(l0, l0, 0x0c060c02u);
+        uint32_t V = __builtin_amdgcn_perm(b, a, 0x0c040c00u);
+        uint32_t V0 = __builtin_amdgcn_perm(b, a, 0x0c050c01u);
+        uint32_t V1 = __builtin_amdgcn_perm(b, a, 0x0c060c02u);
+        acc = bt_pair(U, U0, U1, V, V0, V1);
+    }
+    {
+        const uint32_t a = rr.y, b = rr.w;  // channel 1 (raw) of d, d+1
+        uint32_t U = __builtin_amdgcn_perm(l1, l1, 0x0c040c00u);
+        uint32_t U0 = __builtin_amdgcn_perm(l1, l1, 0x0c050c01u);
+        uint32_t U1 = __builtin_amdgcn_perm(l1, l1, 0x0c060c02u);
+        uint32_t V = __builtin_amdgcn_perm(b, a, 0x0c040c00u);
+        uint32_t V0 = __builtin_amdgcn_perm(b, a, 0x0c050c01u);
+        uint32_t V1 = __builtin_amdgcn_perm(b, a, 0x0c060c02u);
+        uint32_t cr = bt_pair(U, U0, U1, V, V0, V1);
+        acc = pk_add_u16(acc, (cr >> 2) & 0x3fff3fffu);
+    }
+    return acc;
+}
+// ... and on the census cost, where (l0, l1) and the halves of rr are the words
+// of the u64 descriptors: the Hamming distances, each <= 64
+__device__ __forceinline__ uint32_t census_pix_pair(uint32_t l0, uint32_t l1, uint4 rr)
+{
+    const uint32_t c0 = (uint32_t)__builtin_popcount(l0 ^ rr.x) + (uint32_t)__builtin_popcount(l1 ^ rr.y);
+    const uint32_t c1 = (uint32_t)__builtin_popcount(l0 ^ rr.z) + (uint32_t)__builtin_popcount(l1 ^ rr.w);
+    return c0 | (c1 << 16);
+}
+
 constexpr int kStageRegs = 3;  // staging loads per thread per row (nL + nR + 1 <= 768)
 
-template <int CN>
-__global__ __launch_bounds__(256) void sgbm_cost_kernel(const uint64_t* __restrict__ pre, int W,
-                                                        int H, SgbmEff e, int TY,
-                                                        int16_t* __restrict__ C)
+// The tile sweep of the LDS-ring cost kernels.  CENSUS: the planes hold census
+// descriptors (one u64 per pixel, mvsv_census.hip) and the pixel cost of a
+// disparity pair is popcount(l ^ r_d) | popcount(l ^ r_d+1) << 16 -- four
+// v_xor_b32, four v_bcnt_u32_b32 (two chained through the add operand) and one
+// v_lshl_or_b32 -- in place of the BT cost; staging, hsum, the vertical ring
+// and the emission are the same code.
+template <int CN, bool CENSUS>
+__device__ __forceinline__ void cost_ring_tile(unsigned char* smem, const uint64_t* __restrict__ pre, int W,
+                                               int H, const SgbmEff& e, int TY, int16_t* __restrict__ C)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(!CENSUS || CN == 1, "census descriptors: grey pairs");
     const int D = e.D, W1 = e.W1, SW2 = e.SW2, SH2 = e.SH2;
     const CostLayout lay = cost_layout(D, SW2, SH2, TY);
     const int PP = lay.PP, CL = lay.CL, TX = lay.TX, NX = lay.NX, NR = lay.NR;
@@ -299,28 +343,7 @@ __global__ __launch_bounds__(256) void sgbm_cost_kernel(const uint64_t* __restri
                     const int j0 = (xchi - xc) + 2 * p;
                     const uint64_t* src = (j0 & 1) ? (rb + (j0 - 1)) : (ra + j0);
                     const uint4 rr = *(const uint4*)src;  // cols j0, j0+1 (both channels)
-                    uint32_t acc;
-                    {
-                        const uint32_t a = rr.x, b = rr.z;  // channel 0 of d, d+1
-                        uint32_t U = __builtin_amdgcn_perm(l0, l0, 0x0c040c00u);
-                        uint32_t U0 = __builtin_amdgcn_perm(l0, l0, 0x0c050c01u);
-                        uint32_t U1 = __builtin_amdgcn_perm(l0, l0, 0x0c060c02u);
-                        uint32_t V = __builtin_amdgcn_perm(b, a, 0x0c040c00u);
-                        uint32_t V0 = __builtin_amdgcn_perm(b, a, 0x0c050c01u);
-                        uint32_t V1 = __builtin_amdgcn_perm(b, a, 0x0c060c02u);
-                        acc = bt_pair(U, U0, U1, V, V0, V1);
-                    }
-                    {
-                        const uint32_t a = rr.y, b = rr.w;  // channel 1 (raw) of d, d+1
-                        uint32_t U = __builtin_amdgcn_perm(l1, l1, 0x0c040c00u);
-                        uint32_t U0 = __builtin_amdgcn_perm(l1, l1, 0x0c050c01u);
-                        uint32_t U1 = __builtin_amdgcn_perm(l1, l1, 0x0c060c02u);
-                        uint32_t V = __builtin_amdgcn_perm(b, a, 0x0c040c00u);
-                        uint32_t V0 = __builtin_amdgcn_perm(b, a, 0x0c050c01u);
-                        uint32_t V1 = __builtin_amdgcn_perm(b, a, 0x0c060c02u);
-                        uint32_t cr = bt_pair(U, U0, U1, V, V0, V1);
-                        acc = pk_add_u16(acc, (cr >> 2) & 0x3fff3fffu);
-                    }
+                    uint32_t acc = CENSUS ? census_pix_pair(l0, l1, rr) : bt_pix_pair(l0, l1, rr);
                     // (the word is this thread's own for every colour channel of the row)
                     if (c > 0) acc = pk_add_u16(acc, pixrow[xv * PP + p]);
                     pixrow[xv * PP + p] = acc;
@@ -352,6 +375,24 @@ __global__ __launch_bounds__(256) void sgbm_cost_kernel(const uint64_t* __restri
             }
         }
     }
+}
+
+template <int CN>
+__global__ __launch_bounds__(256) void sgbm_cost_kernel(const uint64_t* __restrict__ pre, int W,
+                                                        int H, SgbmEff e, int TY,
+                                                        int16_t* __restrict__ C)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    cost_ring_tile<CN, false>(smem, pre, W, H, e, TY, C);
+}
+
+// the census form: `pre` holds the descriptor planes [frame][2][H][W]
+__global__ __launch_bounds__(256) void sgbm_cost_census_kernel(const uint64_t* __restrict__ pre, int W,
+                                                               int H, SgbmEff e, int TY,
+                                                               int16_t* __restrict__ C)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    cost_ring_tile<1, true>(smem, pre, W, H, e, TY, C);
 }
 
 // ---------------------------------------------------------------------------
@@ -931,7 +972,7 @@ int launch_cost(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int W, int H, const 
     if (lay.bytes > 160 * 1024)
         return set_error(ctx, MVSV_E_INVALID_ARG, "blockSize too large for the GPU cost kernel");
     dim3 cgrid((e.W1 + lay.TX - 1) / lay.TX, (H + TY - 1) / TY, n);
-    auto kern = e.cn == 3 ? sgbm_cost_kernel<3> : sgbm_cost_kernel<1>;
+    auto kern = sgbm_census(e) ? sgbm_cost_census_kernel : e.cn == 3 ? sgbm_cost_kernel<3> : sgbm_cost_kernel<1>;
     if (lay.bytes > 65536 &&
         (rc = check_hip(ctx, hipFuncSetAttribute((const void*)kern,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize,

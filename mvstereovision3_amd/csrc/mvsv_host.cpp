@@ -165,8 +165,27 @@ int resolve_sgbm(const mvsv_sgbm_params* p, int W, int H, SgbmEff* e, std::strin
     e->speckle_window = p->speckle_window_size;
     e->speckle_diff = kDispScale * p->speckle_range;
     e->cn = 1;
+    e->cw = e->ch = 0;
     if (e->W1 > 0 && e->W1 <= e->SW2) {
         *why = "image narrower than the SGBM block half-width (OpenCV reads uninitialised memory)";
+        return MVSV_E_INVALID_ARG;
+    }
+    return MVSV_OK;
+}
+
+// A census call: mvsv_sgbm_validate's rules, the window rule, and no cost beyond int16.
+int resolve_sgbm_census(const mvsv_sgbm_params* p, int W, int H, int cw, int ch, SgbmEff* e, std::string* why)
+{
+    if (int rc = resolve_sgbm(p, W, H, e, why)) return rc;
+    if (const char* bad = census_window_check(cw, ch)) {
+        *why = bad;
+        return MVSV_E_INVALID_ARG;
+    }
+    e->cw = cw;
+    e->ch = ch;
+    const long bs = 2L * e->SW2 + 1;
+    if ((long)e->P2 + bs * bs * sgbm_max_pixel_cost(*e) > 32767) {
+        *why = "census cost: P2 + blockSize^2 * (width * height - 1) must be <= 32767 (no cost may leave int16)";
         return MVSV_E_INVALID_ARG;
     }
     return MVSV_OK;
@@ -323,6 +342,13 @@ int mvsv_sgbm_validate(const mvsv_sgbm_params* p, int W, int H)
     SgbmEff e;
     std::string why;
     return resolve_sgbm(p, W, H, &e, &why);
+}
+
+int mvsv_sgbm_census_validate(const mvsv_sgbm_params* p, int W, int H, int cw, int ch)
+{
+    SgbmEff e;
+    std::string why;
+    return resolve_sgbm_census(p, W, H, cw, ch, &e, &why);
 }
 
 int mvsv_bm_validate(const mvsv_bm_params* p, int W, int H)
@@ -568,17 +594,42 @@ int mvsv_synchronize(mvsv_ctx* ctx)
     return rc ? rc : check_report(ctx);
 }
 
+// the bytes of the call whose effective parameters are e
+static size_t workspace_bytes(const SgbmEff& e, int n, int W, int H)
+{
+    // what a context with default kernel options on a 256-CU device allocates:
+    // the plan's buffers, and the speckle filter's
+    const SgbmPlan plan = sgbm_make_plan(KernelOptions(), 256, e, n, W, H);
+    if (plan.empty) return 0;  // an empty column range only fills the map
+    return plan.total_bytes() + (e.speckle_window > 0 ? speckle_bytes(n, W, H).total() : 0);
+}
+
+size_t mvsv_sgbm_workspace_bytes_census(int n, int W, int H, const mvsv_sgbm_params* p, int cw, int ch)
+{
+    SgbmEff e;
+    std::string why;
+    if (n <= 0 || resolve_sgbm_census(p, W, H, cw, ch, &e, &why) != MVSV_OK) return 0;
+    return workspace_bytes(e, n, W, H);
+}
+
+int mvsv_sgbm_plan_census(mvsv_ctx* ctx, int n, int W, int H, const mvsv_sgbm_params* p, int cw, int ch, int* plan)
+{
+    if (!ctx || !plan || n <= 0) return MVSV_E_INVALID_ARG;
+    SgbmEff e;
+    std::string why;
+    const int rc = resolve_sgbm_census(p, W, H, cw, ch, &e, &why);
+    if (rc) return set_error(ctx, rc, why);
+    *plan = sgbm_make_plan(ctx, e, n, W, H).bits();
+    return MVSV_OK;
+}
+
 size_t mvsv_sgbm_workspace_bytes_cn(int n, int W, int H, const mvsv_sgbm_params* p, int cn)
 {
     SgbmEff e;
     std::string why;
     if (n <= 0 || (cn != 1 && cn != 3) || resolve_sgbm(p, W, H, &e, &why) != MVSV_OK) return 0;
     e.cn = cn;
-    // what a context with default kernel options on a 256-CU device allocates:
-    // the plan's buffers, and the speckle filter's
-    const SgbmPlan plan = sgbm_make_plan(KernelOptions(), 256, e, n, W, H);
-    if (plan.empty) return 0;  // an empty column range only fills the map
-    return plan.total_bytes() + (e.speckle_window > 0 ? speckle_bytes(n, W, H).total() : 0);
+    return workspace_bytes(e, n, W, H);
 }
 
 size_t mvsv_sgbm_workspace_bytes(int n, int W, int H, const mvsv_sgbm_params* p)
@@ -606,10 +657,11 @@ int mvsv_sgbm_plan(mvsv_ctx* ctx, int n, int W, int H, const mvsv_sgbm_params* p
 
 }  // extern "C"
 
-// mvsv_sgbm_device (cn 1) / mvsv_sgbm_bgr_device (cn 3: W in pixels, rows of 3 W bytes)
+// mvsv_sgbm_device (cn 1) / mvsv_sgbm_bgr_device (cn 3: W in pixels, rows of 3 W bytes) /
+// mvsv_sgbm_census_device (cn 1, census: the cw x ch window)
 static int sgbm_device_call(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
                             size_t rs, size_t rfs, int W, int H, const mvsv_sgbm_params* p, int16_t* out,
-                            size_t os, size_t ofs, int cn)
+                            size_t os, size_t ofs, int cn, bool census = false, int cw = 0, int ch = 0)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     if (n <= 0 || !L || !R || !out) return set_error(ctx, MVSV_E_INVALID_ARG, "null buffer or n <= 0");
@@ -617,7 +669,7 @@ static int sgbm_device_call(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, s
         return set_error(ctx, MVSV_E_INVALID_ARG, "stride smaller than width");
     SgbmEff e;
     std::string why;
-    int rc = resolve_sgbm(p, W, H, &e, &why);
+    int rc = census ? resolve_sgbm_census(p, W, H, cw, ch, &e, &why) : resolve_sgbm(p, W, H, &e, &why);
     if (rc) return set_error(ctx, rc, why);
     e.cn = cn;
     // an earlier launch that has finished by now gave up a strip wait: its
@@ -662,6 +714,23 @@ int mvsv_sgbm_bgr_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size
                          const mvsv_sgbm_params* p, int16_t* out, size_t os, size_t ofs)
 {
     return sgbm_device_call(ctx, n, L, ls, lfs, R, rs, rfs, W, H, p, out, os, ofs, 3);
+}
+
+int mvsv_sgbm_census_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs,
+                            const uint8_t* R, size_t rs, size_t rfs, int W, int H,
+                            const mvsv_sgbm_params* p, int16_t* out, size_t os, size_t ofs, int cw, int ch)
+{
+    return sgbm_device_call(ctx, n, L, ls, lfs, R, rs, rfs, W, H, p, out, os, ofs, 1, true, cw, ch);
+}
+
+int mvsv_census_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t st, size_t fs, int W, int H, int cw, int ch,
+                       uint64_t* out, size_t os, size_t ofs)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (n <= 0 || !img || !out || W <= 0 || H <= 0) return set_error(ctx, MVSV_E_INVALID_ARG, "null buffer, empty image or n <= 0");
+    if (st < (size_t)W || os < (size_t)W) return set_error(ctx, MVSV_E_INVALID_ARG, "stride smaller than width");
+    DeviceGuard dev_guard(ctx->device);
+    return mark_last_use(ctx, census_device(ctx, n, 1, img, st, fs, img, st, fs, W, H, cw, ch, out, os, 0, ofs));
 }
 
 int mvsv_bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs,
@@ -933,9 +1002,11 @@ int mvsv_view(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, const
     });
 }
 
-// One host pair through either matcher; cn: bytes per input pixel (3: mvsv_sgbm_bgr)
+// One host pair through either matcher; cn: bytes per input pixel (3: mvsv_sgbm_bgr);
+// census: mvsv_sgbm_census with the cw x ch window
 static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs,
-                     int W, int H, int16_t* out, size_t os, bool sgbm, const void* params, int cn = 1)
+                     int W, int H, int16_t* out, size_t os, bool sgbm, const void* params, int cn = 1,
+                     bool census = false, int cw = 0, int ch = 0)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     if (!L || !R || !out || W <= 0 || H <= 0)
@@ -946,8 +1017,9 @@ static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* 
     SgbmEff se;
     BmEff be;
     std::string why;
-    rc = sgbm ? resolve_sgbm((const mvsv_sgbm_params*)params, W, H, &se, &why)
-              : resolve_bm((const mvsv_bm_params*)params, W, H, &be, &why);
+    rc = census ? resolve_sgbm_census((const mvsv_sgbm_params*)params, W, H, cw, ch, &se, &why)
+         : sgbm ? resolve_sgbm((const mvsv_sgbm_params*)params, W, H, &se, &why)
+                : resolve_bm((const mvsv_bm_params*)params, W, H, &be, &why);
     if (rc) return set_error(ctx, rc, why);
     if (sgbm) se.cn = cn;
     if (sgbm && (rc = check_report(ctx))) return rc;  // an earlier device call's give-up
@@ -980,6 +1052,33 @@ int mvsv_sgbm_bgr(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, 
                   int H, const mvsv_sgbm_params* p, int16_t* out, size_t os)
 {
     return host_call(ctx, L, ls, R, rs, W, H, out, os, true, p, 3);
+}
+
+int mvsv_sgbm_census(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs, int W,
+                     int H, const mvsv_sgbm_params* p, int16_t* out, size_t os, int cw, int ch)
+{
+    return host_call(ctx, L, ls, R, rs, W, H, out, os, true, p, 1, true, cw, ch);
+}
+
+int mvsv_census(mvsv_ctx* ctx, const uint8_t* img, size_t st, int W, int H, int cw, int ch, uint64_t* out, size_t os)
+{
+    if (!ctx) return MVSV_E_INVALID_ARG;
+    if (!img || !out || W <= 0 || H <= 0) return set_error(ctx, MVSV_E_INVALID_ARG, "null buffer or empty image");
+    if (st < (size_t)W || os < (size_t)W) return set_error(ctx, MVSV_E_INVALID_ARG, "stride smaller than width");
+    if (const char* why = census_window_check(cw, ch)) return set_error(ctx, MVSV_E_INVALID_ARG, why);
+    DeviceGuard dev_guard(ctx->device);
+    const ImageStage s(H, W, kRowTight, (size_t)W * 8, H);
+    return staged_call(ctx, s, "census staging", [&](Staging& sg) -> int {
+        int rc;
+        uint8_t* in = sg.at<uint8_t>(s.in);
+        uint64_t* o = sg.at<uint64_t>(s.out);
+        if ((rc = sg.up(in, s.in.pitch, img, st, (size_t)W, H, "H2D image")) ||
+            (rc = census_device(ctx, 1, 1, in, s.in.pitch, s.in.bytes, in, s.in.pitch, s.in.bytes, W, H, cw, ch, o,
+                                (size_t)W, 0, (size_t)W * H)) ||
+            (rc = sg.down(out, os * 8, o, s.out.pitch, (size_t)W * 8, H, "D2H descriptors")))
+            return rc;
+        return sg.finish();
+    });
 }
 
 int mvsv_bm(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs, int W,

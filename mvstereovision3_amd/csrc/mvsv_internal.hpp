@@ -200,6 +200,17 @@ int launch_prefilter(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t l
 int launch_cost(mvsv_ctx* ctx, const SgbmPlan& plan, int n, int W, int H, const SgbmEff& e, const uint64_t* pre,
                 int16_t* Cv, uint8_t* Rv, uint16_t* Mv, uint32_t* Bv);
 int launch_cost_fixup(mvsv_ctx* ctx, int n, int H, const SgbmEff& e, int16_t* Cv, uint8_t* Rv, uint16_t* Mv);
+// The census transform (mvsv_census.hip): the window rule as a message (nullptr: the
+// window is valid), and one launch over nimg views (1: L alone, 2: L and R) of n
+// frames.  Input strides in bytes; descriptor (f, img, y, x) goes to
+// out[f * ofs + img * ois + y * ors + x] (strides in u64 elements).
+const char* census_window_check(int cw, int ch);
+int census_device(mvsv_ctx* ctx, int n, int nimg, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
+                  size_t rs, size_t rfs, int W, int H, int cw, int ch, uint64_t* out, size_t ors, size_t ois,
+                  size_t ofs);
+// resolve_sgbm plus the rules of a census call (include/mvsv.h mvsv_sgbm_census_validate);
+// e->cw, e->ch are set
+int resolve_sgbm_census(const mvsv_sgbm_params* p, int W, int H, int cw, int ch, SgbmEff* e, std::string* why);
 // Bit-sliced path aggregation + WTA, MODE_HH and MODE_SGBM (mvsv_bsgm.hip): where the
 // plan's family is kFamBitslice the cost kernel writes the C' planes Bv and bsgm_paths
 // computes raw disparities from them, on the plan's schedule, strip width and planes.

@@ -3,6 +3,7 @@
 // Replaces Disparity::sgbm (src/disparity.cpp:6-10) -> cv::StereoSGBM::compute.
 // Pipeline per batch of frames (all launches on the context stream):
 //   1. sgbm_prefilter_kernel   clipped x-Sobel + raw channel per row    (u8 planes)
+//      (a census call: census_kernel, mvsv_census.hip, and the census form of 2)
 //      (stages 1-3 live in mvsv_cost.hip)
 //   2. sgbm_cost_kernel        Birchfield-Tomasi pixel cost + bs x bs box
 //                              sum -> C[y][x][d] int16 (+P2 bias), LDS-staged
@@ -481,7 +482,15 @@ int sgbm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, c
     uint8_t* Rv = plan.residual ? (uint8_t*)ctx->cres.ptr : nullptr;
     uint16_t* Mv = plan.cres ? (uint16_t*)((uint8_t*)ctx->cres.ptr + plan.cres_min) : nullptr;
 
-    if ((rc = launch_prefilter(ctx, n, L, ls, lfs, R, rs, rfs, W, H, e.ftzero, e.cn, pre))) return rc;
+    if (sgbm_census(e)) {
+        // the descriptors of both views in place of the BT interval planes
+        if (e.cn != 1) return set_error(ctx, MVSV_E_INVALID_ARG, "census window: 3-channel pairs are not supported");
+        if ((rc = census_device(ctx, n, 2, L, ls, lfs, R, rs, rfs, W, H, e.cw, e.ch, pre, (size_t)W, (size_t)W * H,
+                                (size_t)2 * W * H)))
+            return rc;
+    } else if ((rc = launch_prefilter(ctx, n, L, ls, lfs, R, rs, rfs, W, H, e.ftzero, e.cn, pre))) {
+        return rc;
+    }
     if ((rc = launch_cost(ctx, plan, n, W, H, e, pre, Cv, Rv, Mv, Bv))) return rc;
     if (bits) {
         // bit-sliced layouts (MODE_SGBM: copied rows / column 0; MODE_HH: pinned

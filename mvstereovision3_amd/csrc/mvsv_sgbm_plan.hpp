@@ -41,7 +41,23 @@ struct SgbmEff {
     // volume (no 3.4 cost-row quirk).  0 for MODE_SGBM / MODE_HH; fullDP stays 0
     // (the WTA is fused with the R->L pass, so MODE_SGBM's tie rule applies).
     int hh4;
+    // census matching cost (mvsv_sgbm_census): the cw x ch window of the census
+    // transform, both odd, 3 <= cw * ch <= 65.  0, 0: the Birchfield-Tomasi cost.
+    // A pixel cost is then the Hamming distance of two (cw * ch - 1)-bit descriptors.
+    int cw, ch;
 };
+
+// the pair is matched on the census cost
+MVSV_HD inline bool sgbm_census(const SgbmEff& e) { return e.cw != 0 || e.ch != 0; }
+// a grey pair on the Birchfield-Tomasi cost: what the register-ring cost kernel,
+// the residual plane and the bit-sliced pipeline are written for
+MVSV_HD inline bool sgbm_bt_grey(const SgbmEff& e) { return e.cn == 1 && !sgbm_census(e); }
+// the largest pixel cost: every descriptor bit differs, or every channel's BT
+// cost is at its ceiling
+MVSV_HD inline int sgbm_max_pixel_cost(const SgbmEff& e)
+{
+    return sgbm_census(e) ? e.cw * e.ch - 1 : e.cn * (2 * e.ftzero + 63);
+}
 
 // The path directions of a mode, counted with R->L (which the final kernels
 // run): 5 (MODE_SGBM), 8 (MODE_HH), 4 (MODE_HH4).  The direction passes run
@@ -119,13 +135,13 @@ constexpr size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // ---------------------------------------------------------------------------
 // Predicates: one definition each
 // ---------------------------------------------------------------------------
-// Every cost C = P2 + (box sum of blockSize^2 BT costs, each <= cn * (2*ftzero + 63)),
+// Every cost C = P2 + (box sum of blockSize^2 pixel costs, each <= sgbm_max_pixel_cost),
 // every L <= C and delta = minLp + P2: when that bound stays <= 32767 nothing
 // wraps in int16 and the path kernels may use the NW recurrence (sgm_pair).
 inline bool sgbm_no_wrap(const SgbmEff& e)
 {
     const long bs = 2L * e.SW2 + 1;
-    return (long)e.P2 + bs * bs * e.cn * (2L * e.ftzero + 63) + e.P2 <= 32767;
+    return (long)e.P2 + bs * bs * sgbm_max_pixel_cost(e) + e.P2 <= 32767;
 }
 
 // u8 accumulator when the summed path deltas (each <= P2) fit a byte
@@ -159,12 +175,13 @@ inline Cost2Launch cost2_launch(const SgbmEff& e, int fixed_pp, int TY)
     c.fits = c.l.CL >= 1 && items <= kCost2Threads * 2 && c.lds <= 160 * 1024;
     return c;
 }
-// the register-ring cost kernel runs (grey pairs: colour pairs always take the
-// LDS-ring kernel, which sums the channels); it alone writes the residual
-// plane and the bit-sliced C' planes
+// the register-ring cost kernel runs (grey pairs on the BT cost: colour pairs
+// always take the LDS-ring kernel, which sums the channels, and so do census
+// launches, whose pixel phase only that kernel has); it alone writes the
+// residual plane and the bit-sliced C' planes
 inline bool cost2_runs(const KernelOptions& o, const SgbmEff& e)
 {
-    return e.cn == 1 && o.cost2 && cost2_launch(e, o.cost_fixed_pp, kCostTileHeights[0]).fits;
+    return sgbm_bt_grey(e) && o.cost2 && cost2_launch(e, o.cost_fixed_pp, kCostTileHeights[0]).fits;
 }
 
 // Bit-sliced path aggregation (mvsv_bsgm.hip): the parameters admit it
@@ -172,7 +189,7 @@ inline bool cost2_runs(const KernelOptions& o, const SgbmEff& e)
 // test, no int16 wrap) and int32 word offsets cover the C' planes
 inline bool bsgm_eligible(const KernelOptions& o, const SgbmEff& e, int n, int H)
 {
-    return e.cn == 1 && !e.hh4 && o.bitslice && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && sgbm_no_wrap(e) &&
+    return sgbm_bt_grey(e) && !e.hh4 && o.bitslice && e.D == 128 && e.P1 == 2 && e.P2 == 5 && e.uniq == 0 && sgbm_no_wrap(e) &&
            e.W1 > 0 && (size_t)n * H * bs::padq(e.W1) * 16 < ((size_t)1 << 31);
 }
 
@@ -191,7 +208,7 @@ inline bool wta_split(const KernelOptions& o, const SgbmEff& e) { return o.final
 // register-ring cost kernel only.
 inline bool use_residual(const KernelOptions& o, const SgbmEff& e, int sched)
 {
-    return e.cn == 1 && o.cost_res && (sched == 1 || sched == 2) && sgbm_no_wrap(e) && 3 * e.P2 <= 15 &&
+    return sgbm_bt_grey(e) && o.cost_res && (sched == 1 || sched == 2) && sgbm_no_wrap(e) && 3 * e.P2 <= 15 &&
            (e.D == 32 || e.D == 64 || e.D == 128);
 }
 
@@ -382,7 +399,7 @@ inline SgbmPlan sgbm_make_plan(const KernelOptions& o, int cus, const SgbmEff& e
     p.family = bits ? kFamBitslice : (e.D == 16 && p.sched == 2) ? kFamPacked8 : wide ? kFamPacked16 : kFamGeneric;
     p.residual = !bits && p.cost2 && use_residual(o, e, p.sched);
 
-    p.pre = (size_t)n * 2 * e.cn * frame * 8;  // BT interval planes of both views
+    p.pre = (size_t)n * 2 * e.cn * frame * 8;  // BT interval planes (census descriptors) of both views
     // (rows padded to a multiple of 4 pixels: the bit-sliced pipeline's layout)
     p.cost = (size_t)n * H * bs::padq(e.W1) * e.D * 2;
     p.raw = (size_t)n * frame * 2;

@@ -780,7 +780,9 @@ int mvsv_stream_set_params(mvsv_stream* st, const mvsv_sgbm_params* p)
     if (!st) return MVSV_E_INVALID_ARG;
     SgbmEff e;
     std::string why;
-    int rc = resolve_sgbm(p, st->W, st->H, &e, &why);
+    // (a census window set with mvsv_stream_set_census stays: the new parameters must satisfy its rules)
+    int rc = sgbm_census(st->eff) ? resolve_sgbm_census(p, st->W, st->H, st->eff.cw, st->eff.ch, &e, &why)
+                                  : resolve_sgbm(p, st->W, st->H, &e, &why);
     if (rc) return set_error(st->ctx, rc, why);
     DeviceGuard dev_guard(st->ctx->device);
     if ((rc = stream_launch(st))) return rc;  // pending frames keep the old parameters
@@ -799,6 +801,8 @@ int mvsv_stream_set_bm_params(mvsv_stream* st, const mvsv_bm_params* p)
     if (rc) return set_error(st->ctx, rc, why);
     if (st->bgr.match)
         return set_error(st->ctx, MVSV_E_INVALID_ARG, "colour matching is on: StereoBM takes grey pairs only");
+    if (st->matcher == MVSV_MATCHER_SGBM && sgbm_census(st->eff))
+        return set_error(st->ctx, MVSV_E_INVALID_ARG, "the census cost is on: it is for the SGBM matcher only");
     DeviceGuard dev_guard(st->ctx->device);
     if ((rc = stream_launch(st))) return rc;  // pending frames keep their matcher and parameters
     st->bm_params = *p;
@@ -984,6 +988,8 @@ int mvsv_stream_set_bgr_match(mvsv_stream* st, int on)
     if (int rc = idle_check(st, "colour matching changes")) return rc;
     if (on && st->matcher != MVSV_MATCHER_SGBM)
         return set_error(ctx, MVSV_E_INVALID_ARG, "colour matching is for the SGBM matcher: StereoBM takes grey pairs only");
+    if (on && sgbm_census(st->eff))
+        return set_error(ctx, MVSV_E_INVALID_ARG, "the census cost is on: it takes grey pairs only");
     DeviceGuard dev_guard(ctx->device);
     Bgr& b = st->bgr;
     if (on && b.halve && !b.half &&
@@ -992,6 +998,27 @@ int mvsv_stream_set_bgr_match(mvsv_stream* st, int on)
         return set_error(ctx, MVSV_E_OOM, "colour pair allocation failed");
     }
     b.match = on != 0;
+    return MVSV_OK;
+}
+
+int mvsv_stream_set_census(mvsv_stream* st, int cw, int ch)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (int rc = idle_check(st, "the census cost changes")) return rc;
+    if (st->matcher != MVSV_MATCHER_SGBM)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "the census cost is for the SGBM matcher only");
+    SgbmEff e;
+    std::string why;
+    if (cw == 0 && ch == 0) {  // back to the Birchfield-Tomasi cost
+        if (int rc = resolve_sgbm(&st->params, st->W, st->H, &e, &why)) return set_error(ctx, rc, why);
+        st->eff = e;
+        return MVSV_OK;
+    }
+    if (st->bgr.match)
+        return set_error(ctx, MVSV_E_INVALID_ARG, "colour matching is on: the census cost takes grey pairs only");
+    if (int rc = resolve_sgbm_census(&st->params, st->W, st->H, cw, ch, &e, &why)) return set_error(ctx, rc, why);
+    st->eff = e;
     return MVSV_OK;
 }
 

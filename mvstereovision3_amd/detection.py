@@ -560,6 +560,15 @@ class DisparityStream:
         working and never share a launch with colour-matched frames."""
         check(lib().mvsv_stream_set_bgr_match(self._live(), 1 if on else 0), self._ctx.handle)
 
+    def census(self, window=(9, 7)):
+        """Every frame pushed from now on is matched on the census cost with this
+        ``window`` = (width, height) (StereoSGBM.compute_census; mvsv_stream_set_census);
+        ``None`` switches back to the Birchfield-Tomasi cost.  Only while no frame is
+        pending, SGBM only, and not together with colour matching; every optional stage
+        follows the census map."""
+        cw, ch = (0, 0) if window is None else (int(window[0]), int(window[1]))
+        check(lib().mvsv_stream_set_census(self._live(), cw, ch), self._ctx.handle)
+
     def push_bgr(self, left, right):
         """Push a colour pair: uint8 (height, width, 3) BGR arrays of enable_bgr's shape."""
         self._live()

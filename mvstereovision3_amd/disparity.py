@@ -231,6 +231,29 @@ class StereoSGBM(StereoMatcher):
             return _run_device_bgr(lib().mvsv_sgbm_bgr_device, self._params, left, right, disparity, "StereoSGBM")
         return _run_host_bgr(lib().mvsv_sgbm_bgr, self._params, left, right, disparity, "StereoSGBM")
 
+    def compute_census(self, left, right, disparity=None, window=(9, 7)):
+        """StereoSGBM on the census cost (mvsv_sgbm_census): the pixel cost is the Hamming
+        distance of the two views' census descriptors over the ``window`` = (width,
+        height) neighbourhood (:func:`census_transform`); everything after the pixel
+        cost is :meth:`compute`'s.  Inputs and result as :meth:`compute`: (H, W) numpy
+        arrays, or (H, W) / (N, H, W) torch device tensors on the current stream.
+        preFilterCap has no effect; the cost is invariant under any strictly increasing
+        map of either image's intensities."""
+        cw, ch = (int(v) for v in window)
+        if _is_torch(left) != _is_torch(right):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "StereoSGBM: left and right must both be numpy or both torch")
+        if _is_torch(left):
+            return _run_device(lambda *a: lib().mvsv_sgbm_census_device(*a, cw, ch), self._params, left, right,
+                               disparity, "StereoSGBM")
+        return _run_host(lambda *a: lib().mvsv_sgbm_census(*a, cw, ch), self._params, left, right, disparity,
+                         "StereoSGBM")
+
+    def census_validate(self, width, height, window=(9, 7)) -> bool:
+        """mvsv_sgbm_census_validate: whether :meth:`compute_census` accepts these
+        parameters and this window for a width x height pair (no device needed)."""
+        return lib().mvsv_sgbm_census_validate(ctypes.byref(self._params), int(width), int(height),
+                                               int(window[0]), int(window[1])) == 0
+
     def setPreFilterCap(self, v): self._params.pre_filter_cap = int(v)      # noqa: E704
     def getPreFilterCap(self): return self._params.pre_filter_cap            # noqa: E704
     def setUniquenessRatio(self, v): self._params.uniqueness_ratio = int(v)  # noqa: E704
@@ -287,6 +310,13 @@ class Disparity:
     def sgbm_bgr(inputImages: Stereopair, output, dispCompute: StereoSGBM):
         """Disparity::sgbm on a CV_8UC3 pair (cv::StereoSGBM::compute matches in colour)."""
         return dispCompute.compute_bgr(inputImages.mLeft, inputImages.mRight, output)
+
+    @staticmethod
+    def binary_sgbm(inputImages: Stereopair, output, dispCompute: StereoSGBM, window=(9, 7)):
+        """Disparity::binary_sgbm (inc/disparity.h:30, src/disparity.cpp:12-15; commented out in
+        the reference as "currently not working"): SGBM on a census cost, on this engine's
+        own contract (StereoSGBM.compute_census)."""
+        return dispCompute.compute_census(inputImages.mLeft, inputImages.mRight, output, window)
 
     @staticmethod
     def bm(inputImages: Stereopair, output, dispCompute: StereoBM):
@@ -374,6 +404,39 @@ def tm(left, right, kernel_size: int, wide: bool = False):
     ctx = host_context()
     check(lib().mvsv_tm(ctx.handle, L.ctypes.data, L.strides[0], R.ctypes.data, R.strides[0], W, H, k,
                         out.ctypes.data, out.strides[0]), ctx.handle)
+    return out
+
+
+def census_transform(img, window=(9, 7)):
+    """The census descriptors :meth:`StereoSGBM.compute_census` matches on (mvsv_census):
+    uint64 per pixel, bit k = 1 iff the k-th window offset's pixel (row-major over the
+    ``window`` = (width, height) neighbourhood, centre skipped, clamped into the image)
+    is darker than the centre.  (H, W) uint8 numpy array -> numpy uint64; (H, W) or
+    (N, H, W) uint8 torch device tensor -> device tensor of int64 holding the same bits
+    (torch has no general uint64), on the current stream."""
+    cw, ch = (int(v) for v in window)
+    if _is_torch(img):
+        import torch
+        if img.dtype != torch.uint8 or not img.is_cuda or img.dim() not in (2, 3):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "census_transform: (H, W) or (N, H, W) uint8 device tensor expected")
+        t = img if img.dim() == 3 else img.unsqueeze(0)
+        if t.stride(2) != 1:
+            t = t.contiguous()
+        n, H, W = t.shape
+        out = torch.empty((n, H, W), dtype=torch.int64, device=img.device)
+        ctx = device_context(img)
+        check(lib().mvsv_census_device(ctx.handle, n, t.data_ptr(), t.stride(1), t.stride(0), W, H, cw, ch,
+                                       out.data_ptr(), W, H * W), ctx.handle)
+        return out if img.dim() == 3 else out[0]
+    a = np.asarray(img)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise MvsvError(_lib.MVSV_E_INVALID_ARG, "census_transform: a 2-D uint8 image expected")
+    if a.strides[1] != 1:
+        a = np.ascontiguousarray(a)
+    H, W = a.shape
+    out = np.empty((H, W), np.uint64)
+    ctx = host_context()
+    check(lib().mvsv_census(ctx.handle, a.ctypes.data, a.strides[0], W, H, cw, ch, out.ctypes.data, W), ctx.handle)
     return out
 
 
