@@ -16,6 +16,9 @@
  *                                     census cost, on this engine's own contract
  *   mvsv_bm / mvsv_bm_device          Disparity::bm          src/disparity.cpp:18-22,
  *                                     decl inc/disparity.h:31
+ *   mvsv_bm_census(_device)           Disparity::binary_bm: StereoBM on a census cost
+ *                                     (the StereoBinaryBM of inc/disparity.h:13's
+ *                                     module), on this engine's own contract
  *   mvsv_load_sgbm_yaml               Disparity::loadSGBMParameters
  *                                     src/disparity.cpp:60-108, inc/disparity.h:34
  *   mvsv_load_bm_yaml                 (new) loader for configs/bm.yml:2-7, which
@@ -384,6 +387,38 @@ MVSV_API int mvsv_census(mvsv_ctx* ctx, const uint8_t* img, size_t stride, int w
 MVSV_API int mvsv_census_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t stride, size_t frame_stride,
                                 int width, int height, int census_width, int census_height, uint64_t* out,
                                 size_t out_stride, size_t out_frame_stride);
+
+/* StereoBM on a census matching cost: Disparity::binary_bm.  The reference's file loop
+ * runs both matchers side by side (trgt/disparityTest.cpp:267-268) and the module its
+ * header names (inc/disparity.h:13, opencv_contrib stereo) pairs StereoBinarySGBM with
+ * StereoBinaryBM.  The contract is this engine's own, not opencv_contrib's.
+ *
+ * Descriptors: the census transform above, unchanged.  Pixel cost: wherever StereoBM
+ * takes |Lf(y, xl) - Rf(y, xr)| on prefiltered bytes, popcount(T_left(y, xl) ^
+ * T_right(y, xr)) for the same column pairs (virtual column j = x - lofs, left column
+ * lofs + clamp(j, -lofs, W - 1 - lofs), right column rofs + clamp(j, -rofs,
+ * W - numDisparities - rofs) + k).  Everything after the pixel cost is mvsv_bm's for the
+ * same parameters: blockSize^2 window sum, argmin (ties -> smallest index), uniqueness
+ * test, parabola fit, FILTERED = (minDisparity - 1) * 16, validateDisparity when
+ * disp12MaxDiff >= 0, the valid rectangle, filterSpeckles.  pre_filter_type,
+ * pre_filter_size, pre_filter_cap and texture_threshold have no effect (they are still
+ * checked by mvsv_bm_validate's rules); there is no texture test.  A map does not change
+ * under a strictly increasing map of either view's intensities.
+ *
+ * mvsv_bm_census_validate: mvsv_bm_validate's rules and the window rule.  Grey pairs only.
+ * The calls return MVSV_E_INVALID_ARG with a message that names the broken rule, also
+ * for a blockSize / numDisparities whose descriptor tiles no kernel form can hold.  Other
+ * arguments as mvsv_bm / mvsv_bm_device. */
+MVSV_API int mvsv_bm_census_validate(const mvsv_bm_params* p, int W, int H, int census_width,
+                                     int census_height);
+MVSV_API int mvsv_bm_census(mvsv_ctx* ctx, const uint8_t* left, size_t left_stride, const uint8_t* right,
+                            size_t right_stride, int width, int height, const mvsv_bm_params* p,
+                            int16_t* out, size_t out_stride, int census_width, int census_height);
+MVSV_API int mvsv_bm_census_device(mvsv_ctx* ctx, int n, const uint8_t* left, size_t left_stride,
+                                   size_t left_frame_stride, const uint8_t* right, size_t right_stride,
+                                   size_t right_frame_stride, int width, int height,
+                                   const mvsv_bm_params* p, int16_t* out, size_t out_stride,
+                                   size_t out_frame_stride, int census_width, int census_height);
 
 /* MeanDisparityDetection post-pass on device: 9x9 tile means of an int16 map
  * (tile = (W/9)x(H/9), remainder ignored; mean over values > 1 with integer
@@ -869,6 +904,12 @@ MVSV_API int mvsv_stream_set_bgr_match(mvsv_stream* s, int on);
  * a switch to StereoBM are refused, and mvsv_stream_set_params validates against the
  * census rules.  Every stage computed from the map follows the census map. */
 MVSV_API int mvsv_stream_set_census(mvsv_stream* s, int census_width, int census_height);
+/* mvsv_stream_set_bm_census: the same for the StereoBM matcher (mvsv_bm_census_device);
+ * 0, 0 switches back to the SAD cost.  Valid while no frame is pending and with the
+ * StereoBM matcher (MVSV_E_INVALID_ARG otherwise, also for a window or parameters that
+ * mvsv_bm_census_validate refuses); while it is on, mvsv_stream_set_bm_params validates
+ * against the census rules and mvsv_stream_set_params (a switch to SGBM) is refused. */
+MVSV_API int mvsv_stream_set_bm_census(mvsv_stream* s, int census_width, int census_height);
 
 /* ---- device ends of a stream: frames from device memory, maps handed back there ------
  * mvsv_stream_push_device / _push_raw_device / _push_bgr_device: n >= 1 frames (strides in

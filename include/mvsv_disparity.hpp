@@ -271,6 +271,20 @@ public:
                       reinterpret_cast<int16_t*>(disparity.data), disparity.step / 2),
               c);
     }
+    // CV_8UC1 pairs on the census cost (mvsv_bm_census): the Hamming distance of the census
+    // descriptors over a census_width x census_height window in place of the SAD of the
+    // prefiltered views; everything after the pixel cost is compute()'s, without the
+    // texture test
+    void computeCensus(const Mat& left, const Mat& right, Mat& disparity, int census_width = 9, int census_height = 7)
+    {
+        check_pair(left, right);
+        disparity.create(left.rows, left.cols, MAT_16SC1);
+        mvsv_ctx* c = thread_context();
+        check(mvsv_bm_census(c, left.data, left.step, right.data, right.step, left.cols, left.rows, &p,
+                             reinterpret_cast<int16_t*>(disparity.data), disparity.step / 2, census_width,
+                             census_height),
+              c);
+    }
     void setMinDisparity(int v) { p.min_disparity = v; }
     int getMinDisparity() const { return p.min_disparity; }
     void setNumDisparities(int v) { p.num_disparities = v; }
@@ -290,6 +304,39 @@ public:
     int getUniquenessRatio() const { return p.uniqueness_ratio; }
     mvsv_bm_params p{};
 };
+
+// The matcher of Disparity::binary_bm (opencv_contrib's stereo module, which the reference
+// includes at inc/disparity.h:13, names it cv::stereo::StereoBinaryBM): a StereoBM that
+// carries its census window.  The matching is this engine's own census contract
+// (include/mvsv.h), not opencv_contrib's.
+namespace stereo {
+class StereoBinaryBM : public StereoBM {
+public:
+    static Ptr<StereoBinaryBM> create(int numDisparities = 0, int blockSize = 9)
+    {
+        auto m = std::make_shared<StereoBinaryBM>();
+        mvsv_bm_params_default(&m->p, numDisparities, blockSize);
+        return m;
+    }
+    void setCensusWindow(int width, int height)
+    {
+        census_width = width;
+        census_height = height;
+    }
+    int getCensusWidth() const { return census_width; }
+    int getCensusHeight() const { return census_height; }
+    // whether compute() accepts the parameters and the window for a width x height pair
+    bool validate(int width, int height) const
+    {
+        return mvsv_bm_census_validate(&p, width, height, census_width, census_height) == MVSV_OK;
+    }
+    void compute(const Mat& left, const Mat& right, Mat& disparity)
+    {
+        computeCensus(left, right, disparity, census_width, census_height);
+    }
+    int census_width = 9, census_height = 7;
+};
+}  // namespace stereo
 
 }  // namespace mvsv
 
@@ -345,6 +392,22 @@ inline void binary_sgbm(Pair const& inputImages, mvsv::Mat& output,
 // src/disparity.cpp:18-22
 template <class Pair>
 inline void bm(Pair const& inputImages, mvsv::Mat& output, mvsv::Ptr<mvsv::StereoBM> dispCompute)
+{
+    dispCompute->compute(inputImages.mLeft, inputImages.mRight, output);
+}
+
+// StereoBM on a census cost (mvsv_bm_census), the counterpart of binary_sgbm for the fast
+// matcher.  With a StereoBM the window is an argument; a stereo::StereoBinaryBM carries
+// its own.
+template <class Pair>
+inline void binary_bm(Pair const& inputImages, mvsv::Mat& output, mvsv::Ptr<mvsv::StereoBM> dispCompute,
+                      int census_width = 9, int census_height = 7)
+{
+    dispCompute->computeCensus(inputImages.mLeft, inputImages.mRight, output, census_width, census_height);
+}
+template <class Pair>
+inline void binary_bm(Pair const& inputImages, mvsv::Mat& output,
+                      mvsv::Ptr<mvsv::stereo::StereoBinaryBM> dispCompute)
 {
     dispCompute->compute(inputImages.mLeft, inputImages.mRight, output);
 }

@@ -163,6 +163,10 @@ def _declare(lib, strict=True):
         "mvsv_census": ([P, P, Z, I, I, I, I, P, Z], I),
         "mvsv_census_device": ([P, I, P, Z, Z, I, I, I, I, P, Z, Z], I),
         "mvsv_stream_set_census": ([P, I, I], I),
+        "mvsv_bm_census_validate": ([P, I, I, I, I], I),
+        "mvsv_bm_census": ([P, P, Z, P, Z, I, I, P, P, Z, I, I], I),
+        "mvsv_bm_census_device": ([P, I, P, Z, Z, P, Z, Z, I, I, P, P, Z, Z, I, I], I),
+        "mvsv_stream_set_bm_census": ([P, I, I], I),
         "mvsv_mean_disparity_grid_device": ([P, I, P, Z, Z, I, I, P], I),
         "mvsv_median_blur3_device": ([P, I, P, Z, Z, P, Z, Z, I, I], I),
         "mvsv_filter_speckles_device": ([P, I, P, Z, Z, I, I, I, I, I], I),

@@ -24,6 +24,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "mvsv_bm_decide.hpp"
 #include "mvsv_device.hpp"
 #include "mvsv_internal.hpp"
 
@@ -283,10 +284,12 @@ __global__ __launch_bounds__(256) void bm_match_kernel(const uint8_t* __restrict
 //     same way) and the parabola neighbours as bm_match_kernel.
 // Same virtual-column clamps and the same per-pixel decisions as
 // bm_match_kernel (which remains for blockSize > 21 or numDisparities > 128).
+// The slab phase (argmin, uniqueness, parabola neighbours, records, flush) is
+// bm2::decide_row of mvsv_bm_decide.hpp, shared with the census kernel.
 // ---------------------------------------------------------------------------
-constexpr int kBm2Cols = 16;   // output columns per column group
-constexpr int kBm2Waves = 4;   // waves per block
-constexpr uint32_t kBm2Pad = 0x10000u;  // per-column offset of the unused disparity lanes
+constexpr int kBm2Cols = bm2::kCols;    // output columns per column group
+constexpr int kBm2Waves = bm2::kWaves;  // waves per block
+constexpr uint32_t kBm2Pad = bm2::kPad;  // per-column offset of the unused disparity lanes
 
 struct Bm2Layout {
     int NJ, NJP, NRW, NRC;
@@ -436,11 +439,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
     const uint32_t capsh = (uint32_t)(e.cap + 1) << (8 * ((c0 + lane) & 3));
     __syncthreads();
 
-    // argmin phase: output column qx of the group (LPC lanes each), sub-lane h
-    // scans the disparity indices [16 h, 16 h + 16)
-    constexpr int LPC = 4 * NR, CPW = kBm2Cols / NR;
-    const int qx = g * CPW + lane / LPC, h = lane % LPC;
-
     uint32_t cs[NC];
     uint32_t tc = 0;  // texture column sum of virtual column `lane` (lanes < NC)
     auto colsums = [&](auto LIN, auto INIT, int t) {
@@ -482,51 +480,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
             }
         }
     };
-    auto group_sync = [&]() {
-        if constexpr (NR == 1) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        } else {
-            __syncthreads();
-        }
-    };
-    auto wave_sync = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    // output records: rows t0 .. t0 + cnt - 1 of the wave's CPW columns; lane
-    // (slot, column) = (lane / CPW, lane % CPW)
-    constexpr int RB = LPC;  // rows per flush: RB * CPW = 64
-    auto flush = [&](int t0, int cnt) {
-        wave_sync();  // the h == 0 lanes' records
-        const int slot = lane / CPW, qf = g * CPW + lane % CPW;
-        const int xf = xl0 + c0 + qf, xi = lofs + xf;
-        if (slot < cnt && xf < e.ncol) {
-            const uint2 r = recs[lane];
-            const int y = yr0 + t0 + slot;
-            const int mind = (int)(r.x & 0xffu);
-            const int minsad = (int)((r.x & 0x3fffffffu) >> 8);
-            int16_t res = (int16_t)e.filtered;
-            const bool fail = (!keep_border && (xi < e.xmin || xi >= e.xmax)) || (r.x >> 30) != 0;
-            if (!fail) {
-                const int pp = (int)(r.y & 0xffffu), nn = (int)(r.y >> 16);
-                const int v1 = nd - mind - 1 + e.mindisp;
-                int val;
-                if (0 < mind && mind < nd - 1) {
-                    const int d = pp + nn - 2 * minsad + abs(pp - nn);
-                    val = (v1 * 256 + (d != 0 ? (pp - nn) * 256 / d : 0) + 15) >> 4;
-                } else {
-                    val = (v1 * 256 + 15) >> 4;
-                }
-                res = (int16_t)val;
-                if (cost) cost[((size_t)f * H + y) * W + xi] = minsad;
-            }
-            out[f * ofs + (size_t)y * os + xi] = res;
-        }
-    };
-    // one row's window SADs, argmin, tests and output
+    const bm2::Where where{f, xl0, c0, yr0, W, H, keep_border, out, os, ofs, cost};
+    // one row's window SADs into the slab; argmin, tests and output: bm2::decide_row
     auto row_out = [&](int t) {
         // window SADs of the group's 16 output columns -> slab [column][disparity]
         {
@@ -542,71 +497,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
             }
         }
         tcb[lane] = (int)tc;
-        group_sync();
-        uint32_t* srow = sadx + qx * SS;
-        const int k0 = h * 16;
-        // argmin over this lane's 16 slab entries, keys (sad << 8) | index
-        uint32_t best;
-        {
-            uint32_t key[16];
-#pragma unroll
-            for (int i = 0; i < 16; i += 4) {
-                const uint4 w = *(const uint4*)(srow + k0 + i);
-                key[i] = (w.x << 8) | (uint32_t)i;
-                key[i + 1] = (w.y << 8) | (uint32_t)(i + 1);
-                key[i + 2] = (w.z << 8) | (uint32_t)(i + 2);
-                key[i + 3] = (w.w << 8) | (uint32_t)(i + 3);
-            }
-            best = min(key[0], key[1]);
-#pragma unroll
-            for (int i = 2; i < 16; i += 2) best = min(min(best, key[i]), key[i + 1]);
-            best |= (uint32_t)k0;
-        }
-        best = min(best, (uint32_t)__builtin_amdgcn_mov_dpp((int)best, 0xB1, 0xf, 0xf, false));
-        best = min(best, (uint32_t)__builtin_amdgcn_mov_dpp((int)best, 0x4E, 0xf, 0xf, false));
-        if constexpr (NR == 2)  // row_half_mirror: quad 0 <-> quad 1 of each 8 lanes
-            best = min(best, (uint32_t)__builtin_amdgcn_mov_dpp((int)best, 0x141, 0xf, 0xf, false));
-        const int mind = (int)(best & 0xff);
-        const uint32_t minsad = best >> 8;
-        // parabola neighbours (read before the uniqueness pass masks them)
-        const int pp = (int)srow[min(mind + 1, 64 * NR - 1)];
-        const int nn = (int)srow[max(mind - 1, 0)];
-        bool bad = false;
-        if (e.uniq > 0) {
-            const uint32_t ms = minsad;
-            const uint32_t thresh = ms + (uint32_t)((int)ms * e.uniq / 100);
-            wave_sync();  // every lane of the column has read the slab row
-            if (h == 0) {
-                srow[mind] = 0xffffffffu;
-                if (mind > 0) srow[mind - 1] = 0xffffffffu;
-                if (mind + 1 < 64 * NR) srow[mind + 1] = 0xffffffffu;
-            }
-            wave_sync();
-            uint32_t m2 = 0xffffffffu;
-#pragma unroll
-            for (int i = 0; i < 16; i += 4) {
-                const uint4 w = *(const uint4*)(srow + k0 + i);
-                m2 = min(min(m2, w.x), w.y);
-                m2 = min(min(m2, w.z), w.w);
-            }
-            m2 = min(m2, (uint32_t)__builtin_amdgcn_mov_dpp((int)m2, 0xB1, 0xf, 0xf, false));
-            m2 = min(m2, (uint32_t)__builtin_amdgcn_mov_dpp((int)m2, 0x4E, 0xf, 0xf, false));
-            if constexpr (NR == 2)
-                m2 = min(m2, (uint32_t)__builtin_amdgcn_mov_dpp((int)m2, 0x141, 0xf, 0xf, false));
-            bad = m2 <= thresh;
-        }
-        int tsum = 0;
-#pragma unroll
-        for (int qq = 0; qq < win; qq++) tsum += tcb[qx + qq];
-        // park the column's verdict; every RB rows the wave's 64 lanes finish
-        // RB x CPW pixels at once (division, stores) instead of 16 / NR lanes
-        // per row
-        if (h == 0)
-            recs[(t & (RB - 1)) * CPW + lane / LPC] =
-                make_uint2(best | (bad ? 1u << 31 : 0u) | (tsum < e.tex ? 1u << 30 : 0u),
-                           ((uint32_t)pp & 0xffffu) | ((uint32_t)nn << 16));
-        if ((t & (RB - 1)) == RB - 1 || t == rows - 1) flush(t & ~(RB - 1), (t & (RB - 1)) + 1);
-        group_sync();
+        bm2::decide_row<NR, win, true>(sadx, tcb, recs, lane, g, t, rows, e, where);
     };
     // the whole row walk per addressing variant (no register copies between
     // variants at the loop back edge); row 0 builds the column sums
@@ -697,6 +588,15 @@ int bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, con
     if (e.lofs >= W || e.rofs >= W || e.width1 < 1) return MVSV_OK;
     if (e.xmax - e.xmin <= 0 || e.ymax - e.ymin <= 0 || e.ncol <= 0) return MVSV_OK;
     const size_t plane = (size_t)W * H;
+    if (bm_census(e)) {  // the census cost (mvsv_bm_census.hip): descriptors in place of the prefilter
+        int* ccost = nullptr;
+        if (e.disp12 >= 0) {
+            if ((rc = ensure(ctx, ctx->bm_cost, (size_t)n * plane * 4, "bm cost map"))) return rc;
+            ccost = (int*)ctx->bm_cost.ptr;
+        }
+        if ((rc = bm_census_match(ctx, n, L, ls, lfs, R, rs, rfs, W, H, e, out, os, ofs, ccost))) return rc;
+        return bm_finish(ctx, n, W, H, e, out, os, ofs, ccost);
+    }
     // + 64: the match kernel's staging reads whole aligned dwords past a row end
     if ((rc = ensure(ctx, ctx->bm_lf, (size_t)n * plane + 64, "bm left prefilter"))) return rc;
     if ((rc = ensure(ctx, ctx->bm_rf, (size_t)n * plane + 64, "bm right prefilter"))) return rc;

@@ -241,6 +241,21 @@ int resolve_bm(const mvsv_bm_params* p, int W, int H, BmEff* e, std::string* why
     e->speckle_range = p->speckle_range;
     e->prefilter_type = p->pre_filter_type;
     e->prefilter_size = p->pre_filter_size;
+    e->cw = e->ch = 0;
+    return MVSV_OK;
+}
+
+// A census call: mvsv_bm_validate's rules and the window rule.  blockSize^2 * bits is
+// at most 255^2 * 64 < 2^24: no sum leaves 32 bits or the (cost << 8 | index) keys.
+int resolve_bm_census(const mvsv_bm_params* p, int W, int H, int cw, int ch, BmEff* e, std::string* why)
+{
+    if (int rc = resolve_bm(p, W, H, e, why)) return rc;
+    if (const char* bad = census_window_check(cw, ch)) {
+        *why = bad;
+        return MVSV_E_INVALID_ARG;
+    }
+    e->cw = cw;
+    e->ch = ch;
     return MVSV_OK;
 }
 
@@ -356,6 +371,13 @@ int mvsv_bm_validate(const mvsv_bm_params* p, int W, int H)
     BmEff e;
     std::string why;
     return resolve_bm(p, W, H, &e, &why);
+}
+
+int mvsv_bm_census_validate(const mvsv_bm_params* p, int W, int H, int cw, int ch)
+{
+    BmEff e;
+    std::string why;
+    return resolve_bm_census(p, W, H, cw, ch, &e, &why);
 }
 
 int mvsv_create(mvsv_ctx** out, int hip_device)
@@ -733,9 +755,10 @@ int mvsv_census_device(mvsv_ctx* ctx, int n, const uint8_t* img, size_t st, size
     return mark_last_use(ctx, census_device(ctx, n, 1, img, st, fs, img, st, fs, W, H, cw, ch, out, os, 0, ofs));
 }
 
-int mvsv_bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs,
-                   const uint8_t* R, size_t rs, size_t rfs, int W, int H,
-                   const mvsv_bm_params* p, int16_t* out, size_t os, size_t ofs)
+// mvsv_bm_device / mvsv_bm_census_device (census: the cw x ch window)
+static int bm_device_call(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
+                          size_t rs, size_t rfs, int W, int H, const mvsv_bm_params* p, int16_t* out, size_t os,
+                          size_t ofs, bool census, int cw, int ch)
 {
     if (!ctx) return MVSV_E_INVALID_ARG;
     if (n <= 0 || !L || !R || !out) return set_error(ctx, MVSV_E_INVALID_ARG, "null buffer or n <= 0");
@@ -743,7 +766,7 @@ int mvsv_bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs
         return set_error(ctx, MVSV_E_INVALID_ARG, "stride smaller than width");
     BmEff e;
     std::string why;
-    int rc = resolve_bm(p, W, H, &e, &why);
+    int rc = census ? resolve_bm_census(p, W, H, cw, ch, &e, &why) : resolve_bm(p, W, H, &e, &why);
     if (rc) return set_error(ctx, rc, why);
     DeviceGuard dev_guard(ctx->device);
     auto body = [&]() { return bm_device(ctx, n, L, ls, lfs, R, rs, rfs, W, H, e, out, os, ofs); };
@@ -768,6 +791,20 @@ int mvsv_bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs
         return mark_last_use(ctx, graph_run(ctx, key, body));
     }
     return mark_last_use(ctx, body());
+}
+
+int mvsv_bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs,
+                   const uint8_t* R, size_t rs, size_t rfs, int W, int H,
+                   const mvsv_bm_params* p, int16_t* out, size_t os, size_t ofs)
+{
+    return bm_device_call(ctx, n, L, ls, lfs, R, rs, rfs, W, H, p, out, os, ofs, false, 0, 0);
+}
+
+int mvsv_bm_census_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
+                          size_t rs, size_t rfs, int W, int H, const mvsv_bm_params* p, int16_t* out, size_t os,
+                          size_t ofs, int cw, int ch)
+{
+    return bm_device_call(ctx, n, L, ls, lfs, R, rs, rfs, W, H, p, out, os, ofs, true, cw, ch);
 }
 
 int mvsv_mean_disparity_grid_device(mvsv_ctx* ctx, int n, const int16_t* dmap, size_t st,
@@ -1003,7 +1040,7 @@ int mvsv_view(mvsv_ctx* ctx, const int16_t* dmap, size_t st, int W, int H, const
 }
 
 // One host pair through either matcher; cn: bytes per input pixel (3: mvsv_sgbm_bgr);
-// census: mvsv_sgbm_census with the cw x ch window
+// census: mvsv_sgbm_census / mvsv_bm_census with the cw x ch window
 static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs,
                      int W, int H, int16_t* out, size_t os, bool sgbm, const void* params, int cn = 1,
                      bool census = false, int cw = 0, int ch = 0)
@@ -1017,9 +1054,10 @@ static int host_call(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* 
     SgbmEff se;
     BmEff be;
     std::string why;
-    rc = census ? resolve_sgbm_census((const mvsv_sgbm_params*)params, W, H, cw, ch, &se, &why)
-         : sgbm ? resolve_sgbm((const mvsv_sgbm_params*)params, W, H, &se, &why)
-                : resolve_bm((const mvsv_bm_params*)params, W, H, &be, &why);
+    rc = sgbm ? (census ? resolve_sgbm_census((const mvsv_sgbm_params*)params, W, H, cw, ch, &se, &why)
+                        : resolve_sgbm((const mvsv_sgbm_params*)params, W, H, &se, &why))
+              : (census ? resolve_bm_census((const mvsv_bm_params*)params, W, H, cw, ch, &be, &why)
+                        : resolve_bm((const mvsv_bm_params*)params, W, H, &be, &why));
     if (rc) return set_error(ctx, rc, why);
     if (sgbm) se.cn = cn;
     if (sgbm && (rc = check_report(ctx))) return rc;  // an earlier device call's give-up
@@ -1085,6 +1123,12 @@ int mvsv_bm(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t
             int H, const mvsv_bm_params* p, int16_t* out, size_t os)
 {
     return host_call(ctx, L, ls, R, rs, W, H, out, os, false, p);
+}
+
+int mvsv_bm_census(mvsv_ctx* ctx, const uint8_t* L, size_t ls, const uint8_t* R, size_t rs, int W, int H,
+                   const mvsv_bm_params* p, int16_t* out, size_t os, int cw, int ch)
+{
+    return host_call(ctx, L, ls, R, rs, W, H, out, os, false, p, 1, true, cw, ch);
 }
 
 }  // extern "C"

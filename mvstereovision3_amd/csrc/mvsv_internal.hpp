@@ -25,12 +25,17 @@ struct BmEff {
     int disp12;                  // < 0: off
     int speckle_window, speckle_range;
     int prefilter_type, prefilter_size;
+    int cw, ch;                  // census window (mvsv_bm_census); 0, 0: the SAD cost
 };
+inline bool bm_census(const BmEff& e) { return e.cw != 0; }
 
 // Resolve + validate (OpenCV's asserts). Return MVSV_OK or MVSV_E_INVALID_ARG
 // and an explanation in *why.
 int resolve_sgbm(const mvsv_sgbm_params* p, int W, int H, SgbmEff* e, std::string* why);
 int resolve_bm(const mvsv_bm_params* p, int W, int H, BmEff* e, std::string* why);
+// resolve_bm plus the window rule of a census call (include/mvsv.h mvsv_bm_census_validate);
+// e->cw, e->ch are set
+int resolve_bm_census(const mvsv_bm_params* p, int W, int H, int cw, int ch, BmEff* e, std::string* why);
 
 // Grow-only cached device buffer.
 struct DevBuf {
@@ -191,6 +196,10 @@ inline SgbmPlan sgbm_make_plan(const mvsv_ctx* ctx, const SgbmEff& e, int n, int
 int bm_device(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R,
               size_t rs, size_t rfs, int W, int H, const BmEff& e, int16_t* out, size_t os,
               size_t ofs);
+// A census call's descriptors and match kernel (mvsv_bm_census.hip), between bm_device's
+// fill and its finishing passes; cost: the minimum-cost map validateDisparity reads, or null
+int bm_census_match(mvsv_ctx* ctx, int n, const uint8_t* L, size_t ls, size_t lfs, const uint8_t* R, size_t rs,
+                    size_t rfs, int W, int H, const BmEff& e, int16_t* out, size_t os, size_t ofs, int* cost);
 // SGBM stages 1-3 (mvsv_cost.hip): BT interval planes, the cost volume (the kernel
 // and tile height the plan names; the register-ring kernel also writes the residual
 // plane Rv or the bit-sliced C' planes Bv where the plan says so), and OpenCV 3.4's

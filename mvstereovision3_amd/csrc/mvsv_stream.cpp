@@ -784,6 +784,9 @@ int mvsv_stream_set_params(mvsv_stream* st, const mvsv_sgbm_params* p)
     int rc = sgbm_census(st->eff) ? resolve_sgbm_census(p, st->W, st->H, st->eff.cw, st->eff.ch, &e, &why)
                                   : resolve_sgbm(p, st->W, st->H, &e, &why);
     if (rc) return set_error(st->ctx, rc, why);
+    if (st->matcher == MVSV_MATCHER_BM && bm_census(st->bm_eff))
+        return set_error(st->ctx, MVSV_E_INVALID_ARG,
+                         "the StereoBM census cost is on (mvsv_stream_set_bm_census): switch it off before a switch to SGBM");
     DeviceGuard dev_guard(st->ctx->device);
     if ((rc = stream_launch(st))) return rc;  // pending frames keep the old parameters
     st->params = *p;  // applies to frames pushed from now on (trgt/mean_test.cpp:348 setters)
@@ -797,7 +800,10 @@ int mvsv_stream_set_bm_params(mvsv_stream* st, const mvsv_bm_params* p)
     if (!st) return MVSV_E_INVALID_ARG;
     BmEff e;
     std::string why;
-    int rc = resolve_bm(p, st->W, st->H, &e, &why);
+    // (a window set with mvsv_stream_set_bm_census stays: the new parameters must satisfy its rules)
+    const bool census = st->matcher == MVSV_MATCHER_BM && bm_census(st->bm_eff);
+    int rc = census ? resolve_bm_census(p, st->W, st->H, st->bm_eff.cw, st->bm_eff.ch, &e, &why)
+                    : resolve_bm(p, st->W, st->H, &e, &why);
     if (rc) return set_error(st->ctx, rc, why);
     if (st->bgr.match)
         return set_error(st->ctx, MVSV_E_INVALID_ARG, "colour matching is on: StereoBM takes grey pairs only");
@@ -1019,6 +1025,23 @@ int mvsv_stream_set_census(mvsv_stream* st, int cw, int ch)
         return set_error(ctx, MVSV_E_INVALID_ARG, "colour matching is on: the census cost takes grey pairs only");
     if (int rc = resolve_sgbm_census(&st->params, st->W, st->H, cw, ch, &e, &why)) return set_error(ctx, rc, why);
     st->eff = e;
+    return MVSV_OK;
+}
+
+int mvsv_stream_set_bm_census(mvsv_stream* st, int cw, int ch)
+{
+    if (!st) return MVSV_E_INVALID_ARG;
+    mvsv_ctx* ctx = st->ctx;
+    if (int rc = idle_check(st, "the census cost changes")) return rc;
+    if (st->matcher != MVSV_MATCHER_BM)
+        return set_error(ctx, MVSV_E_INVALID_ARG,
+                         "the StereoBM census cost is for the StereoBM matcher only (mvsv_stream_set_census is SGBM's)");
+    BmEff e;
+    std::string why;
+    if (int rc = (cw == 0 && ch == 0) ? resolve_bm(&st->bm_params, st->W, st->H, &e, &why)  // back to the SAD cost
+                                      : resolve_bm_census(&st->bm_params, st->W, st->H, cw, ch, &e, &why))
+        return set_error(ctx, rc, why);
+    st->bm_eff = e;
     return MVSV_OK;
 }
 

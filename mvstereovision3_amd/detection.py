@@ -569,6 +569,15 @@ class DisparityStream:
         cw, ch = (0, 0) if window is None else (int(window[0]), int(window[1]))
         check(lib().mvsv_stream_set_census(self._live(), cw, ch), self._ctx.handle)
 
+    def bm_census(self, window=(9, 7)):
+        """The same for a StereoBM stream (StereoBM.compute_census;
+        mvsv_stream_set_bm_census): every frame pushed from now on is matched on the
+        census cost with this ``window``; ``None`` switches back to the SAD cost.  Only
+        while no frame is pending and with the StereoBM matcher; while it is on a switch
+        to SGBM is refused."""
+        cw, ch = (0, 0) if window is None else (int(window[0]), int(window[1]))
+        check(lib().mvsv_stream_set_bm_census(self._live(), cw, ch), self._ctx.handle)
+
     def push_bgr(self, left, right):
         """Push a colour pair: uint8 (height, width, 3) BGR arrays of enable_bgr's shape."""
         self._live()

@@ -284,6 +284,30 @@ class StereoBM(StereoMatcher):
     def _host_fn(self): return lib().mvsv_bm           # noqa: E704
     def _dev_fn(self): return lib().mvsv_bm_device     # noqa: E704
 
+    def compute_census(self, left, right, disparity=None, window=(9, 7)):
+        """StereoBM on the census cost (mvsv_bm_census): the pixel cost is the Hamming
+        distance of the two views' census descriptors over the ``window`` = (width,
+        height) neighbourhood (:func:`census_transform`) in place of the SAD of the
+        prefiltered views; everything after the pixel cost is :meth:`compute`'s.
+        Inputs and result as :meth:`compute`: (H, W) numpy arrays, or (H, W) / (N, H, W)
+        torch device tensors on the current stream.  The prefilter fields and the
+        texture threshold have no effect; the map is invariant under any strictly
+        increasing map of either image's intensities."""
+        cw, ch = (int(v) for v in window)
+        if _is_torch(left) != _is_torch(right):
+            raise MvsvError(_lib.MVSV_E_INVALID_ARG, "StereoBM: left and right must both be numpy or both torch")
+        if _is_torch(left):
+            return _run_device(lambda *a: lib().mvsv_bm_census_device(*a, cw, ch), self._params, left, right,
+                               disparity, "StereoBM")
+        return _run_host(lambda *a: lib().mvsv_bm_census(*a, cw, ch), self._params, left, right, disparity,
+                         "StereoBM")
+
+    def census_validate(self, width, height, window=(9, 7)) -> bool:
+        """mvsv_bm_census_validate: whether :meth:`compute_census` accepts these
+        parameters and this window for a width x height pair (no device needed)."""
+        return lib().mvsv_bm_census_validate(ctypes.byref(self._params), int(width), int(height),
+                                             int(window[0]), int(window[1])) == 0
+
     def setPreFilterType(self, v): self._params.pre_filter_type = int(v)     # noqa: E704
     def getPreFilterType(self): return self._params.pre_filter_type          # noqa: E704
     def setPreFilterSize(self, v): self._params.pre_filter_size = int(v)     # noqa: E704
@@ -322,6 +346,13 @@ class Disparity:
     def bm(inputImages: Stereopair, output, dispCompute: StereoBM):
         """src/disparity.cpp:18-22."""
         return dispCompute.compute(inputImages.mLeft, inputImages.mRight, output)
+
+    @staticmethod
+    def binary_bm(inputImages: Stereopair, output, dispCompute: StereoBM, window=(9, 7)):
+        """StereoBM on a census cost (StereoBM.compute_census), the counterpart of
+        binary_sgbm for the fast matcher (trgt/disparityTest.cpp:267-268 runs both
+        matchers side by side), on this engine's own contract."""
+        return dispCompute.compute_census(inputImages.mLeft, inputImages.mRight, output, window)
 
     @staticmethod
     def tm(inputImages: Stereopair, output, kernelSize: int):

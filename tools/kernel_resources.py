@@ -21,7 +21,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mvstereovision3_amd", "csrc")
 DEFAULT = (["mvsv_cost.hip", "mvsv_census.hip", "mvsv_sgbm.hip"] + [f"mvsv_sgbm_packed.hip:MVSV_SGBM_NP={n}" for n in (1, 2, 4, 8)] +
-           ["mvsv_bsgm.hip", "mvsv_bm.hip", "mvsv_post.hip"])
+           ["mvsv_bsgm.hip", "mvsv_bm.hip", "mvsv_bm_census.hip", "mvsv_post.hip"])
 
 
 def demangle(names):
