@@ -276,7 +276,17 @@ MVSV_API int mvsv_set_option(mvsv_ctx* ctx, int option, long long value);
 MVSV_API int mvsv_trim(mvsv_ctx* ctx);
 
 /* Host pointers, synchronous.  Strides are in elements (bytes for u8, int16
- * elements for out); stride >= W allows ROI views (src/Stereosystem.cpp:255-256). */
+ * elements for out); stride >= W allows ROI views (src/Stereosystem.cpp:255-256).
+ *
+ * mvsv_sgbm and costs above 32767.  P2 + blockSize^2 pixel costs can pass int16 on
+ * high-contrast pairs (blockSize 21, or 15 with P2 in the thousands).  OpenCV's own map then
+ * depends on its build: the SIMD build's cost-row update saturates, the scalar (non-SIMD)
+ * build's wraps modulo 2^16, and a wrapped -- negative -- cost wins the WTA in both.  The
+ * engine reproduces the scalar build bit for bit: modular cost rows, signed path costs, a
+ * signed S saturated on both sides (tests/test_gpu_sgbm_wrap.py).  The
+ * test oracle's default flags restate the saturating update, ORC_F_COST_WRAP the wrapping
+ * one; on the tests' inputs the two differ in 27 % of the map pixels.  MODE_HH4 and three
+ * live colour channels have no reference in this regime. */
 MVSV_API int mvsv_sgbm(mvsv_ctx* ctx, const uint8_t* left, size_t left_stride,
                        const uint8_t* right, size_t right_stride, int width, int height,
                        const mvsv_sgbm_params* p, int16_t* out, size_t out_stride);

@@ -148,7 +148,10 @@ __global__ __launch_bounds__(256) void sgbm_prefilter_bgr_kernel(
 //          instruction (bytes -> u16 halves with v_perm_b32);
 //   hsum   horizontal box sum, sliding along the thread's run of RUN columns;
 //   vsum   vertical window sum kept in registers, the last 2*SH2+1 horizontal
-//          sums in an LDS ring; emit C = P2 + window sum (u16 wrap = int16 cast).
+//          sums in an LDS ring; emit C = P2 + window sum (u16 wrap = int16 cast:
+//          the cost-row update of OpenCV's non-SIMD build, oracle flag
+//          ORC_F_COST_WRAP; sums that really pass 32767 run in
+//          tests/test_gpu_sgbm_wrap.py, both kernels -- DESIGN.md 4b-wrap).
 // CN = 3 (interleaved BGR pairs, planes [frame][2][3][H][W]): a source row is
 // staged and BT-costed once per colour channel and the channels' costs are
 // summed in the pixel-cost row (<= 3 * 189 per u16 half) before the row enters

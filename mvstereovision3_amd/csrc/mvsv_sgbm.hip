@@ -175,6 +175,8 @@ __global__ __launch_bounds__(64) void sgbm_final_kernel(const int16_t* __restric
     const uint32_t p1x2 = (uint32_t)(e.P1 & 0xffff) * 0x10001u;
     const uint32_t p2x2 = (uint32_t)(e.P2 & 0xffff) * 0x10001u;
     const int ndir = sgbm_ndir(e);  // 8, 5 or 4
+    // a cost may pass 32767: C read as signed, S saturated on both sides
+    const bool sgn = sgbm_signed_costs(e);
     int minp = 0;
     const int uq = e.uniq;
 
@@ -213,6 +215,14 @@ __global__ __launch_bounds__(64) void sgbm_final_kernel(const int16_t* __restric
             u16x2 sv = __builtin_elementwise_min(__builtin_elementwise_add_sat(t, acc),
                                                  (u16x2){32767, 32767});
             st[p] = valid[p] ? __builtin_bit_cast(uint32_t, sv) : 0x7fff7fffu;
+            if (sgn && valid[p]) {
+                // S = clamp(ndir*(C - P2) + sum of deltas, -32768, MAX_COST) on the signed cost, in int32
+                const uint32_t dl2 = path_delta(ln[p], c[p], p2x2);
+                auto one = [&](int cs, uint32_t a, uint32_t dlt) -> int {
+                    return max(min(ndir * (cs - e.P2) + (int)(a & 0xffffu) + (int)(dlt & 0xffffu), kMaxCost), -32768);
+                };
+                st[p] = pk2(one(lo16(c[p]), sb[j][p], dl2), one(hi16(c[p]), sb[j][p] >> 16, dl2 >> 16));
+            }
             lp[p] = ln[p];
 #pragma unroll
             for (int h = 0; h < 2; h++) {

@@ -11,6 +11,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "mvsv_device.hpp"
 #include "mvsv_internal.hpp"
@@ -407,7 +408,9 @@ __device__ __forceinline__ void sgm_step_row(const uint32_t (&lp)[NP], uint32_t 
 // non-negative int16, so with u = delta - min(m, delta) = max(delta - m, 0)
 // (one unsigned saturating subtract) L = C - u, and the path's increment over
 // cb is P2 - u: five VALU per pair instead of six.  tu[] returns u (NW) or the
-// signed t = -u (the general form, exact for wrapped costs too).
+// signed t = -u (the general form: signed saturating int16 as OpenCV's SIMD
+// recurrence, so it stays exact on a wrapped -- negative -- cost; the final
+// kernels carry a signed S there, DESIGN.md 4b-wrap, tests/test_gpu_sgbm_wrap.py).
 template <bool NW>
 __device__ __forceinline__ void sgm_pair(uint32_t lp, uint32_t nb, uint32_t delta2, uint32_t p1x2,
                                          uint32_t c, uint32_t& ln, uint32_t& tu)
@@ -449,12 +452,22 @@ __device__ __forceinline__ void sgm_step_row_t(const uint32_t (&lp)[NP], uint32_
     // d-1 / d+1 neighbours across the lane boundary: zero-filled DPP shifts
     // (bound_ctrl) OR'ed with MAX at the segment ends fold into v_or_b32_dpp
     // (an 8-lane segment's first lane receives the previous segment's last
-    // lane; the OR with MAX discards it: L values are in [0, 0x7fff])
+    // lane; the OR with MAX discards it: L values are in [0, 0x7fff] -- in the
+    // no-wrap form.  In the general form an L may be negative (a wrapped cost)
+    // and x | MAX would be -1, so the 8-lane segment ends select MAX instead.)
     const uint32_t rls = __lane_id() % LPC;
-    const uint32_t prev_hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[NP - 1], 0x111, 0xf, 0xf, true) |
-                             (rls == 0 ? MAXP : 0u);
-    const uint32_t next_lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[0], 0x101, 0xf, 0xf, true) |
-                             (rls == LPC - 1 ? MAXP : 0u);
+    uint32_t prev_hi, next_lo;
+    if constexpr (NW || LPC == 16) {
+        prev_hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[NP - 1], 0x111, 0xf, 0xf, true) |
+                  (rls == 0 ? MAXP : 0u);
+        next_lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[0], 0x101, 0xf, 0xf, true) |
+                  (rls == LPC - 1 ? MAXP : 0u);
+    } else {
+        const uint32_t sh_hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[NP - 1], 0x111, 0xf, 0xf, true);
+        prev_hi = rls == 0 ? MAXP : sh_hi;
+        const uint32_t sh_lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[0], 0x101, 0xf, 0xf, true);
+        next_lo = rls == LPC - 1 ? MAXP : sh_lo;
+    }
     uint32_t X[NP + 1];  // X[q + 1] = X_q, X[0] = X_{-1}
     X[0] = pk_min(prev_hi, lp[0]);
 #pragma unroll
@@ -505,12 +518,13 @@ __device__ __forceinline__ void sgm_step_seg_t(const uint32_t (&lp)[NP], uint32_
     } else {
         const uint32_t MAXP = 0x7fff7fffu;
         // zero-filled wave shifts (bound_ctrl) OR'ed with MAX at the segment
-        // ends (L values are in [0, 0x7fff], so x | MAXP == MAXP): one
+        // ends (no-wrap form: L values are in [0, 0x7fff], so x | MAXP == MAXP): one
         // v_or_b32_dpp per neighbour
-        const uint32_t prev_hi =
-            (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[NP - 1], 0x138, 0xf, 0xf, true) | (seg_first ? MAXP : 0u);
-        const uint32_t next_lo =
-            (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[0], 0x130, 0xf, 0xf, true) | (seg_last ? MAXP : 0u);
+        // (general form: an L of the other row's end lane may be negative, so select)
+        const uint32_t sh_hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[NP - 1], 0x138, 0xf, 0xf, true);
+        const uint32_t sh_lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)lp[0], 0x130, 0xf, 0xf, true);
+        const uint32_t prev_hi = NW ? (sh_hi | (seg_first ? MAXP : 0u)) : (seg_first ? MAXP : sh_hi);
+        const uint32_t next_lo = NW ? (sh_lo | (seg_last ? MAXP : 0u)) : (seg_last ? MAXP : sh_lo);
         uint32_t X[NP + 1];  // X[q + 1] = X_q, X[0] = X_{-1}
         X[0] = pk_min(prev_hi, lp[0]);
 #pragma unroll

@@ -266,6 +266,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NP >= 8 ? 1 
     // S = min(ndir*(C - P2) + sum of deltas, MAX_COST) = min((ndir-1)*cb + L + acc, MAX_COST)
     // with cb = C - P2, L = cb + delta of the R->L direction computed here
     const uint32_t ndm1 = (uint32_t)(sgbm_ndir(e) - 1) * 0x10001u;
+    // The general form (NOWRAP false) where a cost may pass 32767: C is a signed int16 as in
+    // OpenCV, S = clamp(ndir*(C - P2) + sum of deltas, -32768, MAX_COST) in int32 per half.
+    // (Every L of a pixel and disparity has C's sign -- L = C + t, t in [-P2, 0], C >= P2 or
+    // C < 0 -- so OpenCV's chain of saturating adds is this two-sided clamp of the sum.)  The
+    // general form carries S as a signed half everywhere: the key's high half, the records,
+    // the LDS row; the uniqueness minimum and the right-view keys take it biased by 32768.
+    const bool sgn = !NOWRAP && sgbm_signed_costs(e);
+    const int ndS = sgbm_ndir(e);
     const int uq = e.uniq;
     // tie order of the WTA key: d, or OpenCV's SIMD lane order for MODE_SGBM
     uint32_t subk[2 * NP];
@@ -334,18 +342,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NP >= 8 ? 1 
         sgm_step_seg_t<NP, LPR, NOWRAP>(lp, delta2, p1x2, c, ln, tt, seg_first, seg_last);
         minp = seg_min_i32<LPR>(lane_min_row<NP>(ln));
         AR::template combine<NACC>(ab[j], acc);
-        uint32_t key = 0x7fffffffu;
+        typename std::conditional<NOWRAP, uint32_t, int>::type key = 0x7fffffff;
 #pragma unroll
         for (int p = 0; p < NP; p++) {
-            // residual form (RESF): R >= P2, L + deltas <= 4 P2 + 7 P2 -- the
-            // full-rate 32-bit sub / add never borrow or carry
-            const uint32_t cbv = RESF ? sub2_nb(c[p], p2x2) : pk_sub_u16(c[p], p2x2);
-            const uint32_t sv = pk_mad_u16_clamp(cbv, ndm1, RESF ? add2_nc(ln[p], acc[p]) : pk_add_u16(ln[p], acc[p]));
-            st[p] = pk_min_u16(sv, 0x7fff7fffu);
+            if (sgn) {
+                auto one = [&](uint32_t cw, uint32_t tw, uint32_t aw) -> uint32_t {
+                    const int S32 = ndS * ((int)(int16_t)cw - e.P2) + (int)(aw & 0xffffu) + (int)(int16_t)tw + e.P2;
+                    return (uint32_t)max(min(S32, kMaxCost), -32768) & 0xffffu;
+                };
+                st[p] = one(c[p] & 0xffffu, tt[p] & 0xffffu, acc[p]) | (one(c[p] >> 16, tt[p] >> 16, acc[p] >> 16) << 16);
+            } else {
+                // residual form (RESF): R >= P2, L + deltas <= 4 P2 + 7 P2 -- the
+                // full-rate 32-bit sub / add never borrow or carry
+                const uint32_t cbv = RESF ? sub2_nb(c[p], p2x2) : pk_sub_u16(c[p], p2x2);
+                const uint32_t sv = pk_mad_u16_clamp(cbv, ndm1, RESF ? add2_nc(ln[p], acc[p]) : pk_add_u16(ln[p], acc[p]));
+                st[p] = pk_min_u16(sv, 0x7fff7fffu);
+            }
             lp[p] = ln[p];
             const uint32_t klo = (st[p] << 16) | subk[2 * p];
             const uint32_t khi = (st[p] & 0xffff0000u) | subk[2 * p + 1];
-            key = min(key, min(klo, khi));
+            if constexpr (NOWRAP)
+                key = min(key, min(klo, khi));
+            else
+                key = min(key, min((int)klo, (int)khi));  // a signed S in the high half
         }
         const int K = seg_min_i32<LPR>((int)key);
         const int minS = K >> 16;
@@ -362,7 +381,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NP >= 8 ? 1 
         // (without them it moved accesses across lanes' writes: wrong maps)
         __builtin_amdgcn_wave_barrier();
         const int bm = max(best - 1, 0), bp = min(best + 1, DR - 1);
-        const int Sm = ms[bm], Sp = ms[bp];
+        const int Sm = ms[bm], Sp = ms[bp];  // (16 bits go into the record; the flush sign-extends them)
         int rej = 0;
         if constexpr (UQ) {
             // min of S outside [best-1, best+1]: y = best + 1 - d is <= 2
@@ -373,13 +392,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NP >= 8 ? 1 
             for (int p = 0; p < NP; p++) {
                 const uint32_t yv = pk_sub_u16(b2, dpair[p]);
                 const uint32_t lift = pk_sub_u16(pk_min_u16(yv, 0x00030003u), 0x00030003u);
-                m2 = pk_min_u16(m2, pk_max_u16(st[p], lift));
+                if constexpr (NOWRAP)
+                    m2 = pk_min_u16(m2, pk_max_u16(st[p], lift));
+                else  // S biased by 32768 (order-preserving for a signed half); lifted cells to 0xffff
+                    m2 = pk_min_u16(m2, pk_max_u16(st[p] ^ 0x80008000u, lift | ((lift >> 1) & 0x7fff7fffu)));
             }
             const int m2r = seg_min_i32<LPR>((int)min(m2 & 0xffffu, m2 >> 16));
-            rej = m2r < 0xfffd && m2r * (100 - uq) < minS * 100;
+            if constexpr (NOWRAP)
+                rej = m2r < 0xfffd && m2r * (100 - uq) < minS * 100;
+            else  // (D >= 16: a cell outside [best-1, best+1] always exists)
+                rej = (m2r - 32768) * (100 - uq) < minS * 100;
         }
-        recs[s & (LPR - 1)] = make_uint2((uint32_t)K | ((uint32_t)rej << 31),
-                                  ((uint32_t)Sp << 16) | ((uint32_t)Sm & 0xffffu));
+        if constexpr (NOWRAP)
+            recs[s & (LPR - 1)] = make_uint2((uint32_t)K | ((uint32_t)rej << 31),
+                                      ((uint32_t)Sp << 16) | ((uint32_t)Sm & 0xffffu));
+        else  // bit 31 is S's sign: the verdict goes into bit 15 (sub has 15 bits)
+            recs[s & (LPR - 1)] = make_uint2(((uint32_t)K & 0xffff7fffu) | ((uint32_t)rej << 15),
+                                      ((uint32_t)Sp << 16) | ((uint32_t)Sm & 0xffffu));
         __builtin_amdgcn_wave_barrier();
     };
     // lane rl finishes column s0 + rl of the sweep (x = W1 - 1 - s)
@@ -400,17 +429,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NP >= 8 ? 1 
         *(own ? orow + x + minX1 : dslot) = v;
         const int x2 = x + minX1 - best - minD;
         const bool hit = own && !kRej && minS < kMaxCost && x2 >= 0 && x2 < W;
+        constexpr int kKeyBias = NOWRAP ? 0 : 32768;  // a signed minS orders as unsigned
         atomicMin(krow + clampi(x2, 0, W - 1),
-                  hit ? (((uint32_t)minS << 16) | (uint32_t)(0xffff - x)) : 0xffffffffu);
+                  hit ? (((uint32_t)(minS + kKeyBias) << 16) | (uint32_t)(0xffff - x)) : 0xffffffffu);
     };
     auto flush = [&](int s0, int cnt) {
         const int s = s0 + rl;
         const bool own = exists && rl < cnt;
         const uint2 rec = recs[rl];
         const uint32_t kK = rec.x & 0x7fffffffu, kS = rec.y;
-        const int kRej = (int)(rec.x >> 31);
-        const int minS = (int)(kK >> 16);
-        const int sub = (int)(kK & 0xffffu);
+        const int kRej = NOWRAP ? (int)(rec.x >> 31) : (int)((rec.x >> 15) & 1u);
+        const int minS = NOWRAP ? (int)(kK >> 16) : ((int)rec.x >> 16);
+        const int sub = NOWRAP ? (int)(kK & 0xffffu) : (int)(rec.x & 0x7fffu);
         const int best = lane_rule ? (((sub & 0xfff) << 3) | (sub >> 12)) : sub;
         const int Sm = (int)(int16_t)(kS & 0xffffu), Sp = (int)(int16_t)(kS >> 16);
         finish(own, W1 - 1 - s, best, minS, Sm, Sp, kRej);
@@ -580,6 +610,10 @@ __global__ __launch_bounds__(kWtaThreads) void sgbm_wta_planes_kernel(const int1
     __syncthreads();
     const bool lane_rule = !e.fullDP && !(e.variant & MVSV_VARIANT_WTA_MIN_D);
     const int ndir = sgbm_ndir(e);
+    // costs past 32767 are negative int16 as in OpenCV (sgbm_signed_costs): S is then signed,
+    // saturated on both sides, and the keys carry it biased by 32768
+    const bool sgn = sgbm_signed_costs(e);
+    const int bias = sgn ? 32768 : 0;
     const size_t row0 = ((size_t)f * H + y) * W1;
     const int sl = threadIdx.x % LPP, gbase = (int)(threadIdx.x & 63) - sl;  // lane in the pixel, its first lane
     const int d0 = 8 * sl;
@@ -594,8 +628,9 @@ __global__ __launch_bounds__(kWtaThreads) void sgbm_wta_planes_kernel(const int1
             int acc[8];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                acc[2 * i] = ndir * ((int)(cv[i] & 0xffffu) - e.P2);
-                acc[2 * i + 1] = ndir * ((int)(cv[i] >> 16) - e.P2);
+                const int clo = (int)(cv[i] & 0xffffu), chi = (int)(cv[i] >> 16);
+                acc[2 * i] = ndir * ((sgn ? (int)(int16_t)clo : clo) - e.P2);
+                acc[2 * i + 1] = ndir * ((sgn ? (int)(int16_t)chi : chi) - e.P2);
             }
             for (int k = 0; k < nplanes; k++) {
                 uint32_t dv[8];
@@ -604,7 +639,7 @@ __global__ __launch_bounds__(kWtaThreads) void sgbm_wta_planes_kernel(const int1
                 for (int i = 0; i < 8; i++) acc[i] += (int)dv[i];
             }
 #pragma unroll
-            for (int i = 0; i < 8; i++) S[i] = min(acc[i], kMaxCost);
+            for (int i = 0; i < 8; i++) S[i] = max(min(acc[i], kMaxCost), -bias);
         }
         // argmin, ties in OpenCV's order (d, or MODE_SGBM's SIMD lane d mod 8 first)
         uint32_t key = 0xffffffffu;
@@ -612,11 +647,11 @@ __global__ __launch_bounds__(kWtaThreads) void sgbm_wta_planes_kernel(const int1
         for (int i = 0; i < 8; i++) {
             const int d = d0 + i;
             const uint32_t sub = lane_rule ? (uint32_t)((i << 12) | (d >> 3)) : (uint32_t)d;
-            key = min(key, ((uint32_t)S[i] << 16) | sub);
+            key = min(key, ((uint32_t)(S[i] + bias) << 16) | sub);
         }
 #pragma unroll
         for (int m = 1; m < LPP; m <<= 1) key = min(key, (uint32_t)__shfl_xor((int)key, m, 64));
-        const int minS = (int)(key >> 16), sub = (int)(key & 0xffffu);
+        const int minS = (int)(key >> 16) - bias, sub = (int)(key & 0xffffu);
         const int best = lane_rule ? (((sub & 0xfff) << 3) | (sub >> 12)) : sub;
         const int bm = max(best - 1, 0), bp = min(best + 1, D - 1);
         auto elem = [&](int d) -> int {  // S[d & 7] of this lane
@@ -647,7 +682,7 @@ __global__ __launch_bounds__(kWtaThreads) void sgbm_wta_planes_kernel(const int1
             orow[x + minX1] = rej ? (int16_t)INV : (int16_t)(d16 + minD * kDispScale);
             const int x2 = x + minX1 - bst - minD;
             if (!rej && minS < kMaxCost && x2 >= 0 && x2 < W)
-                atomicMin(krow + x2, ((uint32_t)minS << 16) | (uint32_t)(0xffff - x));
+                atomicMin(krow + x2, ((uint32_t)(minS + bias) << 16) | (uint32_t)(0xffff - x));
         }
     }
     __threadfence_block();

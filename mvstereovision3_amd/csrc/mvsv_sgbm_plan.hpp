@@ -144,6 +144,18 @@ inline bool sgbm_no_wrap(const SgbmEff& e)
     return (long)e.P2 + bs * bs * sgbm_max_pixel_cost(e) + e.P2 <= 32767;
 }
 
+// The same bound for the kernels (device code): a cost may pass 32767.  OpenCV
+// keeps such a cost as a wrapped -- negative -- int16: its path costs are
+// negative with it, S saturates at -32768 on that side too, and the disparity
+// wins the WTA.  The final kernels then read C as signed and carry a signed S
+// (DESIGN.md 4b-wrap); where this is false the unsigned and the signed reading
+// of a cost are the same number and the kernels keep their unsigned forms.
+MVSV_HD inline bool sgbm_signed_costs(const SgbmEff& e)
+{
+    const long bs = 2L * e.SW2 + 1;
+    return (long)e.P2 + bs * bs * sgbm_max_pixel_cost(e) + e.P2 > 32767;
+}
+
 // u8 accumulator when the summed path deltas (each <= P2) fit a byte
 MVSV_HD inline bool acc_is_u8(const SgbmEff& e) { return sgbm_ndir(e) * e.P2 <= 255; }
 // 4-bit accumulator planes: the sheared-strip schedule writes one plane per

@@ -22,6 +22,14 @@ static inline int imin(int a, int b) { return a < b ? a : b; }
 static inline int imax(int a, int b) { return a > b ? a : b; }
 static inline int iabs(int a) { return a < 0 ? -a : a; }
 static inline int sat16(int v) { return v > 32767 ? 32767 : (v < -32768 ? -32768 : v); }
+/* The running update of a cost row, C(y) = C(y-1) - hsum(y-SH2-1) + hsum(y+SH2): OpenCV's
+ * SIMD build subtracts and adds with saturation, its non-SIMD build casts the int sum
+ * (ORC_F_COST_WRAP).  The two part only once a cost leaves int16. */
+static inline int16_t cost_update(int cprev, int hsub, int hadd, unsigned flags)
+{
+    if (flags & ORC_F_COST_WRAP) return (int16_t)(uint16_t)(cprev - hsub + hadd);
+    return (int16_t)sat16(sat16(cprev - hsub) + hadd);
+}
 
 #define MAX_COST 32767
 #define DISP_SHIFT 4
@@ -228,7 +236,7 @@ static int sgbm_run(const uint8_t* L, ptrdiff_t ls, const uint8_t* R, ptrdiff_t 
                             const int16_t* Cprev = (!e.fullDP) ? C : C - row;
                             if (flags & ORC_F_FIRSTCOL_FIX)
                                 for (int d = 0; d < D; d++)
-                                    C[d] = (int16_t)sat16(sat16(Cprev[d] - hsub[d]) + hadd[d]);
+                                    C[d] = cost_update(Cprev[d], hsub[d], hadd[d], flags);
                             for (int x = 1; x < W1; x++) {
                                 const int16_t* padd = pix + (size_t)imin(x + SW2, W1 - 1) * D;
                                 const int16_t* psub = pix + (size_t)imax(x - SW2 - 1, 0) * D;
@@ -236,7 +244,7 @@ static int sgbm_run(const uint8_t* L, ptrdiff_t ls, const uint8_t* R, ptrdiff_t 
                                     int hv = (int16_t)(hadd[(size_t)(x - 1) * D + d] + padd[d] - psub[d]);
                                     hadd[(size_t)x * D + d] = (int16_t)hv;
                                     size_t i = (size_t)x * D + d;
-                                    C[i] = (int16_t)sat16(sat16(Cprev[i] - hsub[i]) + hv);
+                                    C[i] = cost_update(Cprev[i], hsub[i], hv, flags);
                                 }
                             }
                         } else {

@@ -28,6 +28,18 @@
  *                       ties (later releases); 3.4's SSE2 path picks the
  *                       lowest SIMD lane (d mod 8) among ties.
  * Default (flags = 0) is OpenCV 3.4 behaviour.
+ *
+ * A third switch follows OpenCV's build, not its release:
+ *   ORC_F_COST_WRAP     OpenCV's non-SIMD build: the running update of a cost row
+ *                       is the plain int sum cast to CostType,
+ *                       (int16_t)(Cprev - hsumSub + hsumAdd), a sum modulo 2^16.
+ *                       The SIMD build (the default here) computes
+ *                       sat16(sat16(Cprev - hsumSub) + hsumAdd); once a cost
+ *                       passes 32767 that clips, and the clipping error travels
+ *                       down the column.  The two agree on every input whose
+ *                       costs stay within int16.  A reference switch only: the
+ *                       engine's `variant` word has no such bit.  Paths, S, the
+ *                       WTA and the post-filters are the same under either.
  */
 #ifndef MVSV_ORACLE_H
 #define MVSV_ORACLE_H
@@ -41,6 +53,7 @@ extern "C" {
 
 #define ORC_F_FIRSTCOL_FIX 1u
 #define ORC_F_WTA_MIN_D    2u
+#define ORC_F_COST_WRAP    4u
 
 /* Raw OpenCV StereoSGBM parameters (cv::StereoSGBM::create argument order). */
 typedef struct {

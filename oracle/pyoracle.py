@@ -16,6 +16,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "build", "libmvsv_oracle.so")
 _lib = None
 
+# mvsv_oracle.h's flags; F_COST_WRAP is the reference's alone (no bit of the engine's variant word)
+F_FIRSTCOL_FIX, F_WTA_MIN_D, F_COST_WRAP = 1, 2, 4
+
 SGBM_FIELDS = ("min_disparity", "num_disparities", "block_size", "p1", "p2",
                "disp12_max_diff", "pre_filter_cap", "uniqueness_ratio",
                "speckle_window_size", "speckle_range", "mode")

@@ -26,6 +26,11 @@ import numpy as np
 MAX_COST = 32767
 F_FIRSTCOL_FIX = 1
 F_WTA_MIN_D = 2
+# The C oracle's ORC_F_COST_WRAP (the wrapping cost-row update of OpenCV's non-SIMD build).
+# sgbm_cost_volume here is the closed form in int32 and takes no such flag: its value
+# modulo 2^16 is the flagged oracle's volume; sgbm_core / sgbm_compute restate the paths
+# on costs within int16 only.
+F_COST_WRAP = 4
 
 
 def _sat16(a):

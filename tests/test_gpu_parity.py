@@ -64,6 +64,22 @@ def rand_pair(rng, H, W, shift, kind):
     return L, R
 
 
+def saw_pair(H, W, period, noise, seed, shift, fade):
+    """A pair whose SGBM costs leave int16: L a horizontal sawtooth, R its negative shifted by
+    `shift`, so that (preFilterCap 63) the x-Sobel channel sits near 126 in L and near 0 in R on
+    most columns and a pixel cost is near its ceiling.  `fade` scales the contrast of both by
+    linspace(0.2, 1, H) down the rows: the window sums then cross 32767 along a column, which is
+    where a saturating and a wrapping cost-row update part.  Uniform noise in [-noise, noise]."""
+    rng = np.random.default_rng(seed)
+    saw = (np.arange(W) % period) * (255 // (period - 1))
+    f = np.linspace(0.2, 1.0, H)[:, None] if fade else np.ones((H, 1))
+    L = np.broadcast_to(saw, (H, W)) * f
+    R = np.broadcast_to(255 - np.roll(saw, -shift), (H, W)) * f
+    L = np.clip(np.rint(L).astype(int) + rng.integers(-noise, noise + 1, (H, W)), 0, 255).astype(np.uint8)
+    R = np.clip(np.rint(R).astype(int) + rng.integers(-noise, noise + 1, (H, W)), 0, 255).astype(np.uint8)
+    return L, R
+
+
 # ---------------------------------------------------------------- SGBM -----
 @pytest.mark.parametrize("seed", range(24))
 def test_sgbm_random_small(gpu, mvsv, oracle, seed):

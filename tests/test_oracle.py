@@ -173,6 +173,50 @@ def test_sgbm_saturated_costs_invalid(oracle):
     assert (a == -80).any()
 
 
+# ------------------------------------- the wrapping cost update (ORC_F_COST_WRAP) -----
+# inputs of tests/sgbm_wrap_cases.py whose costs leave int16: the LDS-ring window, the register-ring
+# window under large and small P2, no fade, the double wrap
+WRAP_INPUTS = ("var0-mode0", "ring-D64-bs15", "dflt-D32-bs15-P5-s0-m0", "nofade-D16", "double-wrap", "odd-D128-H37")
+
+
+@pytest.mark.parametrize("name", WRAP_INPUTS)
+def test_cost_wrap_flag_is_the_twin_volume_mod_2_16(oracle, name):
+    """With ORC_F_COST_WRAP the oracle's running cost rows are the closed-form sums modulo
+    2^16, in both modes and under all four FIRSTCOL_FIX / WTA_MIN_D combinations; without it
+    (the saturating SIMD update) the volume differs on these inputs."""
+    from oracle import twin
+    from tests import sgbm_wrap_cases as wc
+    c = wc.case(name)
+    L, R, _ = wc.frames(c)[0]
+    for mode in (0, 1):
+        p = dict(c.params, mode=mode)
+        for flags in range(4):
+            T = twin.sgbm_cost_volume(L, R, p, flags)
+            assert T.max() > 32767
+            C = oracle.sgbm_cost_volume(L, R, p, flags | oracle.F_COST_WRAP)
+            assert C.dtype == np.int16 and np.array_equal(C, T.astype(np.int16)), (mode, flags)
+            assert not np.array_equal(oracle.sgbm_cost_volume(L, R, p, flags), C), (mode, flags)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_cost_wrap_flag_changes_nothing_within_int16(oracle, seed):
+    """Where the twin's volume stays <= 32767 the flag changes no int16 of the map or of
+    the volume (the two updates are the same function there)."""
+    from oracle import twin
+    rng = np.random.default_rng(300 + seed)
+    H, W, D = int(rng.integers(14, 40)), int(rng.integers(60, 110)), int(rng.choice([16, 32]))
+    p = dict(min_disparity=int(rng.integers(-3, 4)), num_disparities=D, block_size=int(rng.choice([5, 9, 11, 15])),
+             p1=int(rng.choice([2, 72, 300])), p2=int(rng.choice([5, 288, 4000])), disp12_max_diff=1,
+             pre_filter_cap=int(rng.choice([15, 63])), uniqueness_ratio=5, speckle_window_size=int(rng.choice([0, 20])),
+             speckle_range=2, mode=seed % 2)
+    L, R = _rand_pair(rng, H, W, int(rng.integers(0, 16)), seed % 3)
+    for flags in range(4):
+        assert twin.sgbm_cost_volume(L, R, p, flags).max() <= 32767
+        assert np.array_equal(oracle.sgbm_cost_volume(L, R, p, flags | oracle.F_COST_WRAP),
+                              oracle.sgbm_cost_volume(L, R, p, flags))
+        assert np.array_equal(oracle.sgbm(L, R, p, flags | oracle.F_COST_WRAP), oracle.sgbm(L, R, p, flags))
+
+
 def test_oracle_resize_linear_properties(oracle):
     """orc_resize_linear (cv::resize INTER_LINEAR restatement): factor 1 is the
     identity, a factor of 0.5 is the rounded 2x2 mean on whole blocks, and every

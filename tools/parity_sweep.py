@@ -4,7 +4,7 @@ shapes, parameters, OpenCV variants, frame batches and every launch-shape option
 GPU through the package and checked bit-exactly against the C oracle (test
 infrastructure; the oracle frames run on a process pool of host threads).
 
-Usage (GPU box):  python tools/parity_sweep.py [--sgbm 200] [--bm 200] [--seed 1]
+Usage (GPU box):  python tools/parity_sweep.py [--sgbm 200] [--bm 200] [--saw 0] [--seed 1]
 Prints one line per mismatch and a summary; exit status 1 on any mismatch.
 """
 import argparse
@@ -32,6 +32,19 @@ def rand_pair(rng, H, W, shift, kind):
     return L, R
 
 
+def saw_pair(H, W, period, noise, seed, shift, fade):
+    """tests.test_gpu_parity.saw_pair: a sawtooth against its shifted negative, faded down the rows --
+    a pair whose SGBM costs leave int16 under large windows or penalties."""
+    rng = np.random.default_rng(seed)
+    saw = (np.arange(W) % period) * (255 // (period - 1))
+    f = np.linspace(0.2, 1.0, H)[:, None] if fade else np.ones((H, 1))
+    L = np.broadcast_to(saw, (H, W)) * f
+    R = np.broadcast_to(255 - np.roll(saw, -shift), (H, W)) * f
+    L = np.clip(np.rint(L).astype(int) + rng.integers(-noise, noise + 1, (H, W)), 0, 255).astype(np.uint8)
+    R = np.clip(np.rint(R).astype(int) + rng.integers(-noise, noise + 1, (H, W)), 0, 255).astype(np.uint8)
+    return L, R
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sgbm", type=int, default=200)
@@ -44,6 +57,10 @@ def main():
                          "uniquenessRatio 0): random shapes, batches, schedules, bit-sliced on / off")
     ap.add_argument("--bits-large", type=int, default=0,
                     help="bit-sliced-regime cases at 640x480 / 1280x960, 1-8 frames")
+    ap.add_argument("--saw", type=int, default=0,
+                    help="SGBM cases on sawtooth pairs (blockSize 15-21, P2 up to 14112) whose costs pass 32767: "
+                         "checked against the oracle's wrapping cost update (ORC_F_COST_WRAP) where the twin's "
+                         "volume exceeds 32767 (DESIGN.md 4b-wrap)")
     a = ap.parse_args()
     import torch
 
@@ -105,6 +122,29 @@ def main():
             jobs.append((tag, got[j], pool.submit(pyoracle.sgbm, L, R, p, variant)))
     _lib.set_option(_lib.OPT_PATH_SCHEDULE, 0)
     _lib.set_option(_lib.OPT_STRIP_WAVES, 0)
+
+    from oracle import twin
+    for i in range(a.saw):  # costs that leave int16
+        D = int(rng.choice([16, 32, 48, 64, 128]))
+        H, W = int(rng.integers(24, 52)), D + int(rng.integers(60, 130))
+        bs = int(rng.choice([15, 17, 19, 21]))
+        P1, P2 = [(2, 5), (8, 100), (100, 3000), (600, 9000), (300, 14112)][int(rng.integers(0, 5))]
+        kw = dict(minDisparity=int(rng.choice([-2, 0, 3])), numDisparities=D, blockSize=bs, P1=P1, P2=P2,
+                  disp12MaxDiff=int(rng.choice([-1, 1])), preFilterCap=63, uniquenessRatio=int(rng.choice([0, 5])),
+                  speckleWindowSize=0, speckleRange=1, mode=int(rng.integers(0, 2)))
+        variant = int(rng.integers(0, 4))
+        sched = int(rng.choice([0, 1, 2]))
+        L, R = saw_pair(H, W, int(rng.choice([6, 8])), 20, int(rng.integers(0, 1 << 30)), int(rng.integers(0, 6)),
+                        int(rng.integers(0, 4)) > 0)
+        m = mvsv.StereoSGBM.create(**kw)
+        m.setVariant(variant)
+        _lib.set_option(_lib.OPT_PATH_SCHEDULE, sched)
+        got = m.compute(L, R)
+        p = {k: v for k, v in m.params().items() if k != "variant"}
+        wraps = int(twin.sgbm_cost_volume(L, R, p, variant).max()) > 32767
+        tag = f"saw #{i} {H}x{W} {kw} variant={variant} sched={sched} wraps={wraps}"
+        jobs.append((tag, got, pool.submit(pyoracle.sgbm, L, R, p, variant | (pyoracle.F_COST_WRAP if wraps else 0))))
+    _lib.set_option(_lib.OPT_PATH_SCHEDULE, 0)
 
     for i in range(a.large):  # batch shapes: wide strips, lines after the strips
         W, H = (640, 480) if rng.integers(0, 3) else (1280, 960)
